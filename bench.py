@@ -7,13 +7,18 @@ BASELINE.md §3 specifies), both players' int8 code-plane observations are writt
 replaced by fresh ones.  Workload = BASELINE.json configs[2]'s env side: 65 536 parallel 24x24 envs per
 GPU, mode=None.
 
-The timed region (K steps, bracketed by barrier + synchronize, MAX over ranks) is repeated R times
-(--repeats, default 5); `value` is the median repeat, min / max are in the line.  Order: W warm-up steps, the
-K steps timed as they are then (`cold_start`: the chip was idle before the warm-up), --settle-steps further
-untimed steps (the same launches, back to back), then the R timed regions of the headline.  Further records ride
-on the same line: `per_step_launches` (the same K steps as one kernel launch per step — what a caller that
-supplies actions every step gets) and `dqn` (DDQN.train at BASELINE configs[1]: env-steps/s with the
-epsilon-greedy CNN policy in the loop and transitions/s consumed by learn()).
+A plain run (`bench.py --steps K --warmup W`) does what the headline needs and no more: W warm-up steps,
+--settle-steps further untimed steps (the same launches, back to back, so that the timed steps see a chip under
+load), then ONE timed region of exactly K steps (bracketed by barrier + synchronize, MAX over ranks).
+`ms_per_step` is that region's wall time / K.  --dump-outputs DIR then writes what the timed path computed in
+its last step (a fixed, seeded sample of the observation buffer and every env's sums, as .npy files).
+
+--full adds every secondary record, as before: the timed region is repeated R times (--repeats, default 5 with
+--full; `value` is the median repeat, min / max are in the line), and the K steps are also timed right after the
+warm-up (`cold_start`: the chip was idle before it).  Further records ride on the same line: `per_step_launches`
+(the same K steps as one kernel launch per step — what a caller that supplies actions every step gets),
+`resident_rollout`, `temper`, `dqn` / `dqn_config3` (DDQN.train at BASELINE configs[1] / [2]: env-steps/s with
+the epsilon-greedy CNN policy in the loop and transitions/s consumed by learn()) and `cpu_baseline`.
 
 Multi-GPU: envs are independent, so each rank owns its own 65 536 envs and its own Philox stream (weak
 scaling, no data-path collective); the DQN record adds the one real exchange, the gradient all-reduce.
@@ -149,6 +154,25 @@ def net_forward_flops(width, in_channels=3):
     f += 2 * o * o * 64 * 64 * 49
     f += 2 * (64 * o * o * 256 + 256 * 128 + 128 * 64 + 64 * 4)
     return f
+
+
+def dump_outputs(out_dir, env, budget=48 << 20):
+    """--dump-outputs: what the timed rollout hands its caller after its last step, the observation buffer env.obs
+    (both players' int8 codes or f32 planes, [N, 2, ...]), as .npy files: `obs` (float32) holds the whole
+    observations of a fixed, seeded sample of envs within `budget` bytes, `obs_envs` (float64) their indices, and
+    `obs_env_sums` (float64 [N, 2]) each player's observation summed, for every env."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    obs = env.obs
+    n = obs.shape[0]
+    k = min(n, max(1, budget // (obs[0].numel() * 4)))
+    idx = np.sort(np.random.default_rng(0x5EED).choice(n, size=k, replace=False)) if k < n else np.arange(n)
+    sample = obs.index_select(0, torch.as_tensor(idx, device=obs.device)).float().cpu().numpy()
+    sums = obs.reshape(n, 2, -1).sum(-1, dtype=torch.float64).cpu().numpy()
+    np.save(os.path.join(out_dir, "obs.npy"), sample)
+    np.save(os.path.join(out_dir, "obs_envs.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "obs_env_sums.npy"), sums)
 
 
 def max_over_ranks(x, world):
@@ -316,13 +340,20 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=320)     # multiples of the rollout's 64 steps per launch
     ap.add_argument("--warmup", type=int, default=64)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; value = median")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every secondary record (cold_start, per_step_launches, resident_rollout, temper, "
+                         "dqn, dqn_config3, cpu_baseline) and repeat the timed region (--repeats, default 5)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; value = median (default 1; 5 with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy "
+                         "(float32 / float64): a fixed, seeded sample of rank 0's observation buffer and every env's sums")
     ap.add_argument("--envs", type=int, default=None, help="envs per GPU (default 65536; --dqn: 4096)")
     ap.add_argument("--width", type=int, default=None, help="board side (default 24; --dqn: 10)")
     ap.add_argument("--obs", default="codes", choices=["codes", "planes3", "planes4"])
     ap.add_argument("--mode", default="none", choices=["none", "ice", "temper"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-dqn", action="store_true", help="skip the DQN transitions/s record")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline record")
+    ap.add_argument("--no-dqn", action="store_true", help="--full: skip the DQN transitions/s records")
     ap.add_argument("--incremental", action="store_true",
                     help="secondary variant: in-place observation update (only touched cells and restarted boards "
                          "are written); reported under its own label, not comparable with the default line")
@@ -338,10 +369,10 @@ def main():
     ap.add_argument("--acktr-iterations", type=int, default=5, help="ACKTR record: timed iterations (5 = 10 updates = one period of the eigendecompositions, Tf = 10)")
     ap.add_argument("--dqn3-steps", type=int, default=8, help="config-3 DQN record (65 536 envs x 24x24): env steps per timed region")
     ap.add_argument("--settle-steps", type=int, default=6400,
-                    help="untimed steps (in launches of --steps) run after the --warmup steps and before the timed regions, so that "
+                    help="untimed steps (in launches of --steps, at most --settle-steps each) run after the --warmup steps and before the timed regions, so that "
                          "the timed K steps see the clocks of a chip under load: from an idle chip the same launch is 5-12 %% slower "
-                         "for the first tens of milliseconds (scripts/roll_fixed_cost.sh).  The K steps timed right after --warmup "
-                         "alone are reported beside the headline as `cold_start`; 0 = skip (the headline is then the cold figure)")
+                         "for the first tens of milliseconds (scripts/roll_fixed_cost.sh).  With --full the K steps timed right after "
+                         "--warmup alone are reported beside the headline as `cold_start`; 0 = skip (the headline is then the cold figure)")
     ap.add_argument("--only-rollout", action="store_true",
                     help="profiling runs: the warm-up and the timed persistent-rollout launches only (no per-step, two-stream "
                          "or resident passes, no temper / DQN / CPU records), so that every dispatch of the step kernel in a "
@@ -355,6 +386,11 @@ def main():
     ap.add_argument("--dqn-envs", type=int, default=4096)
     ap.add_argument("--dqn-width", type=int, default=10)
     args = ap.parse_args()
+    headline = not (args.config1 or args.acktr or args.dqn)
+    if args.repeats is None:
+        args.repeats = 1 if headline and not args.full else 5
+    if args.dump_outputs and not headline:
+        ap.error("--dump-outputs covers the env-step headline, not --config1 / --acktr / --dqn")
 
     import torch
     import torch.distributed as dist
@@ -471,14 +507,14 @@ def main():
                 env.rollout_random(k, nonreversing=nonrev, per_step_launches=per_step, two_streams=two, resident=resident)
         run(args.warmup)
 
-        def timed_regions(n):
+        def timed_regions(n, k=args.steps):
             w, d = [], []
             for _ in range(n):
                 ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 barrier()
                 t0 = time.perf_counter()
                 ev0.record()                       # same stream the kernels are launched on
-                run(args.steps)
+                run(k)
                 ev1.record()
                 barrier()
                 w.append(max_over_ranks(time.perf_counter() - t0, world))
@@ -486,13 +522,20 @@ def main():
             return w, d
         cold_walls, cold_ms, settled = None, None, 0
         if args.settle_steps > args.warmup:
-            cold_walls, cold_ms = timed_regions(max(1, min(args.repeats, 3)))
-            while settled < args.settle_steps:     # the same launches as the timed ones, back to back, untimed
-                run(args.steps)
-                settled += args.steps
+            if args.full:
+                cold_walls, cold_ms = timed_regions(max(1, min(args.repeats, 3)))
+            settle_k = min(args.steps, args.settle_steps)
+            while settled < args.settle_steps:     # the same launches as the timed ones, back to back, untimed; the last one
+                if settled + settle_k < args.settle_steps:  # bracketed like a timed region: the first region after a synchronised train
+                    run(settle_k)                  # of launches runs ~8 % slower at 20 steps, on the device too
+                else:
+                    timed_regions(1, settle_k)
+                settled += settle_k
         walls, dev_ms = timed_regions(max(1, args.repeats))
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, env)
         # the same K steps as one launch per step (what a caller that supplies actions every step gets)
-        if not args.incremental and not args.only_rollout and not os.environ.get("TRON_ROLL_PER_STEP"):
+        if args.full and not args.incremental and not args.only_rollout and not os.environ.get("TRON_ROLL_PER_STEP"):
             run(min(args.warmup, 16), True)
             for _ in range(max(1, args.repeats)):
                 ev2, ev3 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -533,7 +576,7 @@ def main():
 
     # a sliding mode beside the headline ("temper" as a secondary row): the same K steps on k_obs_roll_slide
     temper = None
-    if args.mode == "none" and args.obs == "codes" and not args.incremental and not args.only_rollout and not nonrev:
+    if args.full and args.mode == "none" and args.obs == "codes" and not args.incremental and not args.only_rollout and not nonrev:
         tenv = VecTron(args.envs, args.width, mode="temper", seed=0x5EED, rank=rank, obs_format="codes")
         tenv.reset()
         t_ms = []
@@ -560,7 +603,7 @@ def main():
                                           if args.width % 2 == 0 else "k_tile_roll (persistent rollout, board-owning layout)")}}
 
     dqn = dqn3 = None
-    if not args.no_dqn and not args.incremental and not args.only_rollout:
+    if args.full and not args.no_dqn and not args.incremental and not args.only_rollout:
         env.close()
         del env
         env = None
@@ -692,7 +735,7 @@ def main():
             out["dqn"] = dqn
         if dqn3 is not None:
             out["dqn_config3"] = dqn3
-        if world == 1 and not args.no_cpu_baseline and not args.only_rollout:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.only_rollout:
             out["cpu_baseline"] = cpu_baseline(args.width)
         print(json.dumps(out), flush=True)
 

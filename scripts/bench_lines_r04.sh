@@ -3,7 +3,7 @@
 set -uo pipefail
 O=gpurun_out/r04/lines
 mkdir -p "$O"
-run() { local name=$1; shift; python bench.py "$@" > "$O/$name.json" 2> "$O/$name.err" || echo "$name failed"; tail -c 300 "$O/$name.err" | grep -i "error\|traceback" || true; }
+run() { local name=$1; shift; python bench.py --full "$@" > "$O/$name.json" 2> "$O/$name.err" || echo "$name failed"; tail -c 300 "$O/$name.err" | grep -i "error\|traceback" || true; }
 run r04_bench
 run r04_bench_driver_invocation --steps 20 --warmup 5
 run r04_bench_nonreversing --no-dqn --no-cpu-baseline --actions nonreversing

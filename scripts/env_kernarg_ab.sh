@@ -4,7 +4,7 @@
 # compiled and linked against build/*.o (as scripts/ws_ablate.sh does for the conv kernels).  Prints value / roofline.frac /
 # kernel_ms of `bench.py --no-dqn --no-cpu-baseline` at the driver's 20-step invocation (three rounds, interleaved), at the
 # default 320 steps, and in temper mode.  Used for the kernel-argument re-read of k_obs_roll.
-run() { python3 bench.py --steps $2 --warmup $3 --no-dqn --no-cpu-baseline $4 2>/dev/null | python3 -c "
+run() { python3 bench.py --full --steps $2 --warmup $3 --no-dqn --no-cpu-baseline $4 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$1', $2, '$4', d['value'], r['frac'], r['kernel_ms'])"; }

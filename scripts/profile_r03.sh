@@ -4,7 +4,7 @@ set -uo pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r03/prof
 mkdir -p "$O"
-B="python3 bench.py --no-cpu-baseline --no-dqn --steps 20 --warmup 5"
+B="python3 bench.py --full --no-cpu-baseline --no-dqn --steps 20 --warmup 5"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace20" -- $B > "$O/trace20.log" 2>&1 || echo "trace20 failed"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/fetch20" -- $B > "$O/fetch20.log" 2>&1 || echo "fetch20 failed"
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$O/write20" -- $B > "$O/write20.log" 2>&1 || echo "write20 failed"

@@ -11,8 +11,8 @@ if [[ $PART == *A* ]]; then
   recs=()
   for cfg in "plain 20 5" "plain 64 64" "resident 20 5"; do
     set -- $cfg
-    B="python3 bench.py --only-rollout --rollout-variant $1 --no-cpu-baseline --no-dqn --steps $(( $2 * 5 )) --warmup $3 --repeats 2"
-    [[ $2 == 20 ]] && B="python3 bench.py --only-rollout --rollout-variant $1 --no-cpu-baseline --no-dqn --steps 20 --warmup $3 --repeats 6"
+    B="python3 bench.py --full --only-rollout --rollout-variant $1 --no-cpu-baseline --no-dqn --steps $(( $2 * 5 )) --warmup $3 --repeats 2"
+    [[ $2 == 20 ]] && B="python3 bench.py --full --only-rollout --rollout-variant $1 --no-cpu-baseline --no-dqn --steps 20 --warmup $3 --repeats 6"
     t=$1_$2
     rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace_$t" -- $B > "$O/trace_$t.log" 2>&1 || echo "trace_$t failed"
     rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/fetch_$t" -- $B > "$O/fetch_$t.log" 2>&1 || echo "fetch_$t failed"
@@ -23,7 +23,7 @@ if [[ $PART == *A* ]]; then
   python3 scripts/kstats.py "$O/trace_plain_20" --filter k_obs > "$O/r04_kernel_trace_rollout_20.txt" 2>&1
   cp $(ls "$O"/trace_plain_20/*/*kernel_stats.csv | head -1) "$O/r04_kernel_stats_rollout_20.csv" 2>/dev/null
   # the driver's own invocation (everything bench.py launches), kernel trace + stats
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace_driver" -- python3 bench.py --no-cpu-baseline --no-dqn --steps 20 --warmup 5 > "$O/trace_driver.log" 2>&1 || echo "trace_driver failed"
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace_driver" -- python3 bench.py --full --no-cpu-baseline --no-dqn --steps 20 --warmup 5 > "$O/trace_driver.log" 2>&1 || echo "trace_driver failed"
   python3 scripts/kstats.py "$O/trace_driver" --filter k_ > "$O/r04_kernel_trace_driver_invocation.txt" 2>&1
   cp $(ls "$O"/trace_driver/*/*kernel_stats.csv | head -1) "$O/r04_kernel_stats_driver_invocation.csv" 2>/dev/null
 fi

@@ -14,7 +14,7 @@ for combo in combos:
         env["TRON_ROLL_GRID"] = str(g)
     if len(combo) > 2:
         env["TRON_ROLL_CHUNK"] = str(combo[2])
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--steps", "640", "--warmup", "64"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--steps", "640", "--warmup", "64"],
                          env=env, capture_output=True, text=True).stdout.strip().splitlines()
     d = json.loads(out[-1])
     print(f"E={e:3d} grid={g or 'auto':>5} chunk={combo[2] if len(combo) > 2 else 64:4d}  {d['ms_per_step'] * 1e3:7.2f} us/step  {d['value'] / 1e9:6.3f} G env-steps/s  frac {d['roofline']['frac']:.3f}",

@@ -5,7 +5,7 @@ set -uo pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r04/temper_pmc
 mkdir -p "$O"
-B="python3 bench.py --only-rollout --mode temper --no-cpu-baseline --no-dqn --steps 64 --warmup 64 --repeats 3 --settle-steps 1280"
+B="python3 bench.py --full --only-rollout --mode temper --no-cpu-baseline --no-dqn --steps 64 --warmup 64 --repeats 3 --settle-steps 1280"
 rocprofv3 --kernel-trace --output-format csv -d "$O/trace" -- $B > "$O/trace.log" 2>&1 || echo trace failed
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/fetch" -- $B > "$O/fetch.log" 2>&1 || echo fetch failed
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$O/write" -- $B > "$O/write.log" 2>&1 || echo write failed

@@ -67,12 +67,12 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
 
 @pytest.mark.timeout(900)
 def test_driver_invocation_two_ranks_with_the_dqn_records():
-    """The driver's own multi-rank command line (`bench.py --gpus N --steps 20 --warmup 5`: headline, cold / settled regions, temper,
-    and the two DDQN records with their per-learn-step gradient all-reduce, deferred update and the one-launch optimizer) with two
-    ranks on one GPU: both ranks exit 0, rank 0 prints the one line, no record carries an error."""
+    """The driver's multi-rank command line with every record (`bench.py --gpus N --steps 20 --warmup 5 --full`: headline,
+    cold / settled regions, temper, and the two DDQN records with their per-learn-step gradient all-reduce, deferred update and
+    the one-launch optimizer) with two ranks on one GPU: both ranks exit 0, rank 0 prints the one line, no record carries an error."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    outs = _spawn(2, ["bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5"], timeout=800)
+    outs = _spawn(2, ["bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5", "--full"], timeout=800)
     lines = [ln for ln in outs[0][1].splitlines() if ln.startswith("{")]
     assert len(lines) == 1 and not [ln for ln in outs[1][1].splitlines() if ln.startswith("{")]
     rec = json.loads(lines[0])
