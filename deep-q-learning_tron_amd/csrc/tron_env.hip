@@ -28,7 +28,8 @@
 //   k_obs / obs_tile        observation-is-state (mode None, int8 codes, even side): the caller's
 //                           attached obs buffer is the env state; read G, write 2G per env-step
 //   k_obs_roll, k_tile_roll tron_rollout_random: the same per-tile step, but each workgroup steps
-//                           its own tile up to TRON_ROLLOUT_CHUNK times in ONE launch
+//                           its own tile up to TRON_ROLLOUT_CHUNK times in ONE launch (k_obs_roll: memory
+//                           is read in the first step only, roll_resident; k_obs_roll_walk / _slide: obs_tile)
 //   k_inc                   TRON_STEP_INCREMENTAL: writes only the touched cells + restarted boards
 //   k_reset, k_obs_reset, k_obs_to_grid, k_obs_planes, k_get_state, k_encode_codes, k_pop_up, ...
 //                           resets, read-back and stateless encodes
@@ -818,8 +819,8 @@ __device__ inline void lane_move_codes_slide(const Params &P, unsigned char *g, 
 }
 
 // One tile of E envs through one step; `smem` is the workgroup's dynamic LDS.  Shared by k_obs (one
-// tile per workgroup per launch) and k_obs_roll (workgroups that keep stepping their own tiles).
-// keep_tile (persistent rollout, TRON_ROLLOUT_RESIDENT): the tile's LDS copy is left exactly as the next step needs
+// tile per workgroup per launch) and k_obs_roll_walk / k_obs_roll_slide (workgroups that keep stepping their own tiles).
+// keep_tile (k_obs_roll_slide, TRON_ROLLOUT_RESIDENT): the tile's LDS copy is left exactly as the next step needs
 // it (restarted boards are written back to it); have_tile: it already is, so the tile is not loaded again.
 template <bool DO_STEP, bool SLIDING = false>
 __device__ __forceinline__ void obs_tile(const Params &P, int E, uint32_t cpe, uint32_t cpe_magic,
@@ -1017,13 +1018,199 @@ __global__ __launch_bounds__(BLOCK) void k_obs_slide(Params P, int E, uint32_t c
     obs_tile<true, true>(P, E, cpe, cpe_magic, actions, flags, out, (int)blockIdx.x + tile0, smem, false, false, uniforms);
 }
 
+// load_params for a loop that must not issue a vector-memory load: the source is typed as 32-bit words, so the copy is
+// known to be dword-aligned and becomes s_load_dwordx4/x8 (lgkmcnt).  Through kernarg_t's byte pointer the same copy is
+// taken for unaligned and comes out as global_load_dwordx4 + v_readfirstlane: vmcnt, behind every store the wave has issued.
+typedef __attribute__((address_space(4))) const uint32_t kernarg_words_t;
+__device__ __forceinline__ void load_params_scalar(Params &p, kernarg_t *kp)
+{
+    kernarg_words_t *q = reinterpret_cast<kernarg_words_t *>(kp);
+    asm volatile("" : "+s"(q));                                     // (a pointer the compiler cannot see through)
+    __builtin_memcpy(&p, q, sizeof(Params));
+}
+
+// The steps of a persistent launch that owns its tile (k_obs_roll, one tile per workgroup): nobody else touches the
+// tile's planes or state words during the launch, so everything a step reads is carried in LDS from the step before —
+// the board (tile), st4 (rec_st), rs4 (rs_in), the speculative next start (rec_rs) and the fresh-board template (tmpl).
+// Memory is read in the prologue only.  That is G bytes per env-step less to fetch, and it is what lets the stores run
+// on: vmcnt counts a wave's loads and stores in issue order, so ONE global load per step (obs_tile issues three: st4 /
+// rs4, the template's P.fresh, the tile) makes the wave wait for all its plane stores of the step before.  Every step
+// still writes both planes of every env in full; st4 / rs4 are written by the launch's last step (same bytes as one
+// store per step leaves behind).  The random-number work that obs_tile hides under the tile load runs here in waves
+// that would idle: wave 1 draws the next start (make_game) while wave 0 moves — and only for envs whose rs4 changed,
+// i.e. after a restart — and wave 0 draws the Philox words of step s + 1 (its tick is known once step s has moved)
+// behind its share of the stream of step s, while the stores are on their way.
+__device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, uint32_t cpe, uint32_t cpe_magic, uint32_t flags,
+                                              const StepOut &out, unsigned long long *acc, int k_steps, unsigned char *smem)
+{
+    uint4 *tile = reinterpret_cast<uint4 *>(smem);                  // the LDS layout of obs_tile
+    uint4 *tmpl = tile + (size_t)E * cpe;
+    uint4 *rec_st = tmpl + cpe;                                     // [E] st4, carried
+    uint4 *rec_out = rec_st + E;                                    // [E] this step's result record
+    uint4 *rec_rs = rec_out + E;                                    // [E] rs4 after the env's next restart
+    uint4 *rs_in = rec_rs + E;                                      // [E] rs4, carried
+
+    const int tid = threadIdx.x;
+    const int wave = tid >> 6, lane = tid & 63;
+    const bool autoreset = (flags & TRON_STEP_AUTORESET) != 0u, nonrev = (flags & TRON_STEP_NONREVERSING) != 0u;
+    const int e0 = (int)blockIdx.x * E;
+    const int env = e0 + lane;
+    int ne;
+    uint32_t nchunks;
+    int8_t *otile;
+    uint32_t x0 = 0u, x1 = 0u;                                      // wave 0: the Philox words of the coming step's actions
+    bool st_dirty = false, rs_dirty = false, rs_fresh = true;       // wave 0 / wave 1 / wave 1: rec_rs is to be drawn from rs_in
+
+    // ---- prologue: the only loads from memory of the launch
+    {
+        Params P;
+        load_params_scalar(P, kp);
+        const int G = P.G;
+        ne = min(E, P.N - e0);
+        nchunks = (uint32_t)ne * cpe;
+        otile = P.obs_state + (size_t)e0 * 2u * G;
+        uint4 st = make_uint4(0u, 0u, 0u, 0u);
+        if (lane < ne) {
+            if (wave == 0) st = P.st4[env];
+            else if (wave == 1 && autoreset) st = P.rs4[env];
+        }
+        if (autoreset)
+            for (uint32_t d = (uint32_t)tid; d < cpe * 16u; d += BLOCK)
+                reinterpret_cast<int8_t *>(tmpl)[d] = (d < (uint32_t)G) ? (P.fresh[d] == TRON_EMPTY ? (int8_t)1 : (int8_t)-1) : (int8_t)0;
+        for (uint32_t base = 0; base < nchunks; base += DK * BLOCK) {
+            uint4 v[DK];
+#pragma unroll
+            for (int k = 0; k < DK; ++k) {
+                const uint32_t i = base + (uint32_t)tid + (uint32_t)k * BLOCK;
+                const uint32_t le = chunk_env(i, cpe, cpe_magic);
+                if (i < nchunks) v[k] = load_chunk<true>(otile + (size_t)le * 2u * G + (i - le * cpe) * 16u);   // player-1 plane
+            }
+#pragma unroll
+            for (int k = 0; k < DK; ++k) {
+                const uint32_t i = base + (uint32_t)tid + (uint32_t)k * BLOCK;
+                if (i < nchunks) tile[i] = v[k];
+            }
+        }
+        if (lane < ne) {
+            if (wave == 0) {
+                rec_st[lane] = st;
+                uint32_t x[4];
+                philox4x32_10((uint32_t)env, st.w, RNG_STEP, 0u, P.seed, P.stream, x);
+                x0 = x[0];
+                x1 = x[1];
+            } else if (wave == 1 && autoreset) {
+                rs_in[lane] = st;
+            }
+        }
+    }
+    __syncthreads();
+
+    for (int s = 0; s < k_steps; ++s) {
+        Params P;                                                   // re-read per step: see k_obs_roll
+        load_params_scalar(P, kp);
+        const int G = P.G;
+        const bool last = s + 1 == k_steps;
+
+        // ---- the move: wave 0, one env per lane; beside it wave 1 draws the next starts that are due
+        if (wave == 0) {
+            uint4 ro = make_uint4(0u, 0u, 0u, 0u);
+            if (lane < ne) {
+                const uint4 st = rec_st[lane];
+                EnvRegs R{};
+                R.pos = st.x; R.meta = st.y; R.eplen = st.z; R.tick = st.w;
+                if (autoreset) R.nstart = rs_in[lane].z;
+                const int a[2] = {draw_action(x0, (R.meta >> 8) & 0xFu, nonrev), draw_action(x1, (R.meta >> 12) & 0xFu, nonrev)};
+                uint4 rst;
+                lane_move_codes(P, reinterpret_cast<unsigned char *>(tile + (size_t)lane * cpe), R, a, flags, rst, ro);
+                if (ro.x & RES_STORE_ST) {
+                    rec_st[lane] = rst;
+                    st_dirty = true;
+                }
+            }
+            if (lane < E) rec_out[lane] = ro;
+        } else if (wave == 1 && autoreset && lane < ne && rs_fresh) {
+            const uint4 rs = rs_in[lane];
+            const NewGame ng = make_game(P.seed, P.stream, P.W, P.fair, (uint32_t)env, rs.y + 1u);
+            rec_rs[lane] = make_uint4(rs.w, rs.y + 1u, pack_pos(ng.r1, ng.c1, ng.r2, ng.c2), pack_envp(ng.w0, ng.w1, ng.degree));
+            rs_fresh = false;
+        }
+        __syncthreads();
+
+        // ---- the records (lane = env): wave 1 the restarts' rs4, wave 2 done / winner, wave 3 rewards and totals
+        if (wave >= 1 && lane < ne) {
+            const uint4 ro = rec_out[lane];
+            if (wave == 1) {
+                if (ro.x & RES_RESET) {
+                    rs_in[lane] = rec_rs[lane];
+                    rs_dirty = rs_fresh = true;
+                }
+                if (last && rs_dirty) P.rs4[env] = rs_in[lane];
+            } else if (wave == 2) {
+                if (out.done) out.done[env] = (int8_t)((ro.x & RES_DONE) != 0u);
+                if (out.winner) out.winner[env] = (int8_t)((ro.x >> 4) & 3u);
+            } else {
+                if (out.reward)
+                    reinterpret_cast<float2 *>(out.reward)[env] = make_float2(__uint_as_float(ro.y), __uint_as_float(ro.z));
+            }
+        }
+        if (out.totals && wave == 3) {
+            const uint32_t f = lane < ne ? rec_out[lane].x : 0u;
+            const int wn = ((f & RES_STEPPED) && (f & RES_DONE)) ? (int)((f >> 4) & 3u) : -1;
+            const unsigned long long bs = __ballot((f & RES_STEPPED) != 0u);
+            const unsigned long long b1 = __ballot(wn == 1), b2 = __ballot(wn == 2), b0 = __ballot(wn == 0);
+            if (lane == 0) {                                        // summed in LDS over the launch: see k_obs_roll
+                acc[0] += (unsigned long long)__popcll(bs);
+                acc[1] += (unsigned long long)__popcll(b1);
+                acc[2] += (unsigned long long)__popcll(b2);
+                acc[3] += (unsigned long long)__popcll(b0);
+            }
+        }
+
+        // ---- the stream: both planes of every chunk; a restarted board goes back into the tile as well
+        for (uint32_t i = (uint32_t)tid; i < nchunks; i += BLOCK) {
+            const uint32_t le = chunk_env(i, cpe, cpe_magic);
+            const uint32_t k = i - le * cpe;
+            const uint32_t c = k * 16u;
+            const int nb = min(16, G - (int)c);
+            uint4 t = tile[i];
+            const uint32_t ri = rec_out[le].w;
+            if (ri >> 31) {                                            // restarted env: fresh board + heads (as obs_tile)
+                t = tmpl[k];
+                const uint32_t d1 = (ri & 0x3FFFu) - c, d2 = ((ri >> 14) & 0x3FFFu) - c;
+                const uint32_t v1 = (uint32_t)(0x01 ^ 0x0A) << ((d1 & 3u) * 8u), v2 = (uint32_t)(0x01 ^ 0xF6) << ((d2 & 3u) * 8u);
+                t.x ^= (d1 < 4u ? v1 : 0u) ^ (d2 < 4u ? v2 : 0u);
+                t.y ^= (d1 - 4u < 4u ? v1 : 0u) ^ (d2 - 4u < 4u ? v2 : 0u);
+                t.z ^= (d1 - 8u < 4u ? v1 : 0u) ^ (d2 - 8u < 4u ? v2 : 0u);
+                t.w ^= (d1 - 12u < 4u ? v1 : 0u) ^ (d2 - 12u < 4u ? v2 : 0u);
+                tile[i] = t;
+            }
+            const uint32_t w1[4] = {t.x, t.y, t.z, t.w};
+            const uint32_t w2[4] = {swap_codes4(t.x), swap_codes4(t.y), swap_codes4(t.z), swap_codes4(t.w)};
+            int8_t *o1 = otile + (size_t)le * 2u * G + c;
+            store_chunk<true>(o1, nb, w1);
+            store_chunk<true>(o1 + G, nb, w2);
+        }
+        if (wave == 0 && lane < ne) {
+            const uint4 st = rec_st[lane];                             // (this wave's own write of the move phase)
+            if (last) {
+                if (st_dirty) P.st4[env] = st;
+            } else {
+                uint32_t x[4];
+                philox4x32_10((uint32_t)env, st.w, RNG_STEP, 0u, P.seed, P.stream, x);
+                x0 = x[0];
+                x1 = x[1];
+            }
+        }
+        __syncthreads();        // the restarted boards and rs_in are in LDS before the next move reads them
+    }
+}
+
 // The random-action rollout as ONE launch for k_steps steps (tron_rollout_random): envs never interact,
-// so a workgroup can step its own tiles k_steps times without waiting for anybody else — there is no
-// drain of the whole chip between steps, the load phase of one workgroup overlaps the store phase of
-// its neighbours across step boundaries.  Workgroup w owns tiles w, w + gridDim.x, ...; every step
-// still reads its tile's state from memory and rewrites both observation planes (the same work and
-// the same results, bit for bit, as k_steps launches of k_obs).  Every workgroup runs a fixed trip
-// count, so the grid always drains.
+// so a workgroup can step its own tile k_steps times without waiting for anybody else — there is no
+// drain of the whole chip between steps.  The same results, bit for bit, as k_steps launches of k_obs.
+// One tile per workgroup (gridDim.x == ntiles): memory is read in the first step only (roll_resident).
+// TRON_ROLLOUT_RESIDENT asks for what this kernel does by itself; the flag is accepted for its callers' sake.
+// A kernel of its own beside k_obs_roll_walk: 63 VGPRs here against obs_tile's 108.
 __global__ __launch_bounds__(BLOCK) void k_obs_roll(Params P, int E, uint32_t cpe, uint32_t cpe_magic, uint32_t flags,
                                                    StepOut out, int k_steps, int ntiles)
 {
@@ -1031,28 +1218,41 @@ __global__ __launch_bounds__(BLOCK) void k_obs_roll(Params P, int E, uint32_t cp
     // the {steps, wins, wins, draws} counters are summed in LDS over the whole launch and flushed once:
     // 4 global atomics per tile per step on the same four words serialise in L2 (98 us per step measured)
     __shared__ unsigned long long acc[4];
+    if (out.totals) {
+        if (threadIdx.x < 4) acc[threadIdx.x] = 0ull;
+        __syncthreads();
+    }
+    // The step's parameters are re-read from the kernel-argument segment at every step (scalar loads through a pointer the
+    // compiler cannot see through) instead of kept live across the loop: 26 words of Params in SGPRs for the whole launch
+    // spill, and every spilled word is a v_readlane per use.
+    kernarg_t *kp = (kernarg_t *)__builtin_amdgcn_kernarg_segment_ptr();       // (Params is the first argument)
+    roll_resident(kp, E, cpe, cpe_magic, flags & ~TRON_ROLLOUT_RESIDENT, out, acc, k_steps, smem);
+    if (out.totals && threadIdx.x < 4 && acc[threadIdx.x]) atomicAdd(&out.totals[threadIdx.x], acc[threadIdx.x]);
+}
+
+// Fewer workgroups than tiles (the TRON_ROLL_GRID override): workgroup w owns tiles w, w + gridDim.x, ... and
+// every step reads its tile's state from memory and rewrites both planes (obs_tile, as k_obs).  Every
+// workgroup runs a fixed trip count, so the grid always drains.
+__global__ __launch_bounds__(BLOCK) void k_obs_roll_walk(Params P, int E, uint32_t cpe, uint32_t cpe_magic, uint32_t flags,
+                                                        StepOut out, int k_steps, int ntiles)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ unsigned long long acc[4];           // see k_obs_roll
     StepOut lo = out;
     if (out.totals) {
         if (threadIdx.x < 4) acc[threadIdx.x] = 0ull;
         lo.totals = acc;
         __syncthreads();
     }
-    // TRON_ROLLOUT_RESIDENT (one tile per workgroup): the board never leaves LDS between the steps of a launch — it is
-    // read from memory once, every step still writes both observation planes (which also are the state in memory)
-    const bool resident = (flags & TRON_ROLLOUT_RESIDENT) != 0u && (int)gridDim.x == ntiles;
     flags &= ~TRON_ROLLOUT_RESIDENT;
-    // The step's parameters are re-read from the kernel-argument segment at every step (scalar loads through a pointer the
-    // compiler cannot see through): kept live across the loop, the 26 words of Params pushed the kernel to 63 SGPR spills —
-    // 122 v_readlane per step; re-read, 33 / 24 (and 108 VGPRs instead of 93: four waves per SIMD instead of five), and the
-    // rollout is 3.5 % faster at 64 steps per launch, 0.5 - 1.5 % at 20 (same box, A/B, scripts/env_kernarg_ab.sh).
-    kernarg_t *kp = (kernarg_t *)__builtin_amdgcn_kernarg_segment_ptr();       // (Params is the first argument)
+    kernarg_t *kp = (kernarg_t *)__builtin_amdgcn_kernarg_segment_ptr();       // (Params is the first argument: see k_obs_roll)
     for (int s = 0; s < k_steps; ++s)
         for (int t = (int)blockIdx.x; t < ntiles; t += (int)gridDim.x) {
             kernarg_t *q = kp;
             asm volatile("" : "+s"(q));
             Params Pl;
             load_params(Pl, q);
-            obs_tile<true>(Pl, E, cpe, cpe_magic, nullptr, flags, lo, t, smem, resident && s > 0, resident);
+            obs_tile<true>(Pl, E, cpe, cpe_magic, nullptr, flags, lo, t, smem);
             __syncthreads();        // the tile's LDS is reused; this step's state words are visible to the next
         }
     if (out.totals && threadIdx.x < 4 && acc[threadIdx.x]) atomicAdd(&out.totals[threadIdx.x], acc[threadIdx.x]);
@@ -1064,6 +1264,7 @@ template <class F> struct first_kernel_arg;
 template <class R, class A0, class... A> struct first_kernel_arg<R (*)(A0, A...)> { typedef A0 type; };
 static_assert(std::is_same<first_kernel_arg<decltype(&k_obs_roll)>::type, Params>::value,
               "k_obs_roll re-reads Params from kernarg offset 0: Params must stay its first parameter");
+static_assert(std::is_same<first_kernel_arg<decltype(&k_obs_roll_walk)>::type, Params>::value, "k_obs_roll_walk re-reads Params from kernarg offset 0");
 static_assert(std::is_trivially_copyable<Params>::value && alignof(Params) <= 8 && sizeof(Params) % 4 == 0,
               "Params is block-copied from the kernel-argument segment with scalar loads");
 
@@ -1907,17 +2108,13 @@ int tron_get_state(tron_handle h, int8_t *pos, int8_t *alive, int8_t *dir, int8_
 
 namespace {
 
-// k_steps steps of the observation-is-state kernel as persistent launches (k_obs_roll) of at most
-// TRON_ROLLOUT_CHUNK steps.  One tile per workgroup: with more workgroups than the chip holds at once the
-// late ones start as the early ones finish their steps — measured best at 65 536 x 24x24 (22.1 us per
-// step; 23.5-24.0 us with 1024-1536 workgroups walking several tiles each; 27.2 us with one launch per
-// step).  TRON_ROLL_E / TRON_ROLL_GRID / TRON_ROLL_CHUNK override tile size, grid and steps per launch.
-// Tile size of the persistent rollout.  One tile per workgroup, and the chip holds `slots` workgroups at once
-// (occupancy x CUs: 5 x 256 at 24x24), so the launch runs in ceil(ntiles / slots) rounds and the last one should be
-// full: at 65 536 envs 32-env tiles are 2 048 workgroups = 1.6 rounds (the tail runs 3 per CU, latency-bound), 26-env
-// tiles are 2 521 = 1.97 rounds — 21.4 instead of 21.9 us per step (gpurun sweep, round 2).  Picks the E in
-// [3/4 E0, E0] with the fullest last round (E0 = the per-step kernels' tile); small batches that fit in one round
-// keep E0.  (With this file's current k_obs_roll — occupancy 4 — 32-env tiles are exactly two rounds and win the sweep.)
+// k_steps steps of the observation-is-state kernel as persistent launches of at most TRON_ROLLOUT_CHUNK steps, one tile per
+// workgroup: with more workgroups than the chip holds at once the late ones start as the early ones finish their steps.
+// TRON_ROLL_E / TRON_ROLL_GRID / TRON_ROLL_CHUNK override tile size, grid and steps per launch.
+// Tile size for the kernels that run obs_tile every step (the sliding modes; k_obs_roll_walk has the same code and occupancy
+// and is what is asked here).  The chip holds `slots` workgroups at once (occupancy x CUs), so the launch runs in
+// ceil(ntiles / slots) rounds and the last one should be full.  Picks the E in [3/4 E0, E0] with the fullest last round
+// (E0 = the per-step kernels' tile); small batches that fit in one round keep E0.
 int roll_tile_envs(const tron_env *h)
 {
     const int E0 = h->E;
@@ -1928,7 +2125,7 @@ int roll_tile_envs(const tron_env *h)
     for (int E = E0; E >= (3 * E0 + 3) / 4 && E >= 1; --E) {
         const size_t smem = ((size_t)E + 1u) * h->cpe * 16u + 4u * (size_t)E * 16u;
         int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_obs_roll, BLOCK, smem) != hipSuccess || per_cu < 1) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_obs_roll_walk, BLOCK, smem) != hipSuccess || per_cu < 1) {
             (void)hipGetLastError();
             continue;
         }
@@ -1951,19 +2148,20 @@ int rollout_persistent(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out
         if (const char *v = getenv("TRON_ROLL_CHUNK")) chunk = atoi(v) > 0 ? atoi(v) : TRON_ROLLOUT_CHUNK;
         probed = true;
     }
-    static uint64_t prepared = 0;
+    static uint64_t prepared = 0, prepared_w = 0;
     allow_big_lds(reinterpret_cast<const void *>(k_obs_roll), h->device, prepared);
+    allow_big_lds(reinterpret_cast<const void *>(k_obs_roll_walk), h->device, prepared_w);
     if (!h->roll_E) h->roll_E = roll_tile_envs(h);
-    // the resident variant is store-bound and measured best on the per-step tile (3.51 vs 3.21 G env-steps/s at 26)
-    // ... and so is a call that fits ONE launch (k_steps <= chunk): measured at 65 536 x 24x24, a single 20- / 64-step launch
-    // runs 2.71-2.74 / 2.92 G env-steps/s on 32-env tiles against 2.64-2.65 / 2.84 on 26-env ones, while five 64-step
-    // launches back to back run 3.00 against 3.05 — the full last round pays off when the next launch follows at once
-    const int E = env_e > 0 ? env_e : ((flags & TRON_ROLLOUT_RESIDENT) || k_steps <= chunk) ? h->E : h->roll_E;
+    const bool sliding = h->P.mode != TRON_MODE_NONE;
+    // the sliding modes (obs_tile every step): the per-step tile for a call that fits ONE launch and for the resident variant,
+    // else the tile with the fullest last round — measured at 65 536 x 24x24.  Mode None (roll_resident, 63 VGPRs, six
+    // 32-env workgroups per CU by LDS): the per-step tile; swept at 65 536 x 24x24, 64 / 20 steps per launch: 32 envs 14.5 /
+    // 16.2 us per step, 26: 14.5 / 16.1, 22: 15.1 / 19.0, 16: 16.5 / 18.4, 11: 20.4 / 22.3, 8: 25.0 / 27.0
+    const int E = env_e > 0 ? env_e : !sliding ? h->E : ((flags & TRON_ROLLOUT_RESIDENT) || k_steps <= chunk) ? h->E : h->roll_E;
     const size_t smem = ((size_t)E + 1u) * h->cpe * 16u + 4u * (size_t)E * 16u;
     if (smem > 160u * 1024u) return TRON_ERR_BAD_ARG;
     const int ntiles = (h->P.N + E - 1) / E;
     const int grid = (env_grid > 0 && env_grid < ntiles) ? env_grid : ntiles;
-    const bool sliding = h->P.mode != TRON_MODE_NONE;
     if (sliding) {
         static uint64_t prepared_s = 0;
         allow_big_lds(reinterpret_cast<const void *>(k_obs_roll_slide), h->device, prepared_s);
@@ -1972,8 +2170,11 @@ int rollout_persistent(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out
         if (sliding)
             hipLaunchKernelGGL(k_obs_roll_slide, dim3(grid), dim3(BLOCK), smem, st, h->P, E, h->cpe, h->cpe_magic, flags, out,
                                left < chunk ? left : chunk, ntiles);
-        else
+        else if (grid == ntiles)
             hipLaunchKernelGGL(k_obs_roll, dim3(grid), dim3(BLOCK), smem, st, h->P, E, h->cpe, h->cpe_magic, flags, out,
+                               left < chunk ? left : chunk, ntiles);
+        else
+            hipLaunchKernelGGL(k_obs_roll_walk, dim3(grid), dim3(BLOCK), smem, st, h->P, E, h->cpe, h->cpe_magic, flags, out,
                                left < chunk ? left : chunk, ntiles);
         if (launch_status() != TRON_OK) return TRON_ERR_LAUNCH;
     }
