@@ -29,7 +29,8 @@
 //                           attached obs buffer is the env state; read G, write 2G per env-step
 //   k_obs_roll, k_tile_roll tron_rollout_random: the same per-tile step, but each workgroup steps
 //                           its own tile up to TRON_ROLLOUT_CHUNK times in ONE launch (k_obs_roll: memory
-//                           is read in the first step only, roll_resident; k_obs_roll_walk / _slide: obs_tile)
+//                           is read in the first step only and a step stores only the chunks it changes,
+//                           roll_resident; k_obs_roll_walk / _slide: obs_tile)
 //   k_inc                   TRON_STEP_INCREMENTAL: writes only the touched cells + restarted boards
 //   k_reset, k_obs_reset, k_obs_to_grid, k_obs_planes, k_get_state, k_encode_codes, k_pop_up, ...
 //                           resets, read-back and stateless encodes
@@ -1034,9 +1035,14 @@ __device__ __forceinline__ void load_params_scalar(Params &p, kernarg_t *kp)
 // the board (tile), st4 (rec_st), rs4 (rs_in), the speculative next start (rec_rs) and the fresh-board template (tmpl).
 // Memory is read in the prologue only.  That is G bytes per env-step less to fetch, and it is what lets the stores run
 // on: vmcnt counts a wave's loads and stores in issue order, so ONE global load per step (obs_tile issues three: st4 /
-// rs4, the template's P.fresh, the tile) makes the wave wait for all its plane stores of the step before.  Every step
-// still writes both planes of every env in full; st4 / rs4 are written by the launch's last step (same bytes as one
-// store per step leaves behind).  The random-number work that obs_tile hides under the tile load runs here in waves
+// rs4, the template's P.fresh, the tile) makes the wave wait for all its plane stores of the step before.
+// Sparse stores: the planes in memory already hold the tile as the prologue read it (every writer of the API leaves the
+// player-2 plane the swap_codes4 image of the player-1 plane, and the caller never writes the buffer), so a step stores
+// only the 16-byte chunks that can differ, both planes of each: the chunks of the four cells the move wrote (rec_mv,
+// marked whether or not the byte changed) and, for a restarted env, the chunks where the fresh board differs from the
+// tile.  A chunk neither marked nor different from the tile holds in memory what it holds in LDS.  About 8 chunks of
+// the 2 x cpe per env-step at 24x24 under uniform actions.  st4 / rs4 are written by the launch's last step (same
+// bytes as one store per step leaves behind).  The random-number work that obs_tile hides under the tile load runs here in waves
 // that would idle: wave 1 draws the next start (make_game) while wave 0 moves — and only for envs whose rs4 changed,
 // i.e. after a restart — and wave 0 draws the Philox words of step s + 1 (its tick is known once step s has moved)
 // behind its share of the stream of step s, while the stores are on their way.
@@ -1049,6 +1055,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, uint32_t cpe
     uint4 *rec_out = rec_st + E;                                    // [E] this step's result record
     uint4 *rec_rs = rec_out + E;                                    // [E] rs4 after the env's next restart
     uint4 *rs_in = rec_rs + E;                                      // [E] rs4, carried
+    uint2 *rec_mv = reinterpret_cast<uint2 *>(rs_in + E);           // [E] chunks of the cells this step's move wrote
 
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
@@ -1088,7 +1095,17 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, uint32_t cpe
 #pragma unroll
             for (int k = 0; k < DK; ++k) {
                 const uint32_t i = base + (uint32_t)tid + (uint32_t)k * BLOCK;
-                if (i < nchunks) tile[i] = v[k];
+                if (i < nchunks) {
+                    // the words past G of the last chunk (the over-read player-2 plane; G % 4 == 0) are zeroed, as in tmpl,
+                    // so that a restart compares the board only
+                    const int nb = G - (int)((i - chunk_env(i, cpe, cpe_magic) * cpe) * 16u);
+                    if (nb < 16) {
+                        if (nb <= 4) v[k].y = 0u;
+                        if (nb <= 8) v[k].z = 0u;
+                        v[k].w = 0u;
+                    }
+                    tile[i] = v[k];
+                }
             }
         }
         if (lane < ne) {
@@ -1126,6 +1143,18 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, uint32_t cpe
                     rec_st[lane] = rst;
                     st_dirty = true;
                 }
+                // the chunks of the cells the move wrote (the old heads and the new ones: lane_move_codes), 16 bits each;
+                // 0xFFFF is no chunk (a cell index has 15 bits)
+                uint2 mv = make_uint2(~0u, ~0u);
+                if (ro.x & RES_STEPPED) {
+                    const int S = P.S;
+                    const int h0 = cell_index(S, (int)(int8_t)st.x, (int)(int8_t)(st.x >> 8));
+                    const int h1 = cell_index(S, (int)(int8_t)(st.x >> 16), (int)(int8_t)(st.x >> 24));
+                    const int f0 = h0 + (a[0] == 0 ? -S : a[0] == 2 ? S : a[0] == 1 ? 1 : -1);   // UP / DOWN / RIGHT / LEFT
+                    const int f1 = h1 + (a[1] == 0 ? -S : a[1] == 2 ? S : a[1] == 1 ? 1 : -1);
+                    mv = make_uint2((uint32_t)(h0 >> 4) | ((uint32_t)(h1 >> 4) << 16), (uint32_t)(f0 >> 4) | ((uint32_t)(f1 >> 4) << 16));
+                }
+                rec_mv[lane] = mv;
             }
             if (lane < E) rec_out[lane] = ro;
         } else if (wave == 1 && autoreset && lane < ne && rs_fresh) {
@@ -1166,23 +1195,34 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, uint32_t cpe
             }
         }
 
-        // ---- the stream: both planes of every chunk; a restarted board goes back into the tile as well
+        // ---- the stream: both planes of the chunks that can differ from memory (see above); a restarted board goes back
+        // into the tile as well
         for (uint32_t i = (uint32_t)tid; i < nchunks; i += BLOCK) {
             const uint32_t le = chunk_env(i, cpe, cpe_magic);
             const uint32_t k = i - le * cpe;
+            const uint32_t ri = rec_out[le].w;
+            const uint2 mv = rec_mv[le];
+            const uint32_t mx = mv.x ^ (k * 0x10001u), my = mv.y ^ (k * 0x10001u);
+            bool put = !(mx & 0xFFFFu) || !(mx >> 16) || !(my & 0xFFFFu) || !(my >> 16);
+            if (!put && !(ri >> 31)) continue;
             const uint32_t c = k * 16u;
             const int nb = min(16, G - (int)c);
             uint4 t = tile[i];
-            const uint32_t ri = rec_out[le].w;
             if (ri >> 31) {                                            // restarted env: fresh board + heads (as obs_tile)
-                t = tmpl[k];
+                uint4 n = tmpl[k];
                 const uint32_t d1 = (ri & 0x3FFFu) - c, d2 = ((ri >> 14) & 0x3FFFu) - c;
                 const uint32_t v1 = (uint32_t)(0x01 ^ 0x0A) << ((d1 & 3u) * 8u), v2 = (uint32_t)(0x01 ^ 0xF6) << ((d2 & 3u) * 8u);
-                t.x ^= (d1 < 4u ? v1 : 0u) ^ (d2 < 4u ? v2 : 0u);
-                t.y ^= (d1 - 4u < 4u ? v1 : 0u) ^ (d2 - 4u < 4u ? v2 : 0u);
-                t.z ^= (d1 - 8u < 4u ? v1 : 0u) ^ (d2 - 8u < 4u ? v2 : 0u);
-                t.w ^= (d1 - 12u < 4u ? v1 : 0u) ^ (d2 - 12u < 4u ? v2 : 0u);
-                tile[i] = t;
+                n.x ^= (d1 < 4u ? v1 : 0u) ^ (d2 < 4u ? v2 : 0u);
+                n.y ^= (d1 - 4u < 4u ? v1 : 0u) ^ (d2 - 4u < 4u ? v2 : 0u);
+                n.z ^= (d1 - 8u < 4u ? v1 : 0u) ^ (d2 - 8u < 4u ? v2 : 0u);
+                n.w ^= (d1 - 12u < 4u ? v1 : 0u) ^ (d2 - 12u < 4u ? v2 : 0u);
+                // the tile holds memory's bytes except in the marked chunks, which are stored anyway
+                if (n.x == t.x && n.y == t.y && n.z == t.z && n.w == t.w) {
+                    if (!put) continue;
+                } else {
+                    tile[i] = n;
+                }
+                t = n;
             }
             const uint32_t w1[4] = {t.x, t.y, t.z, t.w};
             const uint32_t w2[4] = {swap_codes4(t.x), swap_codes4(t.y), swap_codes4(t.z), swap_codes4(t.w)};
@@ -1210,7 +1250,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, uint32_t cpe
 // drain of the whole chip between steps.  The same results, bit for bit, as k_steps launches of k_obs.
 // One tile per workgroup (gridDim.x == ntiles): memory is read in the first step only (roll_resident).
 // TRON_ROLLOUT_RESIDENT asks for what this kernel does by itself; the flag is accepted for its callers' sake.
-// A kernel of its own beside k_obs_roll_walk: 63 VGPRs here against obs_tile's 108.
+// A kernel of its own beside k_obs_roll_walk: 64 VGPRs here against obs_tile's 108.
 __global__ __launch_bounds__(BLOCK) void k_obs_roll(Params P, int E, uint32_t cpe, uint32_t cpe_magic, uint32_t flags,
                                                    StepOut out, int k_steps, int ntiles)
 {
@@ -2154,14 +2194,16 @@ int rollout_persistent(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out
     if (!h->roll_E) h->roll_E = roll_tile_envs(h);
     const bool sliding = h->P.mode != TRON_MODE_NONE;
     // the sliding modes (obs_tile every step): the per-step tile for a call that fits ONE launch and for the resident variant,
-    // else the tile with the fullest last round — measured at 65 536 x 24x24.  Mode None (roll_resident, 63 VGPRs, six
-    // 32-env workgroups per CU by LDS): the per-step tile; swept at 65 536 x 24x24, 64 / 20 steps per launch: 32 envs 14.5 /
-    // 16.2 us per step, 26: 14.5 / 16.1, 22: 15.1 / 19.0, 16: 16.5 / 18.4, 11: 20.4 / 22.3, 8: 25.0 / 27.0
+    // else the tile with the fullest last round — measured at 65 536 x 24x24.  Mode None (roll_resident, 64 VGPRs, six
+    // 32-env workgroups per CU by LDS): the per-step tile; swept with sparse stores at 65 536 x 24x24, 64 / 20 steps per
+    // launch: 32 envs 13.0 / 14.6 us per step, 26: 13.4 / 15.0, 24: 14.0 / 15.6, 20: 15.0 / 16.7, 16: 15.8 / 17.5,
+    // 12: 19.0 / 20.5, 8: 24.0 / 25.9, 40: 14.1 / 15.7, 48: 15.3 / 17.0, 64: 16.0 / 17.7
     const int E = env_e > 0 ? env_e : !sliding ? h->E : ((flags & TRON_ROLLOUT_RESIDENT) || k_steps <= chunk) ? h->E : h->roll_E;
-    const size_t smem = ((size_t)E + 1u) * h->cpe * 16u + 4u * (size_t)E * 16u;
-    if (smem > 160u * 1024u) return TRON_ERR_BAD_ARG;
     const int ntiles = (h->P.N + E - 1) / E;
     const int grid = (env_grid > 0 && env_grid < ntiles) ? env_grid : ntiles;
+    // + k_obs_roll's rec_mv (8 bytes per env)
+    const size_t smem = ((size_t)E + 1u) * h->cpe * 16u + 4u * (size_t)E * 16u + (!sliding && grid == ntiles ? 8u * (size_t)E : 0u);
+    if (smem > 160u * 1024u) return TRON_ERR_BAD_ARG;
     if (sliding) {
         static uint64_t prepared_s = 0;
         allow_big_lds(reinterpret_cast<const void *>(k_obs_roll_slide), h->device, prepared_s);

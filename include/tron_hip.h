@@ -66,8 +66,10 @@ enum {
 #define TRON_ROLLOUT_RESIDENT 32u  /* tron_rollout_random flag, attached observation buffer only: within a persistent launch
                                     * the boards stay in LDS from step to step instead of being read back from the
                                     * observation buffer each step.  Mode None does this by itself (boards and state words
-                                    * are read in the first step of a launch only: 2G bytes per env-step written, G read
-                                    * once per launch); there the flag changes nothing.  The sliding modes honour it.
+                                    * are read in the first step of a launch only, G bytes per env once per launch, and a
+                                    * step writes only the 16-byte chunks of both planes that it can change: the chunks of
+                                    * the cells a move touches and those where a restarted board differs, about 8 chunks
+                                    * per env-step at 24x24); there the flag changes nothing.  The sliding modes honour it.
                                     * Same results either way; ignored where it does not apply.                        */
 #define TRON_ROLLOUT_TWO_STREAMS 16u /* tron_rollout_random flag: one launch per step and per HALF of the envs, the two
                                       * halves on two streams (the handle owns the second one), so one half's launch
@@ -114,8 +116,10 @@ int tron_reset(tron_handle h, const int8_t *env_mask, const int8_t *start_pos,
                const int16_t *weight, const int16_t *degree, void *stream);
 
 /* Observation-is-state storage (even W, TRON_OBS_CODES_I8; every mode).  The player-1 code plane carries the game — a cell is
- * EMPTY or it is not — so the caller's observation buffer int8[N][2][G] can BE the env state: each step reads the player-1 plane
- * and rewrites both planes — the algorithmic 3G bytes per env-step, with no separate board write-back.  In mode None the plane
+ * EMPTY or it is not — so the caller's observation buffer int8[N][2][G] can BE the env state: a per-step launch reads the player-1
+ * plane and rewrites both planes — the algorithmic 3G bytes per env-step, with no separate board write-back; the mode None
+ * persistent rollout (tron_rollout_random) reads G once per launch and writes only the chunks a step changes, which relies on
+ * the buffer holding what the env last wrote.  In mode None the plane
  * is a lossless image of the board; in ice / temper a slide tile shows as its player's body (map.py:67-81), so the env keeps the
  * slide tiles in a per-env log (2 bytes appended per slide) that tron_get_grid replays: the board image stays exact.
  * After attaching, the buffer belongs to the env until tron_destroy: read it, never write it;
