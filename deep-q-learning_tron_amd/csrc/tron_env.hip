@@ -27,10 +27,12 @@
 //   k_tile / tile_step      board-owning layout (grid[N][G] + caller's obs): every mode, format, side
 //   k_obs / obs_tile        observation-is-state (mode None, int8 codes, even side): the caller's
 //                           attached obs buffer is the env state; read G, write 2G per env-step
-//   k_obs_roll, k_tile_roll tron_rollout_random: the same per-tile step, but each workgroup steps
-//                           its own tile up to TRON_ROLLOUT_CHUNK times in ONE launch (k_obs_roll: memory
-//                           is read in the first step only and a step stores only the chunks it changes,
-//                           roll_resident; k_obs_roll_walk / _slide: obs_tile)
+//   k_obs_roll, k_tile_roll tron_rollout_random: up to TRON_ROLLOUT_CHUNK steps in ONE launch.  k_obs_roll (roll_resident):
+//                           one lane per env and a wave on its own for the whole launch — no barrier in the step loop,
+//                           boards in LDS at 4 bits per cell (the whole batch resident in one round), memory read in the
+//                           prologue only, a step stores the chunks of a per-env mask.  k_tile_roll, k_obs_roll_walk
+//                           (boards of more than 64 chunks, TRON_ROLL_GRID) and k_obs_roll_slide: the per-tile step
+//                           (tile_step / obs_tile), each workgroup stepping its own tiles
 //   k_inc                   TRON_STEP_INCREMENTAL: writes only the touched cells + restarted boards
 //   k_reset, k_obs_reset, k_obs_to_grid, k_obs_planes, k_get_state, k_encode_codes, k_pop_up, ...
 //                           resets, read-back and stateless encodes
@@ -40,6 +42,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <math.h>
 #include <string.h>
@@ -1030,244 +1033,329 @@ __device__ __forceinline__ void load_params_scalar(Params &p, kernarg_t *kp)
     __builtin_memcpy(&p, q, sizeof(Params));
 }
 
-// The steps of a persistent launch that owns its tile (k_obs_roll, one tile per workgroup): nobody else touches the
-// tile's planes or state words during the launch, so everything a step reads is carried in LDS from the step before —
-// the board (tile), st4 (rec_st), rs4 (rs_in), the speculative next start (rec_rs) and the fresh-board template (tmpl).
-// Memory is read in the prologue only.  That is G bytes per env-step less to fetch, and it is what lets the stores run
-// on: vmcnt counts a wave's loads and stores in issue order, so ONE global load per step (obs_tile issues three: st4 /
-// rs4, the template's P.fresh, the tile) makes the wave wait for all its plane stores of the step before.
-// Sparse stores: the planes in memory already hold the tile as the prologue read it (every writer of the API leaves the
-// player-2 plane the swap_codes4 image of the player-1 plane, and the caller never writes the buffer), so a step stores
-// only the 16-byte chunks that can differ, both planes of each: the chunks of the four cells the move wrote (rec_mv,
-// marked whether or not the byte changed) and, for a restarted env, the chunks where the fresh board differs from the
-// tile.  A chunk neither marked nor different from the tile holds in memory what it holds in LDS.  About 8 chunks of
-// the 2 x cpe per env-step at 24x24 under uniform actions.  st4 / rs4 are written by the launch's last step (same
-// bytes as one store per step leaves behind).  The random-number work that obs_tile hides under the tile load runs here in waves
-// that would idle: wave 1 draws the next start (make_game) while wave 0 moves — and only for envs whose rs4 changed,
-// i.e. after a restart — and wave 0 draws the Philox words of step s + 1 (its tick is known once step s has moved)
-// behind its share of the stream of step s, while the stores are on their way.
-__device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, uint32_t cpe, uint32_t cpe_magic, uint32_t flags,
-                                              const StepOut &out, unsigned long long *acc, int k_steps, unsigned char *smem)
+// ---- the boards of k_obs_roll in LDS: 4 bits per cell ---------------------------------------------------------------------
+// The six player-1 codes of mode None (1, -1, -2, -3, 10, -10) have distinct low nibbles (1, F, E, D, A, 6), so a cell is kept
+// as its code's low nibble, cell j of a 16-cell chunk in bits 4 (j & 7) of dword j >> 3: a chunk is two dwords, a 24x24
+// board 43 chunks = 344 bytes.  The code comes back as nibble | 0xF0 where the nibble's bit 2 is set (F, E, D, 6: the
+// negative ones); a padding nibble 0 (cells past G in the last chunk) comes back as 0.
+constexpr uint32_t NIB_EMPTY = 0x1u, NIB_WALL = 0xFu, NIB_P1_BODY = 0xEu, NIB_P2_BODY = 0xDu, NIB_P1_HEAD = 0xAu, NIB_P2_HEAD = 0x6u;
+__device__ __forceinline__ uint32_t pack_codes8(uint32_t w0, uint32_t w1)       // 8 code bytes -> 8 nibbles
 {
-    uint4 *tile = reinterpret_cast<uint4 *>(smem);                  // the LDS layout of obs_tile
-    uint4 *tmpl = tile + (size_t)E * cpe;
-    uint4 *rec_st = tmpl + cpe;                                     // [E] st4, carried
-    uint4 *rec_out = rec_st + E;                                    // [E] this step's result record
-    uint4 *rec_rs = rec_out + E;                                    // [E] rs4 after the env's next restart
-    uint4 *rs_in = rec_rs + E;                                      // [E] rs4, carried
-    uint2 *rec_mv = reinterpret_cast<uint2 *>(rs_in + E);           // [E] chunks of the cells this step's move wrote
+    const uint32_t a = w0 & 0x0F0F0F0Fu, b = w1 & 0x0F0F0F0Fu;
+    const uint32_t ta = a | (a >> 4), tb = b | (b >> 4);                        // bytes 0 and 2 hold two nibbles each
+    return (ta & 0xFFu) | ((ta >> 8) & 0xFF00u) | ((tb & 0xFFu) << 16) | ((tb << 8) & 0xFF000000u);
+}
+__device__ __forceinline__ void expand_codes8(uint32_t p, uint32_t &w0, uint32_t &w1)   // 8 nibbles -> 8 code bytes
+{
+    const uint32_t lo = p & 0x0F0F0F0Fu, hi = (p >> 4) & 0x0F0F0F0Fu;           // even / odd cells
+    const uint32_t a = __builtin_amdgcn_perm(hi, lo, 0x05010400u), b = __builtin_amdgcn_perm(hi, lo, 0x07030602u);
+    w0 = a | (((a >> 2) & 0x01010101u) * 0xF0u);
+    w1 = b | (((b >> 2) & 0x01010101u) * 0xF0u);
+}
+
+// The steps of a persistent launch (k_obs_roll): ONE LANE = ONE ENV for the whole launch, and a wave owns its envs from the
+// prologue to the epilogue.  Nobody else touches an env's planes or state words during the launch, so everything a step
+// reads is carried from the step before: st4, rs4 and the Philox words of the coming step's actions in the lane's
+// registers, the board in the lane's own region of LDS (4 bits per cell, above).  The wave does the move, the plane
+// stores, the records, the totals' ballots, the Philox block of step s + 1 and make_game for the lanes that restarted,
+// all by itself: there is no workgroup barrier in the step loop and no LDS record between waves; the waves of a workgroup
+// share the fresh-board template only, built in the prologue.  Memory is read in the prologue only: a global load in the
+// loop would make the wave wait (vmcnt counts loads and stores in issue order) for every plane store it has issued.
+// The parameters are re-read per step with scalar loads (load_params_scalar).
+// LDS: an env's board takes 2 cpe + 1 dwords — odd, so that the same dword of the boards of the 64 lanes falls on 64
+// different banks (any power-of-two bank count) — and 65 536 boards of 24x24 are 22.8 MB: the whole batch is resident at
+// once, the launch is one round (rollout_persistent).
+// Sparse stores, computed: the planes in memory already hold what the prologue read (every writer of the API leaves the
+// player-2 plane the swap_codes4 image of the player-1 plane, and the caller never writes the buffer), and each env carries
+// a 64-bit mask of the chunks of its player-1 plane that differ from the fresh-board template (cpe <= 64: boards up to
+// 30x30; the host sends wider ones to k_obs_roll_walk).  The prologue builds the mask by comparing what it reads with the
+// template, whoever wrote it; a move stores and marks the chunks of its four cells; a restart stores the chunks in
+// mask | chunks of the two new heads from the template with the heads patched in, and the mask becomes the head chunks.
+// Nothing is compared in the loop, and a chunk outside the mask holds the template in memory and in LDS alike.
+// An env that restarts in the step it finishes in skips the move's four cell writes: its board is rebuilt from the mask
+// as it was before the move.  st4 / rs4 are written by the epilogue (same bytes as one store per step leaves behind).
+// Not reachable through the API today: tron_rollout_random always sets TRON_STEP_AUTORESET and passes out.totals only, so
+// the !autoreset branches and the out.done / out.winner / out.reward stores below (kept as the per-step kernels have them,
+// uniform branches) are run by no caller and no test.
+__device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uint32_t cpe, uint32_t flags, const StepOut &out,
+                                              int k_steps, unsigned char *smem)
+{
+    const uint32_t sd = 2u * cpe + 1u;                              // dwords per board
+    uint32_t *boards = reinterpret_cast<uint32_t *>(smem);          // [E][sd]
+    uint32_t *tmpl = boards + (size_t)E * sd;                       // [2 cpe] fresh board, packed
 
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
     const bool autoreset = (flags & TRON_STEP_AUTORESET) != 0u, nonrev = (flags & TRON_STEP_NONREVERSING) != 0u;
-    const int e0 = (int)blockIdx.x * E;
+    const int we0 = wave * epw;                                     // this wave's first env within the workgroup
+    const int e0 = (int)blockIdx.x * E + we0;
     const int env = e0 + lane;
-    int ne;
-    uint32_t nchunks;
-    int8_t *otile;
-    uint32_t x0 = 0u, x1 = 0u;                                      // wave 0: the Philox words of the coming step's actions
-    bool st_dirty = false, rs_dirty = false, rs_fresh = true;       // wave 0 / wave 1 / wave 1: rec_rs is to be drawn from rs_in
+    uint32_t *wboards = boards + (size_t)we0 * sd;
+    uint32_t *board = wboards + (size_t)lane * sd;                  // this lane's env
+    unsigned char *cellb = reinterpret_cast<unsigned char *>(board);   // two cells per byte
+    bool mine;
+    int8_t *oenv;                                                   // this env's [2][G] planes
+    uint4 st = make_uint4(0u, 0u, 0u, 0u), rs = make_uint4(0u, 0u, 0u, 0u);
+    uint32_t x0 = 0u, x1 = 0u;                                      // the Philox words of the coming step's actions
+    unsigned long long mask = 0ull;                                 // chunks of the player-1 plane that differ from the template
+    bool st_dirty = false, rs_dirty = false;
+    uint32_t n_steps = 0u, n_w1 = 0u, n_w2 = 0u, n_draw = 0u;        // this wave's totals (uniform)
 
     // ---- prologue: the only loads from memory of the launch
     {
         Params P;
         load_params_scalar(P, kp);
         const int G = P.G;
-        ne = min(E, P.N - e0);
-        nchunks = (uint32_t)ne * cpe;
-        otile = P.obs_state + (size_t)e0 * 2u * G;
-        uint4 st = make_uint4(0u, 0u, 0u, 0u);
-        if (lane < ne) {
-            if (wave == 0) st = P.st4[env];
-            else if (wave == 1 && autoreset) st = P.rs4[env];
+        const int ne = min(min(epw, E - we0), P.N - e0);            // this wave's envs (<= 0: none)
+        mine = lane < ne;
+        oenv = P.obs_state + (size_t)(mine ? env : 0) * 2u * G;
+        if (mine) {
+            st = P.st4[env];
+            if (autoreset) rs = P.rs4[env];
         }
-        if (autoreset)
-            for (uint32_t d = (uint32_t)tid; d < cpe * 16u; d += BLOCK)
-                reinterpret_cast<int8_t *>(tmpl)[d] = (d < (uint32_t)G) ? (P.fresh[d] == TRON_EMPTY ? (int8_t)1 : (int8_t)-1) : (int8_t)0;
-        for (uint32_t base = 0; base < nchunks; base += DK * BLOCK) {
-            uint4 v[DK];
+        for (uint32_t d = (uint32_t)tid; d < 2u * cpe; d += blockDim.x) {
+            // eight cells of the fresh board (G % 4 == 0: whole words; a word past G is read as the last one and not used)
+            const uint32_t *fw = reinterpret_cast<const uint32_t *>(P.fresh);
+            const uint32_t last = (uint32_t)G / 4u - 1u;
+            const uint32_t f[2] = {fw[min(2u * d, last)], fw[min(2u * d + 1u, last)]};
+            uint32_t v = 0u;
 #pragma unroll
-            for (int k = 0; k < DK; ++k) {
-                const uint32_t i = base + (uint32_t)tid + (uint32_t)k * BLOCK;
-                const uint32_t le = chunk_env(i, cpe, cpe_magic);
-                if (i < nchunks) v[k] = load_chunk<true>(otile + (size_t)le * 2u * G + (i - le * cpe) * 16u);   // player-1 plane
-            }
+            for (uint32_t j = 0; j < 8u; ++j)
+                if (d * 8u + j < (uint32_t)G)
+                    v |= ((int8_t)(f[j >> 2] >> (8u * (j & 3u))) == TRON_EMPTY ? NIB_EMPTY : NIB_WALL) << (4u * j);
+            tmpl[d] = v;
+        }
+        __syncthreads();
+        // The wave reads its envs' player-1 planes one env at a time, lane = chunk (coalesced), packs them into the env's
+        // board and compares with the template: the ballot is the env's mask.  A plane byte outside the six codes cannot
+        // occur in mode None: the planes are written by k_obs_reset and the attach (code1 of a tile value: six codes, the
+        // slide tiles' among them), by the moves of obs_tile / k_inc / this kernel (the constants -2, -3, 10, -10) and from
+        // the fresh-board template (1 / -1), and the caller never writes the buffer — so the low nibble is the code.
+        const bool ck = (uint32_t)lane < cpe;
+        const int nb = G - lane * 16;                               // valid cells of this lane's chunk (G % 4 == 0)
+        const uint32_t t0 = ck ? tmpl[2 * lane] : 0u, t1 = ck ? tmpl[2 * lane + 1] : 0u;
+        constexpr int PF = 8;                                       // loads in flight (unconditional, so that they are: a lane or an env past the end reads chunk 0 / the last env again)
+        for (int e = 0; e < ne; e += PF) {
+            uint4 v[PF];
 #pragma unroll
-            for (int k = 0; k < DK; ++k) {
-                const uint32_t i = base + (uint32_t)tid + (uint32_t)k * BLOCK;
-                if (i < nchunks) {
-                    // the words past G of the last chunk (the over-read player-2 plane; G % 4 == 0) are zeroed, as in tmpl,
-                    // so that a restart compares the board only
-                    const int nb = G - (int)((i - chunk_env(i, cpe, cpe_magic) * cpe) * 16u);
-                    if (nb < 16) {
-                        if (nb <= 4) v[k].y = 0u;
-                        if (nb <= 8) v[k].z = 0u;
-                        v[k].w = 0u;
-                    }
-                    tile[i] = v[k];
+            for (int j = 0; j < PF; ++j)
+                v[j] = load_chunk<true>(P.obs_state + (size_t)(e0 + min(e + j, ne - 1)) * 2u * G + (ck ? lane * 16 : 0));
+#pragma unroll
+            for (int j = 0; j < PF; ++j) {
+                if (e + j >= ne) break;
+                uint32_t p0 = 0u, p1 = 0u;
+                if (ck) {
+                    if (nb <= 4) v[j].y = 0u;                       // the over-read past G (the player-2 plane) is no board
+                    if (nb <= 8) v[j].z = 0u;
+                    if (nb <= 12) v[j].w = 0u;
+                    p0 = pack_codes8(v[j].x, v[j].y);
+                    p1 = pack_codes8(v[j].z, v[j].w);
+                    uint32_t *b = wboards + (size_t)(e + j) * sd + 2 * lane;
+                    b[0] = p0;
+                    b[1] = p1;
                 }
+                const unsigned long long diff = __ballot(ck && (p0 != t0 || p1 != t1));
+                if (lane == e + j) mask = diff;
             }
         }
-        if (lane < ne) {
-            if (wave == 0) {
-                rec_st[lane] = st;
-                uint32_t x[4];
-                philox4x32_10((uint32_t)env, st.w, RNG_STEP, 0u, P.seed, P.stream, x);
-                x0 = x[0];
-                x1 = x[1];
-            } else if (wave == 1 && autoreset) {
-                rs_in[lane] = st;
-            }
+        if (mine) {
+            uint32_t x[4];
+            philox4x32_10((uint32_t)env, st.w, RNG_STEP, 0u, P.seed, P.stream, x);
+            x0 = x[0];
+            x1 = x[1];
         }
+        __syncthreads();                                            // the boards are in LDS before their lanes read them
     }
-    __syncthreads();
 
     for (int s = 0; s < k_steps; ++s) {
         Params P;                                                   // re-read per step: see k_obs_roll
         load_params_scalar(P, kp);
-        const int G = P.G;
-        const bool last = s + 1 == k_steps;
+        const int S = P.S, W = P.W, G = P.G;
+        STAMP(0);
 
-        // ---- the move: wave 0, one env per lane; beside it wave 1 draws the next starts that are due
-        if (wave == 0) {
-            uint4 ro = make_uint4(0u, 0u, 0u, 0u);
-            if (lane < ne) {
-                const uint4 st = rec_st[lane];
-                EnvRegs R{};
-                R.pos = st.x; R.meta = st.y; R.eplen = st.z; R.tick = st.w;
-                if (autoreset) R.nstart = rs_in[lane].z;
-                const int a[2] = {draw_action(x0, (R.meta >> 8) & 0xFu, nonrev), draw_action(x1, (R.meta >> 12) & 0xFu, nonrev)};
-                uint4 rst;
-                lane_move_codes(P, reinterpret_cast<unsigned char *>(tile + (size_t)lane * cpe), R, a, flags, rst, ro);
-                if (ro.x & RES_STORE_ST) {
-                    rec_st[lane] = rst;
-                    st_dirty = true;
-                }
-                // the chunks of the cells the move wrote (the old heads and the new ones: lane_move_codes), 16 bits each;
-                // 0xFFFF is no chunk (a cell index has 15 bits)
-                uint2 mv = make_uint2(~0u, ~0u);
-                if (ro.x & RES_STEPPED) {
-                    const int S = P.S;
-                    const int h0 = cell_index(S, (int)(int8_t)st.x, (int)(int8_t)(st.x >> 8));
-                    const int h1 = cell_index(S, (int)(int8_t)(st.x >> 16), (int)(int8_t)(st.x >> 24));
-                    const int f0 = h0 + (a[0] == 0 ? -S : a[0] == 2 ? S : a[0] == 1 ? 1 : -1);   // UP / DOWN / RIGHT / LEFT
-                    const int f1 = h1 + (a[1] == 0 ? -S : a[1] == 2 ? S : a[1] == 1 ? 1 : -1);
-                    mv = make_uint2((uint32_t)(h0 >> 4) | ((uint32_t)(h1 >> 4) << 16), (uint32_t)(f0 >> 4) | ((uint32_t)(f1 >> 4) << 16));
-                }
-                rec_mv[lane] = mv;
+        // ---- the move: Game.next_frame + Game.step in code space (lane_move_codes) on the packed board
+        bool stepped = false, restart = false;
+        bool done = (st.y & META_DONE) != 0u;
+        int winner = (int)((st.y >> 4) & 3u);
+        float rw0 = 0.0f, rw1 = 0.0f;
+        unsigned long long sm = 0ull;                               // chunks this step stores
+        uint32_t h1 = 0u, h2 = 0u;                                  // a restart's head cells
+        if (mine && !done) {
+            stepped = true;
+            const int a[2] = {draw_action(x0, (st.y >> 8) & 0xFu, nonrev), draw_action(x1, (st.y >> 12) & 0xFu, nonrev)};
+            int r[2] = {(int)(int8_t)(st.x), (int)(int8_t)(st.x >> 16)};
+            int c[2] = {(int)(int8_t)(st.x >> 8), (int)(int8_t)(st.x >> 24)};
+            int cells[4];                                            // the old heads, the new ones
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                cells[p] = cell_index(S, r[p], c[p]);
+                r[p] += (a[p] == 0) ? -1 : (a[p] == 2) ? 1 : 0;          // UP / DOWN   (player.py:124-132)
+                c[p] += (a[p] == 1) ? 1 : (a[p] == 3) ? -1 : 0;          // RIGHT / LEFT
+                cells[2 + p] = cell_index(S, r[p], c[p]);
             }
-            if (lane < E) rec_out[lane] = ro;
-        } else if (wave == 1 && autoreset && lane < ne && rs_fresh) {
-            const uint4 rs = rs_in[lane];
-            const NewGame ng = make_game(P.seed, P.stream, P.W, P.fair, (uint32_t)env, rs.y + 1u);
-            rec_rs[lane] = make_uint4(rs.w, rs.y + 1u, pack_pos(ng.r1, ng.c1, ng.r2, ng.c2), pack_envp(ng.w0, ng.w1, ng.degree));
-            rs_fresh = false;
-        }
-        __syncthreads();
-
-        // ---- the records (lane = env): wave 1 the restarts' rs4, wave 2 done / winner, wave 3 rewards and totals
-        if (wave >= 1 && lane < ne) {
-            const uint4 ro = rec_out[lane];
-            if (wave == 1) {
-                if (ro.x & RES_RESET) {
-                    rs_in[lane] = rec_rs[lane];
-                    rs_dirty = rs_fresh = true;
-                }
-                if (last && rs_dirty) P.rs4[env] = rs_in[lane];
-            } else if (wave == 2) {
-                if (out.done) out.done[env] = (int8_t)((ro.x & RES_DONE) != 0u);
-                if (out.winner) out.winner[env] = (int8_t)((ro.x >> 4) & 3u);
-            } else {
-                if (out.reward)
-                    reinterpret_cast<float2 *>(out.reward)[env] = make_float2(__uint_as_float(ro.y), __uint_as_float(ro.z));
+            uint32_t b[4];                                           // one LDS round trip: the bytes of the four cells
+#pragma unroll
+            for (int k = 0; k < 4; ++k) b[k] = cellb[cells[k] >> 1];
+            uint32_t tf[2];
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                tf[p] = (b[2 + p] >> ((cells[2 + p] & 1) * 4)) & 15u;
+                // game.py:155-156 — heads turn into bodies BEFORE anyone moves
+                if (cells[2 + p] == cells[0]) tf[p] = NIB_P1_BODY;
+                if (cells[2 + p] == cells[1]) tf[p] = NIB_P2_BODY;
             }
-        }
-        if (out.totals && wave == 3) {
-            const uint32_t f = lane < ne ? rec_out[lane].x : 0u;
-            const int wn = ((f & RES_STEPPED) && (f & RES_DONE)) ? (int)((f >> 4) & 3u) : -1;
-            const unsigned long long bs = __ballot((f & RES_STEPPED) != 0u);
-            const unsigned long long b1 = __ballot(wn == 1), b2 = __ballot(wn == 2), b0 = __ballot(wn == 0);
-            if (lane == 0) {                                        // summed in LDS over the launch: see k_obs_roll
-                acc[0] += (unsigned long long)__popcll(bs);
-                acc[1] += (unsigned long long)__popcll(b1);
-                acc[2] += (unsigned long long)__popcll(b2);
-                acc[3] += (unsigned long long)__popcll(b0);
+            if (cells[3] == cells[2]) tf[1] = NIB_P1_HEAD;           // game.py:205-214: P2 tests after P1's head is down
+            uint32_t alive = st.y & 3u;
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const bool oob = r[p] < 0 || c[p] < 0 || r[p] >= W || c[p] >= W;
+                if (oob || tf[p] != NIB_EMPTY) alive &= ~(1u << p);
             }
-        }
-
-        // ---- the stream: both planes of the chunks that can differ from memory (see above); a restarted board goes back
-        // into the tile as well
-        for (uint32_t i = (uint32_t)tid; i < nchunks; i += BLOCK) {
-            const uint32_t le = chunk_env(i, cpe, cpe_magic);
-            const uint32_t k = i - le * cpe;
-            const uint32_t ri = rec_out[le].w;
-            const uint2 mv = rec_mv[le];
-            const uint32_t mx = mv.x ^ (k * 0x10001u), my = mv.y ^ (k * 0x10001u);
-            bool put = !(mx & 0xFFFFu) || !(mx >> 16) || !(my & 0xFFFFu) || !(my >> 16);
-            if (!put && !(ri >> 31)) continue;
-            const uint32_t c = k * 16u;
-            const int nb = min(16, G - (int)c);
-            uint4 t = tile[i];
-            if (ri >> 31) {                                            // restarted env: fresh board + heads (as obs_tile)
-                uint4 n = tmpl[k];
-                const uint32_t d1 = (ri & 0x3FFFu) - c, d2 = ((ri >> 14) & 0x3FFFu) - c;
-                const uint32_t v1 = (uint32_t)(0x01 ^ 0x0A) << ((d1 & 3u) * 8u), v2 = (uint32_t)(0x01 ^ 0xF6) << ((d2 & 3u) * 8u);
-                n.x ^= (d1 < 4u ? v1 : 0u) ^ (d2 < 4u ? v2 : 0u);
-                n.y ^= (d1 - 4u < 4u ? v1 : 0u) ^ (d2 - 4u < 4u ? v2 : 0u);
-                n.z ^= (d1 - 8u < 4u ? v1 : 0u) ^ (d2 - 8u < 4u ? v2 : 0u);
-                n.w ^= (d1 - 12u < 4u ? v1 : 0u) ^ (d2 - 12u < 4u ? v2 : 0u);
-                // the tile holds memory's bytes except in the marked chunks, which are stored anyway
-                if (n.x == t.x && n.y == t.y && n.z == t.z && n.w == t.w) {
-                    if (!put) continue;
+            // game.py:264-275 — done / winner (same cell => draw)
+            const int n_alive = (int)(alive & 1u) + (int)((alive >> 1) & 1u);
+            if (n_alive <= 1) {
+                if (n_alive == 1 && (r[0] != r[1] || c[0] != c[1])) winner = (alive & 1u) ? 1 : 2;
+                done = true;
+            }
+            if (out.reward) {                                        // rewards: util.py:87-94 / DDQN.py:289-305 / DQN.py:224-241
+                if (!done) {
+                    rw0 = rw1 = P.r_index ? (float)st.z : P.r_step;
+                } else if (winner == 0) {
+                    rw0 = rw1 = P.r_draw;
                 } else {
-                    tile[i] = n;
+                    rw0 = (winner == 1) ? P.r_win : P.r_lose;
+                    rw1 = (winner == 2) ? P.r_win : P.r_lose;
                 }
-                t = n;
             }
-            const uint32_t w1[4] = {t.x, t.y, t.z, t.w};
-            const uint32_t w2[4] = {swap_codes4(t.x), swap_codes4(t.y), swap_codes4(t.z), swap_codes4(t.w)};
-            int8_t *o1 = otile + (size_t)le * 2u * G + c;
-            store_chunk<true>(o1, nb, w1);
-            store_chunk<true>(o1 + G, nb, w2);
+            st = make_uint4(pack_pos(r[0], c[0], r[1], c[1]),
+                            alive | (done ? META_DONE : 0u) | ((uint32_t)winner << 4) | ((uint32_t)(a[0] + 1) << 8) |
+                                ((uint32_t)(a[1] + 1) << 12),
+                            st.z + 1u, st.w + 1u);
+            st_dirty = true;
+            if (!(done && autoreset)) {
+                // the writes in the reference's order: bodies, then P1's head, then P2's (an out-of-bounds head lands on
+                // the border WALL cell; a same-cell head-on leaves P2's head).  Cells that share a byte: a later write
+                // starts from the earlier one's byte, and same-lane LDS writes keep their order.
+                const uint32_t nib[4] = {NIB_P1_BODY, NIB_P2_BODY, NIB_P1_HEAD, NIB_P2_HEAD};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const uint32_t sh = (uint32_t)(cells[k] & 1) * 4u;
+                    b[k] = (b[k] & ~(0xFu << sh)) | (nib[k] << sh);
+#pragma unroll
+                    for (int j = k + 1; j < 4; ++j)
+                        if ((cells[j] >> 1) == (cells[k] >> 1)) b[j] = b[k];
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    cellb[cells[k] >> 1] = (unsigned char)b[k];
+                    sm |= 1ull << (cells[k] >> 4);
+                }
+                mask |= sm;
+            }
         }
-        if (wave == 0 && lane < ne) {
-            const uint4 st = rec_st[lane];                             // (this wave's own write of the move phase)
-            if (last) {
-                if (st_dirty) P.st4[env] = st;
+        if (mine && done && autoreset) {                             // ACKTR.py:307-310
+            restart = true;
+            st = make_uint4(rs.z, META_ALIVE0 | META_ALIVE1, 0u, st.w);
+            st_dirty = true;
+            h1 = (uint32_t)cell_index(S, (int)(int8_t)(rs.z), (int)(int8_t)(rs.z >> 8));
+            h2 = (uint32_t)cell_index(S, (int)(int8_t)(rs.z >> 16), (int)(int8_t)(rs.z >> 24));
+            const unsigned long long heads = (1ull << (h1 >> 4)) | (1ull << (h2 >> 4));
+            sm = mask | heads;
+            mask = heads;
+        }
+        STAMP(1);
+
+        // ---- the stores: both planes of the chunks in sm, from the board — or, for a restarted env, from the template
+        // with the heads in, which goes back into the board as well
+        while (sm) {
+            const uint32_t k = (uint32_t)__ffsll((long long)sm) - 1u;
+            sm &= sm - 1ull;
+            const uint32_t cb = k * 16u;
+            uint32_t p0, p1;
+            if (restart) {
+                p0 = tmpl[2u * k];
+                p1 = tmpl[2u * k + 1u];
+                // the head cells are EMPTY in the template: XOR turns that nibble into the head's (game.py:90-91)
+                const uint32_t d1 = h1 - cb, d2 = h2 - cb;
+                const uint32_t v1 = (NIB_EMPTY ^ NIB_P1_HEAD) << ((d1 & 7u) * 4u), v2 = (NIB_EMPTY ^ NIB_P2_HEAD) << ((d2 & 7u) * 4u);
+                p0 ^= (d1 < 8u ? v1 : 0u) ^ (d2 < 8u ? v2 : 0u);
+                p1 ^= (d1 - 8u < 8u ? v1 : 0u) ^ (d2 - 8u < 8u ? v2 : 0u);
+                board[2u * k] = p0;
+                board[2u * k + 1u] = p1;
             } else {
-                uint32_t x[4];
-                philox4x32_10((uint32_t)env, st.w, RNG_STEP, 0u, P.seed, P.stream, x);
-                x0 = x[0];
-                x1 = x[1];
+                p0 = board[2u * k];
+                p1 = board[2u * k + 1u];
             }
+            uint32_t w1[4];
+            expand_codes8(p0, w1[0], w1[1]);
+            expand_codes8(p1, w1[2], w1[3]);
+            const uint32_t w2[4] = {swap_codes4(w1[0]), swap_codes4(w1[1]), swap_codes4(w1[2]), swap_codes4(w1[3])};
+            const int nbk = min(16, G - (int)cb);
+            store_chunk<true>(oenv + cb, nbk, w1);
+            store_chunk<true>(oenv + G + cb, nbk, w2);
         }
-        __syncthreads();        // the restarted boards and rs_in are in LDS before the next move reads them
+        STAMP(2);
+
+        // ---- the records and the totals
+        if (mine) {
+            if (out.done) out.done[env] = (int8_t)done;
+            if (out.winner) out.winner[env] = (int8_t)winner;
+            if (out.reward) reinterpret_cast<float2 *>(out.reward)[env] = make_float2(rw0, rw1);
+        }
+        if (out.totals) {
+            const int wn = (stepped && done) ? winner : -1;
+            n_steps += (uint32_t)__popcll(__ballot(stepped));
+            n_w1 += (uint32_t)__popcll(__ballot(wn == 1));
+            n_w2 += (uint32_t)__popcll(__ballot(wn == 2));
+            n_draw += (uint32_t)__popcll(__ballot(wn == 0));
+        }
+
+        // ---- the next start of the envs that restarted (rs4 moves on one game), then the coming step's Philox words
+        if (restart) {
+            const NewGame ng = make_game(P.seed, P.stream, W, P.fair, (uint32_t)env, rs.y + 1u);
+            rs = make_uint4(rs.w, rs.y + 1u, pack_pos(ng.r1, ng.c1, ng.r2, ng.c2), pack_envp(ng.w0, ng.w1, ng.degree));
+            rs_dirty = true;
+        }
+        if (mine && s + 1 < k_steps) {
+            uint32_t x[4];
+            philox4x32_10((uint32_t)env, st.w, RNG_STEP, 0u, P.seed, P.stream, x);
+            x0 = x[0];
+            x1 = x[1];
+        }
+        STAMP(3);
     }
+
+    // ---- epilogue: the state words, and the wave's totals in one atomic per counter
+    {
+        Params P;
+        load_params_scalar(P, kp);
+        if (mine && st_dirty) P.st4[env] = st;
+        if (mine && rs_dirty) P.rs4[env] = rs;
+    }
+#ifndef TRON_STAMPS
+    if (out.totals && lane == 0) {
+        if (n_steps) atomicAdd(&out.totals[0], (unsigned long long)n_steps);
+        if (n_w1) atomicAdd(&out.totals[1], (unsigned long long)n_w1);
+        if (n_w2) atomicAdd(&out.totals[2], (unsigned long long)n_w2);
+        if (n_draw) atomicAdd(&out.totals[3], (unsigned long long)n_draw);
+    }
+#endif
 }
 
-// The random-action rollout as ONE launch for k_steps steps (tron_rollout_random): envs never interact,
-// so a workgroup can step its own tile k_steps times without waiting for anybody else — there is no
-// drain of the whole chip between steps.  The same results, bit for bit, as k_steps launches of k_obs.
-// One tile per workgroup (gridDim.x == ntiles): memory is read in the first step only (roll_resident).
-// TRON_ROLLOUT_RESIDENT asks for what this kernel does by itself; the flag is accepted for its callers' sake.
-// A kernel of its own beside k_obs_roll_walk: 64 VGPRs here against obs_tile's 108.
-__global__ __launch_bounds__(BLOCK) void k_obs_roll(Params P, int E, uint32_t cpe, uint32_t cpe_magic, uint32_t flags,
-                                                   StepOut out, int k_steps, int ntiles)
+// The random-action rollout as ONE launch for k_steps steps (tron_rollout_random): envs never interact, so a wave can
+// step its own envs k_steps times without waiting for anybody else — there is no drain of the whole chip between steps
+// and no barrier between the waves of a workgroup.  The same results, bit for bit, as k_steps launches of k_obs.
+// E envs per workgroup, epw (<= 64) per wave, blockDim.x / 64 waves; gridDim.x == ceil(N / E).  Mode None, int8 codes,
+// even side, cpe <= 64 (roll_resident).  TRON_ROLLOUT_RESIDENT asks for what this kernel does by itself; the flag is
+// accepted for its callers' sake.
+__global__ __launch_bounds__(BLOCK) void k_obs_roll(Params P, int E, int epw, uint32_t cpe, uint32_t flags, StepOut out, int k_steps)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // the {steps, wins, wins, draws} counters are summed in LDS over the whole launch and flushed once:
-    // 4 global atomics per tile per step on the same four words serialise in L2 (98 us per step measured)
-    __shared__ unsigned long long acc[4];
-    if (out.totals) {
-        if (threadIdx.x < 4) acc[threadIdx.x] = 0ull;
-        __syncthreads();
-    }
     // The step's parameters are re-read from the kernel-argument segment at every step (scalar loads through a pointer the
     // compiler cannot see through) instead of kept live across the loop: 26 words of Params in SGPRs for the whole launch
     // spill, and every spilled word is a v_readlane per use.
     kernarg_t *kp = (kernarg_t *)__builtin_amdgcn_kernarg_segment_ptr();       // (Params is the first argument)
-    roll_resident(kp, E, cpe, cpe_magic, flags & ~TRON_ROLLOUT_RESIDENT, out, acc, k_steps, smem);
-    if (out.totals && threadIdx.x < 4 && acc[threadIdx.x]) atomicAdd(&out.totals[threadIdx.x], acc[threadIdx.x]);
+    roll_resident(kp, E, epw, cpe, flags & ~TRON_ROLLOUT_RESIDENT, out, k_steps, smem);
 }
 
 // Fewer workgroups than tiles (the TRON_ROLL_GRID override): workgroup w owns tiles w, w + gridDim.x, ... and
@@ -1726,6 +1814,7 @@ struct tron_env {
     hipEvent_t fork, join;
     int part0, nparts;        // slice of the tiles the next launch covers (0, 1 = all of them)
     int roll_E;               // envs per tile of the persistent rollout (0: not chosen yet), see roll_tile_envs
+    int roll_waves;           // waves per workgroup of k_obs_roll (0: not chosen yet), see roll_waves
 };
 
 namespace {
@@ -2178,31 +2267,85 @@ int roll_tile_envs(const tron_env *h)
     return best;
 }
 
+// Mode None on boards of at most 64 chunks (sides up to 30): k_obs_roll, one lane per env.  Envs per wave x waves per
+// workgroup, swept at 65 536 x 24x24 (us per step at 64 steps per launch; parent 13.1; the 20-step form is in
+// profiles/r07_rollout_ab.txt):  64 x 1: 6.90   64 x 2: 8.41   64 x 4: 6.66   32 x 1: 7.85   32 x 2: 7.92   32 x 4: 7.84
+// 16 x 1: 11.04   16 x 2: 11.03   16 x 4: 10.99
+// Full waves win: the step is bound by the instructions a SIMD issues, and a wave of 16 or 32 envs issues as many as one of
+// 64, so two or four narrow waves per SIMD cost what they were meant to hide.  Four waves of 64 per workgroup take 89 KB of
+// LDS at 24x24: one workgroup per CU and one wave per SIMD wherever the dispatcher puts them, where 1 024 one-wave or 512
+// two-wave workgroups land unevenly (64 x 2: some CUs hold three).  Repeated runs of 64 x 1 against 64 x 4 are in
+// profiles/r07_rollout_ab.txt.  A batch with no more 64-env waves than the chip has CUs gets one wave per workgroup, so that
+// it spreads over the CUs: a rule of thumb, not measured (the sweep is at 65 536 envs only).  Chosen once per handle.
+constexpr int ROLL_EPW = 64;
+int roll_waves(tron_env *h)
+{
+    if (!h->roll_waves) {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) { (void)hipGetLastError(); cus = 0; }
+        h->roll_waves = (h->P.N + ROLL_EPW - 1) / ROLL_EPW > cus ? BLOCK / WAVE : 1;
+    }
+    return h->roll_waves;
+}
+
+int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipStream_t st, int E, int waves, int chunk)
+{
+    if (waves < 1) waves = 1;
+    if (E > waves * WAVE) waves = (E + WAVE - 1) / WAVE;            // at most 64 envs per wave
+    if (waves > BLOCK / WAVE) return TRON_ERR_BAD_ARG;
+    const int epw = (E + waves - 1) / waves;
+    const int grid = (h->P.N + E - 1) / E;
+    const size_t smem = ((size_t)E * (2u * h->cpe + 1u) + 2u * h->cpe) * 4u;    // the packed boards + the template (roll_resident)
+    if (smem > 160u * 1024u) return TRON_ERR_BAD_ARG;
+    static uint64_t prepared = 0;
+    allow_big_lds(reinterpret_cast<const void *>(k_obs_roll), h->device, prepared);
+    static bool report = getenv("TRON_ROLL_REPORT") != nullptr;         // the launch shape and its occupancy on stderr, once per process
+    if (report) {
+        report = false;
+        int per_cu = 0;
+        hipDeviceProp_t prop;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_obs_roll, waves * WAVE, smem) == hipSuccess &&
+            hipGetDeviceProperties(&prop, h->device) == hipSuccess)
+            fprintf(stderr, "k_obs_roll: %d envs per workgroup, %d waves of %d envs, %zu B of LDS, grid %d; %d workgroups per CU x %d CUs = %d resident\n",
+                    E, waves, epw, smem, grid, per_cu, prop.multiProcessorCount, per_cu * prop.multiProcessorCount);
+        (void)hipGetLastError();
+    }
+    for (int left = k_steps; left > 0; left -= chunk) {
+        hipLaunchKernelGGL(k_obs_roll, dim3(grid), dim3(waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, out, left < chunk ? left : chunk);
+        if (launch_status() != TRON_OK) return TRON_ERR_LAUNCH;
+    }
+    return TRON_OK;
+}
+
 int rollout_persistent(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipStream_t st)
 {
-    static int env_e = 0, env_grid = 0, chunk = TRON_ROLLOUT_CHUNK;
+    static int env_e = 0, env_grid = 0, env_waves = 0, chunk = TRON_ROLLOUT_CHUNK;
     static bool probed = false;
     if (!probed) {
         if (const char *v = getenv("TRON_ROLL_E")) env_e = atoi(v);
+        if (const char *v = getenv("TRON_ROLL_WAVES")) env_waves = atoi(v);
         if (const char *v = getenv("TRON_ROLL_GRID")) env_grid = atoi(v);
         if (const char *v = getenv("TRON_ROLL_CHUNK")) chunk = atoi(v) > 0 ? atoi(v) : TRON_ROLLOUT_CHUNK;
         probed = true;
     }
-    static uint64_t prepared = 0, prepared_w = 0;
-    allow_big_lds(reinterpret_cast<const void *>(k_obs_roll), h->device, prepared);
+    const bool sliding = h->P.mode != TRON_MODE_NONE;
+    if (!sliding && h->cpe <= 64u) {
+        // TRON_ROLL_E stays envs per workgroup, TRON_ROLL_WAVES its waves; a TRON_ROLL_GRID below the workgroup count asks for
+        // the walking kernel below
+        const int waves = env_waves > 0 ? env_waves : roll_waves(h);
+        const int E = env_e > 0 ? env_e : waves * ROLL_EPW;
+        if (!(env_grid > 0 && env_grid < (h->P.N + E - 1) / E)) return rollout_wave(h, k_steps, flags, out, st, E, waves, chunk);
+    }
+    static uint64_t prepared_w = 0;
     allow_big_lds(reinterpret_cast<const void *>(k_obs_roll_walk), h->device, prepared_w);
     if (!h->roll_E) h->roll_E = roll_tile_envs(h);
-    const bool sliding = h->P.mode != TRON_MODE_NONE;
-    // the sliding modes (obs_tile every step): the per-step tile for a call that fits ONE launch and for the resident variant,
-    // else the tile with the fullest last round — measured at 65 536 x 24x24.  Mode None (roll_resident, 64 VGPRs, six
-    // 32-env workgroups per CU by LDS): the per-step tile; swept with sparse stores at 65 536 x 24x24, 64 / 20 steps per
-    // launch: 32 envs 13.0 / 14.6 us per step, 26: 13.4 / 15.0, 24: 14.0 / 15.6, 20: 15.0 / 16.7, 16: 15.8 / 17.5,
-    // 12: 19.0 / 20.5, 8: 24.0 / 25.9, 40: 14.1 / 15.7, 48: 15.3 / 17.0, 64: 16.0 / 17.7
+    // obs_tile every step (the sliding modes; mode None on boards of more than 64 chunks or with TRON_ROLL_GRID: k_obs_roll_walk).
+    // The sliding modes: the per-step tile for a call that fits ONE launch and for the resident variant, else the tile with the
+    // fullest last round — measured at 65 536 x 24x24.  Mode None: the per-step tile.
     const int E = env_e > 0 ? env_e : !sliding ? h->E : ((flags & TRON_ROLLOUT_RESIDENT) || k_steps <= chunk) ? h->E : h->roll_E;
     const int ntiles = (h->P.N + E - 1) / E;
     const int grid = (env_grid > 0 && env_grid < ntiles) ? env_grid : ntiles;
-    // + k_obs_roll's rec_mv (8 bytes per env)
-    const size_t smem = ((size_t)E + 1u) * h->cpe * 16u + 4u * (size_t)E * 16u + (!sliding && grid == ntiles ? 8u * (size_t)E : 0u);
+    const size_t smem = ((size_t)E + 1u) * h->cpe * 16u + 4u * (size_t)E * 16u;
     if (smem > 160u * 1024u) return TRON_ERR_BAD_ARG;
     if (sliding) {
         static uint64_t prepared_s = 0;
@@ -2211,9 +2354,6 @@ int rollout_persistent(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out
     for (int left = k_steps; left > 0; left -= chunk) {
         if (sliding)
             hipLaunchKernelGGL(k_obs_roll_slide, dim3(grid), dim3(BLOCK), smem, st, h->P, E, h->cpe, h->cpe_magic, flags, out,
-                               left < chunk ? left : chunk, ntiles);
-        else if (grid == ntiles)
-            hipLaunchKernelGGL(k_obs_roll, dim3(grid), dim3(BLOCK), smem, st, h->P, E, h->cpe, h->cpe_magic, flags, out,
                                left < chunk ? left : chunk, ntiles);
         else
             hipLaunchKernelGGL(k_obs_roll_walk, dim3(grid), dim3(BLOCK), smem, st, h->P, E, h->cpe, h->cpe_magic, flags, out,
