@@ -87,8 +87,9 @@ __device__ __forceinline__ int draw_action(uint32_t x, uint32_t last, bool nonre
 // reset stream of (env, episode): u32 number n is word n%4 of Philox(ctr = {env, episode,
 // RNG_RESET, n/4}).  (x, y) of the reference are (row, col).  Only player 1 is re-drawn on a
 // clash (util.py:76-78); bounded at 16 redraw rounds for the GPU.  Written as one loop over the
-// draw index with a phase variable so the Philox body exists once in the code.
-__device__ inline NewGame make_game(uint32_t seed, uint32_t stream, int W, int fair, uint32_t env, uint32_t episode)
+// draw index with a phase variable so the Philox body exists once in the code.  This is the
+// general routine: make_game below takes it for the lanes whose first draw clashes, and only then.
+__device__ inline NewGame make_game_general(uint32_t seed, uint32_t stream, int W, int fair, uint32_t env, uint32_t episode)
 {
     NewGame g{0, 0, 0, 0, 0, 0, 0};
     int lb1x = 0, lb1y = 0, lb2x = 0, lb2y = 0;
@@ -154,6 +155,42 @@ __device__ inline NewGame make_game(uint32_t seed, uint32_t stream, int W, int f
             }
         }
     }
+    return g;
+}
+
+// The same game as make_game_general, drawn as straight-line code.  Without a clash the draws sit at
+// fixed positions of the stream: x1, y1, x2, y2, weight0, weight1, degree are words 0..6 (blocks 0
+// and 1); with `fair`, point_y and point_x come first and the seven are words 2..8 (blocks 0..2).
+// A clash (1 start in W^2; more often with `fair`, whose two boxes meet in the middle of the board)
+// moves every later draw, so those lanes, and only those, start over in the general routine.
+__device__ __forceinline__ NewGame make_game(uint32_t seed, uint32_t stream, int W, int fair, uint32_t env, uint32_t episode)
+{
+    uint32_t u[12];
+    philox4x32_10(env, episode, RNG_RESET, 0u, seed, stream, u);
+    philox4x32_10(env, episode, RNG_RESET, 1u, seed, stream, u + 4);
+    NewGame g;
+    if (!fair) {                                            // util.py:64-74, game.py:83,87
+        g.r1 = randint_u32(u[0], 0, W - 1);
+        g.c1 = randint_u32(u[1], 0, W - 1);
+        g.r2 = randint_u32(u[2], 0, W - 1);
+        g.c2 = randint_u32(u[3], 0, W - 1);
+        g.w0 = randint_u32(u[4], 40, 101);
+        g.w1 = randint_u32(u[5], 40, 101);
+        g.degree = randint_u32(u[6], -30, 30);
+    } else {                                                // util.py:49-62: boxes around a point and its mirror image
+        philox4x32_10(env, episode, RNG_RESET, 2u, seed, stream, u + 8);
+        const int py = randint_u32(u[0], 0, W - 1), px = randint_u32(u[1], 0, W - 1);
+        const int lb1x = max(0, px - 1), ub1x = min(W - 1, px + 1);
+        const int lb1y = max(0, py - 1), ub1y = min(W - 1, py + 1);
+        g.r1 = randint_u32(u[2], lb1x, ub1x);
+        g.c1 = randint_u32(u[3], lb1y, ub1y);
+        g.r2 = randint_u32(u[4], W - 1 - ub1x, W - 1 - lb1x);
+        g.c2 = randint_u32(u[5], W - 1 - ub1y, W - 1 - lb1y);
+        g.w0 = randint_u32(u[6], 40, 101);
+        g.w1 = randint_u32(u[7], 40, 101);
+        g.degree = randint_u32(u[8], -30, 30);
+    }
+    if (g.r1 == g.r2 && g.c1 == g.c2) g = make_game_general(seed, stream, W, fair, env, episode);
     return g;
 }
 

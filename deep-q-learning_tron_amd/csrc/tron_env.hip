@@ -30,7 +30,9 @@
 //   k_obs_roll, k_tile_roll tron_rollout_random: up to TRON_ROLLOUT_CHUNK steps in ONE launch.  k_obs_roll (roll_resident):
 //                           one lane per env and a wave on its own for the whole launch — no barrier in the step loop,
 //                           boards in LDS at 4 bits per cell (the whole batch resident in one round), memory read in the
-//                           prologue only, a step stores the chunks of a per-env mask.  k_tile_roll, k_obs_roll_walk
+//                           prologue only, a step stores the chunks of a per-env mask (both planes from the packed
+//                           board, the player-2 one swapped in nibble space), a restart draws its next game as
+//                           straight-line code (make_game).  k_tile_roll, k_obs_roll_walk
 //                           (boards of more than 64 chunks, TRON_ROLL_GRID) and k_obs_roll_slide: the per-tile step
 //                           (tile_step / obs_tile), each workgroup stepping its own tiles
 //   k_inc                   TRON_STEP_INCREMENTAL: writes only the touched cells + restarted boards
@@ -416,7 +418,7 @@ __device__ __forceinline__ void tile_step(const Params &P, int E, uint32_t cpe, 
                     a[1] = (int)((R.act >> 8) & 3u);
                 }
                 if (autoreset) {       // speculative: stored only if this env restarts in this launch
-                    const NewGame ng = make_game(P.seed, P.stream, P.W, P.fair, (uint32_t)env, R.episode + 1u);
+                    const NewGame ng = make_game_general(P.seed, P.stream, P.W, P.fair, (uint32_t)env, R.episode + 1u);    // (the straight-line make_game costs these kernels 5-6 VGPRs)
                     rec_rs[tid] = make_uint4(R.nenvp, R.episode + 1u, pack_pos(ng.r1, ng.c1, ng.r2, ng.c2),
                                              pack_envp(ng.w0, ng.w1, ng.degree));
                 }
@@ -906,7 +908,7 @@ __device__ __forceinline__ void obs_tile(const Params &P, int E, uint32_t cpe, u
                 }
             } else if (wave == 1 && autoreset) {
                 rs_in[lane] = rs;
-                const NewGame ng = make_game(P.seed, P.stream, P.W, P.fair, (uint32_t)env, rs.y + 1u);
+                const NewGame ng = make_game_general(P.seed, P.stream, P.W, P.fair, (uint32_t)env, rs.y + 1u);
                 rec_rs[lane] = make_uint4(rs.w, rs.y + 1u, pack_pos(ng.r1, ng.c1, ng.r2, ng.c2),
                                           pack_envp(ng.w0, ng.w1, ng.degree));
             }
@@ -1045,12 +1047,27 @@ __device__ __forceinline__ uint32_t pack_codes8(uint32_t w0, uint32_t w1)       
     const uint32_t ta = a | (a >> 4), tb = b | (b >> 4);                        // bytes 0 and 2 hold two nibbles each
     return (ta & 0xFFu) | ((ta >> 8) & 0xFF00u) | ((tb & 0xFFu) << 16) | ((tb << 8) & 0xFF000000u);
 }
+// No multiply: the code of a nibble is a byte LUT on its low three bits (0 -> 0, 1 -> 1, 2 (A) -> 0x0A, 5 (D) -> 0xF5,
+// 6 (6 / E) -> 0xF6, 7 (F) -> 0xF7) with the nibble's bit 3 put back on top.  The same routine serves both players' nibbles.
+constexpr uint32_t EXPAND_LO = pack4(0, 1, 0x0A, 0), EXPAND_HI = pack4(0, 0xF5, 0xF6, 0xF7);
 __device__ __forceinline__ void expand_codes8(uint32_t p, uint32_t &w0, uint32_t &w1)   // 8 nibbles -> 8 code bytes
 {
-    const uint32_t lo = p & 0x0F0F0F0Fu, hi = (p >> 4) & 0x0F0F0F0Fu;           // even / odd cells
-    const uint32_t a = __builtin_amdgcn_perm(hi, lo, 0x05010400u), b = __builtin_amdgcn_perm(hi, lo, 0x07030602u);
-    w0 = a | (((a >> 2) & 0x01010101u) * 0xF0u);
-    w1 = b | (((b >> 2) & 0x01010101u) * 0xF0u);
+    const uint32_t q = p >> 4;                                                  // p: even cells, q: odd cells
+    const uint32_t lo = __builtin_amdgcn_perm(EXPAND_HI, EXPAND_LO, p & 0x07070707u) | (p & 0x08080808u);
+    const uint32_t hi = __builtin_amdgcn_perm(EXPAND_HI, EXPAND_LO, q & 0x07070707u) | (q & 0x08080808u);
+    w0 = __builtin_amdgcn_perm(hi, lo, 0x05010400u);
+    w1 = __builtin_amdgcn_perm(hi, lo, 0x07030602u);
+}
+// Player-2 nibbles from player-1 nibbles, eight cells at once (swap_codes4 in nibble space): bodies E <-> D are ^ 3, heads
+// A <-> 6 are ^ 0xC, and 1, F and the padding 0 stay.  With the nibble's bits b3..b0, a head is b3 ^ b2 and a body is
+// b3 & b2 & (b1 ^ b0).
+__device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
+{
+    const uint32_t s = p >> 1;
+    const uint32_t x = p ^ s;                                                   // bit 0: b1 ^ b0, bit 2: b3 ^ b2 (bit 3 is not used)
+    const uint32_t body = ((p & s) >> 2) & 0x11111111u;                         // bit 0: b3 & b2
+    const uint32_t z = x & (body | 0x44444444u);                                // bit 0: a body, bit 2: a head
+    return p ^ z ^ (z << 1);
 }
 
 // The steps of a persistent launch (k_obs_roll): ONE LANE = ONE ENV for the whole launch, and a wave owns its envs from the
@@ -1072,6 +1089,11 @@ __device__ __forceinline__ void expand_codes8(uint32_t p, uint32_t &w0, uint32_t
 // template, whoever wrote it; a move stores and marks the chunks of its four cells; a restart stores the chunks in
 // mask | chunks of the two new heads from the template with the heads patched in, and the mask becomes the head chunks.
 // Nothing is compared in the loop, and a chunk outside the mask holds the template in memory and in LDS alike.
+// With one wave per SIMD nothing hides an instruction, so the two parts every wave runs in nearly every step are kept short:
+// a trip of the store loop is one LDS read from a per-lane source (board or template), a head patch that is zero for a
+// lane that did not restart, the player-2 nibbles (swap_nibbles8), four multiply-free expansions and two 16-byte stores, with
+// the plane's short last chunk in a branch of its own; and the next game of a restarted env is drawn by make_game, two
+// Philox blocks and seven draws in a line, whose lanes go on into the general routine only when their two starts clash.
 // An env that restarts in the step it finishes in skips the move's four cell writes: its board is rebuilt from the mask
 // as it was before the move.  st4 / rs4 are written by the epilogue (same bytes as one store per step leaves behind).
 // Not reachable through the API today: tron_rollout_random always sets TRON_STEP_AUTORESET and passes out.totals only, so
@@ -1266,33 +1288,55 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         STAMP(1);
 
         // ---- the stores: both planes of the chunks in sm, from the board — or, for a restarted env, from the template
-        // with the heads in, which goes back into the board as well
-        while (sm) {
-            const uint32_t k = (uint32_t)__ffsll((long long)sm) - 1u;
-            sm &= sm - 1ull;
-            const uint32_t cb = k * 16u;
-            uint32_t p0, p1;
-            if (restart) {
-                p0 = tmpl[2u * k];
-                p1 = tmpl[2u * k + 1u];
-                // the head cells are EMPTY in the template: XOR turns that nibble into the head's (game.py:90-91)
-                const uint32_t d1 = h1 - cb, d2 = h2 - cb;
-                const uint32_t v1 = (NIB_EMPTY ^ NIB_P1_HEAD) << ((d1 & 7u) * 4u), v2 = (NIB_EMPTY ^ NIB_P2_HEAD) << ((d2 & 7u) * 4u);
-                p0 ^= (d1 < 8u ? v1 : 0u) ^ (d2 < 8u ? v2 : 0u);
-                p1 ^= (d1 - 8u < 8u ? v1 : 0u) ^ (d2 - 8u < 8u ? v2 : 0u);
-                board[2u * k] = p0;
-                board[2u * k + 1u] = p1;
-            } else {
-                p0 = board[2u * k];
-                p1 = board[2u * k + 1u];
+        // with the heads in, which goes back into the board as well.  One read per trip, from a per-lane source; the head
+        // patch is zero for a lane that did not restart (its head chunks are chunk ~0), and only the board write-back is
+        // under `restart`.  The short last chunk (G % 16 cells: border wall, stored after a head died on it and by the
+        // restart that clears it) has its own branch, so the loop's stores are whole 16-byte ones.
+        {
+            const uint32_t src = restart ? (uint32_t)(tmpl - board) : 0u;       // dwords from the lane's board
+            const uint32_t hk1 = restart ? h1 >> 4 : ~0u, hk2 = restart ? h2 >> 4 : ~0u;
+            // the head cells are EMPTY in the template: XOR turns that nibble into the head's (game.py:90-91)
+            const unsigned long long v1 = (unsigned long long)(NIB_EMPTY ^ NIB_P1_HEAD) << ((h1 & 15u) * 4u);
+            const unsigned long long v2 = (unsigned long long)(NIB_EMPTY ^ NIB_P2_HEAD) << ((h2 & 15u) * 4u);
+            int8_t *const o1 = oenv, *const o2 = oenv + G;
+            auto chunk = [&](uint32_t k, uint32_t (&w1)[4], uint32_t (&w2)[4]) {
+                const unsigned long long v = (k == hk1 ? v1 : 0ull) ^ (k == hk2 ? v2 : 0ull);
+                const uint32_t p0 = board[src + 2u * k] ^ (uint32_t)v, p1 = board[src + 2u * k + 1u] ^ (uint32_t)(v >> 32);
+                if (restart) {
+                    board[2u * k] = p0;
+                    board[2u * k + 1u] = p1;
+                }
+                expand_codes8(p0, w1[0], w1[1]);
+                expand_codes8(p1, w1[2], w1[3]);
+                expand_codes8(swap_nibbles8(p0), w2[0], w2[1]);
+                expand_codes8(swap_nibbles8(p1), w2[2], w2[3]);
+            };
+            const uint32_t tail = (uint32_t)G & 15u;                            // cells of the last chunk if it is short: 4, 8 or 12
+            if (tail && ((sm >> (cpe - 1u)) & 1ull)) {
+                sm &= ~(1ull << (cpe - 1u));
+                const uint32_t cb = (cpe - 1u) * 16u;
+                uint32_t w1[4], w2[4];
+                chunk(cpe - 1u, w1, w2);
+                uint32_t *q1 = reinterpret_cast<uint32_t *>(o1 + cb), *q2 = reinterpret_cast<uint32_t *>(o2 + cb);
+                q1[0] = w1[0];                                                   // never past G: the next plane starts there
+                q2[0] = w2[0];
+                if (tail > 4u) {
+                    q1[1] = w1[1];
+                    q2[1] = w2[1];
+                }
+                if (tail > 8u) {
+                    q1[2] = w1[2];
+                    q2[2] = w2[2];
+                }
             }
-            uint32_t w1[4];
-            expand_codes8(p0, w1[0], w1[1]);
-            expand_codes8(p1, w1[2], w1[3]);
-            const uint32_t w2[4] = {swap_codes4(w1[0]), swap_codes4(w1[1]), swap_codes4(w1[2]), swap_codes4(w1[3])};
-            const int nbk = min(16, G - (int)cb);
-            store_chunk<true>(oenv + cb, nbk, w1);
-            store_chunk<true>(oenv + G + cb, nbk, w2);
+            while (sm) {
+                const uint32_t k = (uint32_t)__ffsll((long long)sm) - 1u;
+                sm &= sm - 1ull;
+                uint32_t w1[4], w2[4];
+                chunk(k, w1, w2);
+                *reinterpret_cast<U4A4 *>(o1 + k * 16u) = U4A4{w1[0], w1[1], w1[2], w1[3]};
+                *reinterpret_cast<U4A4 *>(o2 + k * 16u) = U4A4{w2[0], w2[1], w2[2], w2[3]};
+            }
         }
         STAMP(2);
 
