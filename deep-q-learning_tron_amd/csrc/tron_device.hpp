@@ -19,7 +19,8 @@ struct Params {
     int8_t *grid;              // [N][G] Tile values (map.py:9-17), storage [row+1][col+1] (map.py:86-92)
     uint4 *st4;                // [N] {pos, meta, eplen, tick}
                                //   pos  = r1 | c1<<8 | r2<<16 | c2<<24 (int8 each; game.py:36-41)
-                               //   meta = alive0 | alive1<<1 | done<<2 | winner<<4 | dir0<<8 | dir1<<12
+                               //   meta = alive0 | alive1<<1 | done<<2 | winner<<4 | dir0<<8 | dir1<<12 | slide marks<<16
+                               //          (pack_meta; the marks' count: observation-is-state layout, sliding modes)
                                //   eplen = steps in the current game; tick = steps since create (RNG counter)
     uint4 *rs4;                // [N] {envp, episode, nstart, nenvp}
                                //   envp = weight0 | weight1<<8 | (int8)degree<<16 (game.py:83,87)
@@ -44,6 +45,91 @@ __device__ __forceinline__ uint32_t pack_envp(int w0, int w1, int degree)
     return (uint32_t)(uint8_t)w0 | ((uint32_t)(uint8_t)w1 << 8) | ((uint32_t)(uint8_t)(int8_t)degree << 16);
 }
 __device__ __forceinline__ int cell_index(int S, int r, int c) { return (r + 1) * S + (c + 1); }
+
+// ---- the rule: Game.next_frame + Game.step (game.py:149-277), the parts that are register arithmetic ----
+// Written once; every env kernel's move (tron_env.hip) is these plus its own cell reads and writes.
+__device__ __forceinline__ void unpack_pos(uint32_t pos, int r[2], int c[2])
+{
+    r[0] = (int)(int8_t)(pos);       c[0] = (int)(int8_t)(pos >> 8);
+    r[1] = (int)(int8_t)(pos >> 16); c[1] = (int)(int8_t)(pos >> 24);
+}
+// player.py:124-132: action 0..3 = UP, RIGHT, DOWN, LEFT
+__device__ __forceinline__ void action_delta(int a, int &dr, int &dc)
+{
+    dr = (a == 0) ? -1 : (a == 2) ? 1 : 0;
+    dc = (a == 1) ? 1 : (a == 3) ? -1 : 0;
+}
+__device__ __forceinline__ bool on_board(int W, int r, int c) { return r >= 0 && c >= 0 && r < W && c < W; }
+// The non-sliding move: what each player hits, from the cells read before anything was written.  game.py:155-156 —
+// heads turn into bodies BEFORE anyone moves, so a target that is either old head is a body by now; game.py:205-214 —
+// player 2 tests after player 1's head is down.  old / f: the old and the new head cells; tf in: the two cells as read.
+template <class T>
+__device__ __forceinline__ void plain_targets(const int old[2], const int f[2], T tf[2], T p1_body, T p2_body, T p1_head)
+{
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        if (f[p] == old[0]) tf[p] = p1_body;
+        if (f[p] == old[1]) tf[p] = p2_body;
+    }
+    if (f[1] == f[0]) tf[1] = p1_head;
+}
+// game.py:205-214: player p, now at (r, c) on a cell that held `target`, dies off the board (its head lands on the
+// border WALL cell) or on anything but EMPTY
+__device__ __forceinline__ uint32_t collide(uint32_t alive, int p, int W, int r, int c, bool target_empty)
+{
+    return (!on_board(W, r, c) || !target_empty) ? alive & ~(1u << p) : alive;
+}
+// game.py:264-275: done / winner; two heads on the same cell are a draw whoever is still marked alive
+__device__ __forceinline__ bool settle(uint32_t alive, const int r[2], const int c[2], int &winner)
+{
+    const int n_alive = (int)(alive & 1u) + (int)((alive >> 1) & 1u);
+    if (n_alive > 1) return false;
+    if (n_alive == 1 && (r[0] != r[1] || c[0] != c[1])) winner = (alive & 1u) ? 1 : 2;
+    return true;
+}
+// util.py:87-94 / DDQN.py:289-305 / DQN.py:224-241; eplen = steps of this game before the move
+__device__ __forceinline__ void step_rewards(const Params &P, bool done, int winner, uint32_t eplen, float &rw0, float &rw1)
+{
+    if (!done) {
+        rw0 = rw1 = P.r_index ? (float)eplen : P.r_step;
+    } else if (winner == 0) {
+        rw0 = rw1 = P.r_draw;
+    } else {
+        rw0 = (winner == 1) ? P.r_win : P.r_lose;
+        rw1 = (winner == 2) ? P.r_win : P.r_lose;
+    }
+}
+// st4 after a move (st4.meta as laid out above; slide_cnt: the observation-is-state layout's slide log, bits 16-29) ...
+constexpr uint32_t SLIDE_CNT_SHIFT = 16u, SLIDE_CNT_MASK = 0x3FFFu;      // (a mark takes a cell and so does the head behind it: <= W W / 2 marks; 14 bits cover every side the 15-bit cell index allows)
+__device__ __forceinline__ uint32_t pack_meta(uint32_t alive, bool done, int winner, int a0, int a1, uint32_t slide_cnt = 0u)
+{
+    return alive | (done ? META_DONE : 0u) | ((uint32_t)winner << 4) | ((uint32_t)(a0 + 1) << 8) | ((uint32_t)(a1 + 1) << 12) |
+           (slide_cnt << SLIDE_CNT_SHIFT);
+}
+__device__ __forceinline__ uint4 stepped_st4(const int r[2], const int c[2], uint32_t meta, uint32_t eplen, uint32_t tick)
+{
+    return make_uint4(pack_pos(r[0], c[0], r[1], c[1]), meta, eplen + 1u, tick + 1u);
+}
+// ... and after a restart (ACKTR.py:307-310): the game drawn at the previous restart (rs4.nstart) begins; tick runs on
+__device__ __forceinline__ uint4 restarted_st4(uint32_t nstart, uint32_t tick)
+{
+    return make_uint4(nstart, META_ALIVE0 | META_ALIVE1, 0u, tick);
+}
+// The restart word tells whoever rebuilds a restarted board where the two heads go: bit 31 | head-1 cell | head-2 cell << 14
+// (0 = no restart; cell indices fit 14 bits, checked where the layouts that use the word are attached).
+__device__ __forceinline__ void start_cells(int S, uint32_t nstart, uint32_t &h1, uint32_t &h2)
+{
+    h1 = (uint32_t)cell_index(S, (int)(int8_t)(nstart), (int)(int8_t)(nstart >> 8));
+    h2 = (uint32_t)cell_index(S, (int)(int8_t)(nstart >> 16), (int)(int8_t)(nstart >> 24));
+}
+__device__ __forceinline__ uint32_t restart_word(int S, uint32_t nstart)
+{
+    uint32_t h1, h2;
+    start_cells(S, nstart, h1, h2);
+    return 0x80000000u | h1 | (h2 << 14);
+}
+__device__ __forceinline__ bool is_restart(uint32_t word) { return (word >> 31) != 0u; }
+__device__ __forceinline__ uint32_t restart_head(uint32_t word, int p) { return (word >> (14 * p)) & 0x3FFFu; }
 
 // ---- Philox-4x32-10 (Salmon et al., SC'11) ----------------------------------
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,

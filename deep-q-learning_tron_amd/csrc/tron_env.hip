@@ -38,6 +38,16 @@
 //   k_inc                   TRON_STEP_INCREMENTAL: writes only the touched cells + restarted boards
 //   k_reset, k_obs_reset, k_obs_to_grid, k_obs_planes, k_get_state, k_encode_codes, k_pop_up, ...
 //                           resets, read-back and stateless encodes
+//
+// Where the rule lives.  Game.next_frame + Game.step (game.py:149-277) as register arithmetic — action table, what a
+// player hits, collisions, done / winner, rewards, the st4 words, the restart word — is written once, in tron_device.hpp
+// ("the rule"); the slide decision (temper_threshold, slides) and the per-tile kernels' records (move_records) are below.
+// A kernel's move is those helpers plus its own cell reads and writes:
+//   k_tile, k_tile_roll                       lane_move<BoardCells>  six-cell sliding move on Tile bytes in LDS, dirty-chunk bits
+//   k_obs_slide, k_obs_roll_slide             lane_move<CodeCells>   the same body on player-1 code bytes, slide marks
+//   k_obs, k_obs_roll_walk                    lane_move_codes        mode None: two reads, four writes of code bytes in LDS
+//   k_inc                                     inline in the kernel   lane_move_codes' steps on code bytes in global memory
+//   k_obs_roll                                inline in roll_resident  the same steps on 4-bit codes in LDS, with the store mask
 #include "tron_device.hpp"
 #include "tron_minimax.hpp"
 #include "../../include/tron_hip.h"
@@ -172,68 +182,121 @@ struct EnvRegs {
     double slide;
 };
 
-// result records left in LDS by the move (read by waves 1-3 and by the stream)
+// ------------------------------------------------------------------ the rule --
+// Game.next_frame + Game.step (game.py:149-277).  Its register arithmetic is written once, in tron_device.hpp ("the
+// rule"): action_delta, plain_targets, collide, settle, step_rewards, pack_meta / stepped_st4 / restarted_st4,
+// restart_word.  Here: the slide decision (it reads g_rate_thr), the records of the per-tile kernels, and the sliding move.
+
+// "temper": player p's slide threshold from the table (ok: its degree and weight are inside the table's ranges).  The
+// move asks for both players' before anything else, so that they arrive under the cell reads.
+__device__ __forceinline__ void temper_threshold(uint32_t envp, int p, float &thr, bool &ok)
+{
+    const uint32_t di = (uint32_t)((int)(int8_t)(envp >> 16) + 30);
+    const uint32_t wi = ((envp >> (8 * p)) & 0xFFu) - 40u;
+    ok = di < (uint32_t)RATE_DEG && wi < (uint32_t)RATE_W;
+    thr = g_rate_thr[ok ? di * RATE_W + wi : 0u];
+}
+// game.py:169: random.random() <= rate — "ice": the env's slide rate; "temper": the table, or float64 get_rate outside it
+__device__ __forceinline__ bool slides(const Params &P, const EnvRegs &R, int p, float u, float thr, bool ok)
+{
+    if (P.mode == TRON_MODE_ICE) return (double)u <= R.slide;
+    if (ok) return u <= thr;
+    return (double)u <= get_rate((int)(int8_t)(R.envp >> 16), (int)((R.envp >> (8 * p)) & 0xFFu));
+}
+
+// Result records left in LDS by the move of the per-tile kernels (tile_step, obs_tile), read by waves 1-3 and by the
+// stream: rec_st = the new st4; rec_out = {RES_* flags | winner << 4, reward1, reward2, restart word}, where an env that
+// does not restart may leave another word with bit 31 clear in the restart word's place (the slide marks of CodeCells).
 enum { RES_STEPPED = 1u, RES_DONE = 2u, RES_STORE_ST = 4u, RES_RESET = 8u };
+__device__ __forceinline__ void move_records(int S, const EnvRegs &R, uint32_t flags, uint32_t res, bool done, int winner,
+                                             float rw0, float rw1, uint32_t marks, uint4 &rec_st, uint4 &rec_out)
+{
+    if (done) res |= RES_DONE;
+    uint32_t w = marks;
+    if (done && (flags & TRON_STEP_AUTORESET)) {                    // ACKTR.py:307-310
+        rec_st = restarted_st4(R.nstart, rec_st.w);
+        res |= RES_STORE_ST | RES_RESET;
+        w = restart_word(S, R.nstart);
+    }
+    rec_out = make_uint4(res | ((uint32_t)winner << 4), __float_as_uint(rw0), __float_as_uint(rw1), w);
+}
+
+// The two cell encodings a move works in, and what a written cell reports (wrote: cell, player, "is a slide tile";
+// the words of a move's six cells are ORed into rec_out's last word).
+struct BoardCells {                             // the board-owning layout: Tile values (map.py:9-17)
+    enum { EMPTY = TRON_EMPTY, WALL = TRON_WALL, P1_BODY = TRON_P1_BODY, P2_BODY = TRON_P2_BODY, P1_HEAD = TRON_P1_HEAD,
+           P2_HEAD = TRON_P2_HEAD, P1_SLIDE = TRON_P1_SLIDE, P2_SLIDE = TRON_P2_SLIDE };
+    uint32_t *dirty;                            // LDS bitmask of the tile's chunks that the stream writes back to the grid
+    uint32_t chunk0;                            // this env's first chunk
+    __device__ __forceinline__ uint32_t wrote(int cell, int, bool) const
+    {
+        const uint32_t ci = chunk0 + (uint32_t)(cell >> 4);
+        atomicOr(&dirty[ci >> 5], 1u << (ci & 31u));
+        return 0u;
+    }
+};
+struct CodeCells {                              // observation-is-state: player-1 codes (map.py:67-81), see k_obs below
+    // a slide tile shows as its player's body: the board image tells them apart by the slide log (see slide_log below)
+    enum { EMPTY = 1, WALL = -1, P1_BODY = -2, P2_BODY = -3, P1_HEAD = 10, P2_HEAD = -10, P1_SLIDE = P1_BODY, P2_SLIDE = P2_BODY };
+    // slide marks: (cell + 1) of player 1's slide tile | (cell + 1) << 14 of player 2's, 0 = none
+    __device__ __forceinline__ uint32_t wrote(int cell, int p, bool slide_tile) const
+    {
+        return slide_tile ? (uint32_t)(cell + 1) << (14 * p) : 0u;
+    }
+};
 
 // ------------------------------------------------------------------ the move --
-// One lane = one env, against its LDS copy g: Game.next_frame + Game.step (game.py:149-277).
-// LDS-only, one read round trip.  Leaves: rec_st (new st4), rec_out {flags | winner<<4, reward1,
-// reward2, restart word}.  (Pre-fetching the target cells from HBM before the barrier was
-// measured too: +20 VGPRs held across the tile load cost a workgroup per CU and lost.)
-__device__ inline void lane_move(const Params &P, unsigned char *g, const EnvRegs &R, const int a[2], const float u[2],
-                                 uint32_t flags, uint32_t *dirty, uint32_t chunk0, uint4 &rec_st, uint4 &rec_out)
+// One lane = one env, against its LDS copy g, in the cell encoding L; every mode (mode None never takes the slide).
+// LDS-only, one read round trip.  Leaves its records (move_records).  (Pre-fetching the target cells from HBM before the
+// barrier was measured too: +20 VGPRs held across the tile load cost a workgroup per CU and lost.)
+template <class L>
+__device__ inline void lane_move(const Params &P, const L &layout, unsigned char *g, const EnvRegs &R, const int a[2],
+                                 const float u[2], uint32_t flags, uint4 &rec_st, uint4 &rec_out)
 {
     const int S = P.S, W = P.W;
-    uint32_t m = R.meta;
-    int r[2] = {(int)(int8_t)(R.pos), (int)(int8_t)(R.pos >> 16)};
-    int c[2] = {(int)(int8_t)(R.pos >> 8), (int)(int8_t)(R.pos >> 24)};
+    const bool sliding = (P.mode != TRON_MODE_NONE);
+    const uint32_t m = R.meta;
+    int r[2], c[2];
+    unpack_pos(R.pos, r, c);
     bool done = (m & META_DONE) != 0;
     int winner = (int)((m >> 4) & 3u);
     float rw0 = 0.0f, rw1 = 0.0f;
-    uint32_t res = 0u;
+    uint32_t res = 0u, marks = 0u;
     rec_st = make_uint4(R.pos, R.meta, R.eplen, R.tick);
 
-    // "temper": both players' slide thresholds, requested before anything else so that they arrive under the cell reads
     float thr[2] = {0.0f, 0.0f};
     bool thr_ok[2] = {false, false};
     if (P.mode == TRON_MODE_TEMPER) {
-        const uint32_t di = (uint32_t)((int)(int8_t)(R.envp >> 16) + 30);
 #pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const uint32_t wi = ((R.envp >> (8 * p)) & 0xFFu) - 40u;
-            thr_ok[p] = di < (uint32_t)RATE_DEG && wi < (uint32_t)RATE_W;
-            thr[p] = g_rate_thr[thr_ok[p] ? di * RATE_W + wi : 0u];
-        }
+        for (int p = 0; p < 2; ++p) temper_threshold(R.envp, p, thr[p], thr_ok[p]);
     }
     if (!done) {
         res |= RES_STEPPED;
-        const bool sliding = (P.mode != TRON_MODE_NONE);
         // The <=4 cells the move can look at — first target n[p] and slide landing s[p] of each
         // player (player.py:124-132, game.py:163-178) — are read from the LDS copy in ONE round
         // trip; the write-then-read dependencies between the players are resolved in registers.
         int dr[2], dc[2], n[2], sl[2], tn[2], ts[2];
-        bool inb[2];
+        bool inb[2], slid[2] = {false, false};
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
-            dr[p] = (a[p] == 0) ? -1 : (a[p] == 2) ? 1 : 0;   // UP / DOWN
-            dc[p] = (a[p] == 1) ? 1 : (a[p] == 3) ? -1 : 0;   // RIGHT / LEFT
+            action_delta(a[p], dr[p], dc[p]);
             const int nr = r[p] + dr[p], nc = c[p] + dc[p];
-            inb[p] = nr >= 0 && nc >= 0 && nr < W && nc < W;
+            inb[p] = on_board(W, nr, nc);
             n[p] = cell_index(S, nr, nc);
             sl[p] = inb[p] ? cell_index(S, nr + dr[p], nc + dc[p]) : n[p];
         }
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
             tn[p] = (int)(int8_t)g[n[p]];
-            ts[p] = sliding ? (int)(int8_t)g[sl[p]] : (int)TRON_WALL;
+            ts[p] = sliding ? (int)(int8_t)g[sl[p]] : (int)L::WALL;
         }
         // cells written so far, in program order; a read sees the latest write to that cell
         int cells[6], vals[6];
-        cells[0] = cell_index(S, r[0], c[0]); vals[0] = TRON_P1_BODY;     // game.py:155-156: heads -> bodies first
-        cells[1] = cell_index(S, r[1], c[1]); vals[1] = TRON_P2_BODY;
+        cells[0] = cell_index(S, r[0], c[0]); vals[0] = L::P1_BODY;       // game.py:155-156: heads -> bodies first
+        cells[1] = cell_index(S, r[1], c[1]); vals[1] = L::P2_BODY;
 #pragma unroll
         for (int k = 2; k < 6; ++k) { cells[k] = cells[k & 1]; vals[k] = vals[k & 1]; }
-        auto tile_at = [&](int idx, int before, int upto) {
+        auto cell_at = [&](int idx, int before, int upto) {
             int v = before;
 #pragma unroll
             for (int k = 0; k < 6; ++k)
@@ -249,23 +312,14 @@ __device__ inline void lane_move(const Params &P, unsigned char *g, const EnvReg
             tf[p] = tn[p];
             int nr = r[p] + dr[p], nc = c[p] + dc[p];
             // the uniform is consulted only for an in-bounds EMPTY target (game.py:164-165)
-            if (sliding && inb[p] && tile_at(n[p], tn[p], 2 + p) == TRON_EMPTY) {
-                bool slides;                                             // game.py:169: random.random() <= rate
-                if (P.mode == TRON_MODE_ICE) {
-                    slides = (double)u[p] <= R.slide;
-                } else if (thr_ok[p]) {
-                    slides = u[p] <= thr[p];
-                } else {
-                    slides = (double)u[p] <= get_rate((int)(int8_t)(R.envp >> 16), (int)((R.envp >> (8 * p)) & 0xFFu));
-                }
-                if (slides) {
-                    cells[2 + p] = n[p];
-                    vals[2 + p] = (p == 0) ? TRON_P1_SLIDE : TRON_P2_SLIDE;
-                    f[p] = sl[p];
-                    tf[p] = ts[p];
-                    nr += dr[p];
-                    nc += dc[p];
-                }
+            if (sliding && inb[p] && cell_at(n[p], tn[p], 2 + p) == L::EMPTY && slides(P, R, p, u[p], thr[p], thr_ok[p])) {
+                cells[2 + p] = n[p];
+                vals[2 + p] = (p == 0) ? L::P1_SLIDE : L::P2_SLIDE;
+                slid[p] = true;
+                f[p] = sl[p];
+                tf[p] = ts[p];
+                nr += dr[p];
+                nc += dc[p];
             }
             r[p] = nr;
             c[p] = nc;
@@ -276,60 +330,28 @@ __device__ inline void lane_move(const Params &P, unsigned char *g, const EnvReg
         uint32_t alive = m & 3u;
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
-            const bool oob = r[p] < 0 || c[p] < 0 || r[p] >= W || c[p] >= W;
-            if (oob || tile_at(f[p], tf[p], 4 + p) != TRON_EMPTY)
-                alive &= ~(1u << p);
+            alive = collide(alive, p, W, r[p], c[p], cell_at(f[p], tf[p], 4 + p) == L::EMPTY);
             cells[4 + p] = f[p];
-            vals[4 + p] = (p == 0) ? TRON_P1_HEAD : TRON_P2_HEAD;
+            vals[4 + p] = (p == 0) ? L::P1_HEAD : L::P2_HEAD;
         }
         // the writes, in program order (same-lane LDS writes keep their order); fire and forget
 #pragma unroll
         for (int k = 0; k < 6; ++k) g[cells[k]] = (unsigned char)vals[k];
 
-        // game.py:264-275 — done / winner (same cell => draw)
-        const int n_alive = (int)(alive & 1u) + (int)((alive >> 1) & 1u);
-        if (n_alive <= 1) {
-            if (n_alive == 1 && (r[0] != r[1] || c[0] != c[1]))
-                winner = (alive & 1u) ? 1 : 2;
-            done = true;
-        }
+        done = settle(alive, r, c, winner);
+        step_rewards(P, done, winner, R.eplen, rw0, rw1);
 
-        // rewards: util.py:87-94 / DDQN.py:289-305 / DQN.py:224-241
-        if (!done) {
-            rw0 = rw1 = P.r_index ? (float)R.eplen : P.r_step;
-        } else if (winner == 0) {
-            rw0 = rw1 = P.r_draw;
-        } else {
-            rw0 = (winner == 1) ? P.r_win : P.r_lose;
-            rw1 = (winner == 2) ? P.r_win : P.r_lose;
-        }
-
-        if (!(done && (flags & TRON_STEP_AUTORESET))) {
-            // the stream writes these chunks back to the grid
+        if (!(done && (flags & TRON_STEP_AUTORESET))) {               // (a restarting env's board is rebuilt whole)
 #pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                const uint32_t ci = chunk0 + (uint32_t)(cells[k] >> 4);
-                atomicOr(&dirty[ci >> 5], 1u << (ci & 31u));
-            }
+            for (int k = 0; k < 6; ++k) marks |= layout.wrote(cells[k], k & 1, (k >> 1) == 1 && slid[k & 1]);
         }
-        rec_st = make_uint4(pack_pos(r[0], c[0], r[1], c[1]),
-                            alive | (done ? META_DONE : 0u) | ((uint32_t)winner << 4) | ((uint32_t)(a[0] + 1) << 8) |
-                                ((uint32_t)(a[1] + 1) << 12),
-                            R.eplen + 1u, R.tick + 1u);
+        // a layout whose slide tiles have no value of their own keeps their number in st4.meta (the slide log)
+        const uint32_t cnt = ((int)L::P1_SLIDE != (int)L::P1_BODY) ? 0u
+                           : ((m >> SLIDE_CNT_SHIFT) & SLIDE_CNT_MASK) + ((marks & 0x3FFFu) ? 1u : 0u) + ((marks >> 14) ? 1u : 0u);
+        rec_st = stepped_st4(r, c, pack_meta(alive, done, winner, a[0], a[1], cnt), R.eplen, R.tick);
         res |= RES_STORE_ST;
     }
-    if (done) res |= RES_DONE;
-
-    uint32_t restart = 0u;
-    if (done && (flags & TRON_STEP_AUTORESET)) {                    // ACKTR.py:307-310
-        // the game being started was drawn at the previous restart (rs4.nstart / .nenvp)
-        rec_st = make_uint4(R.nstart, META_ALIVE0 | META_ALIVE1, 0u, rec_st.w);
-        res |= RES_STORE_ST | RES_RESET;
-        const int h1 = cell_index(S, (int)(int8_t)(R.nstart), (int)(int8_t)(R.nstart >> 8));
-        const int h2 = cell_index(S, (int)(int8_t)(R.nstart >> 16), (int)(int8_t)(R.nstart >> 24));
-        restart = 0x80000000u | (uint32_t)h1 | ((uint32_t)h2 << 14);
-    }
-    rec_out = make_uint4(res | ((uint32_t)winner << 4), __float_as_uint(rw0), __float_as_uint(rw1), restart);
+    move_records(S, R, flags, res, done, winner, rw0, rw1, marks, rec_st, rec_out);
 }
 
 // ---------------------------------------------------------------- the kernel --
@@ -439,8 +461,8 @@ __device__ __forceinline__ void tile_step(const Params &P, int E, uint32_t cpe, 
         if (w0) {
             uint4 rs = make_uint4(0u, 0u, 0u, 0u), ro = make_uint4(0u, 0u, 0u, 0u);
             if (mine)
-                lane_move(P, reinterpret_cast<unsigned char *>(tile + (size_t)tid * cpe), R, a, u, flags, dirty,
-                          (uint32_t)tid * cpe, rs, ro);
+                lane_move(P, BoardCells{dirty, (uint32_t)tid * cpe}, reinterpret_cast<unsigned char *>(tile + (size_t)tid * cpe), R, a, u,
+                          flags, rs, ro);
             if (tid < E) {
                 rec_st[tid] = rs;
                 rec_out[tid] = ro;
@@ -493,9 +515,9 @@ __device__ __forceinline__ void tile_step(const Params &P, int E, uint32_t cpe, 
         bool wb = false;
         if (DO_STEP) {
             const uint32_t ri = rec_out[le].w;
-            if (ri >> 31) {                                                // restarted env: fresh board + heads
+            if (is_restart(ri)) {                                          // restarted env: fresh board + heads
                 t = tmpl[k];
-                const uint32_t d1 = (ri & 0x3FFFu) - c, d2 = ((ri >> 14) & 0x3FFFu) - c;
+                const uint32_t d1 = restart_head(ri, 0) - c, d2 = restart_head(ri, 1) - c;
                 const uint32_t v1 = (uint32_t)TRON_P1_HEAD << ((d1 & 3u) * 8u);   // EMPTY is 0: OR the head in
                 const uint32_t v2 = (uint32_t)TRON_P2_HEAD << ((d2 & 3u) * 8u);   // game.py:90-91
                 t.x |= (d1 < 4u ? v1 : 0u) | (d2 < 4u ? v2 : 0u);
@@ -563,7 +585,9 @@ __device__ __forceinline__ void load_params(Params &p, kernarg_t *q)       // Pa
     __builtin_memcpy(&p, q, sizeof(Params));
 }
 
-// persistent rollout on the board-owning layout (every mode / format / side): see k_obs_roll
+// Persistent rollout on the board-owning layout: the COMPATIBILITY PATH of tron_rollout_random — every mode, format and
+// side the observation-is-state kernels (k_obs_roll, k_obs_roll_walk, k_obs_roll_slide) do not take; correct, not tuned.
+// tile_step in k_obs_roll's loop of steps and tiles.
 template <int FMT, bool ALIGNED>
 __global__ __launch_bounds__(BLOCK) void k_tile_roll(Params P, int E, uint32_t cpe, uint32_t cpe_magic, uint32_t flags,
                                                      void *__restrict__ obs, StepOut out, int k_steps, int ntiles)
@@ -596,86 +620,52 @@ __global__ __launch_bounds__(BLOCK) void k_tile_roll(Params P, int E, uint32_t c
 // code space (EMPTY is 1; bodies -2 / -3; heads 10 / -10), the player-2 plane is the
 // swap_codes4 LUT of the player-1 plane, and wave 1 draws the speculative next start so it runs
 // beside wave 0's action Philox instead of after it.
+// The move of mode None in code space (CodeCells): no slide, so two target cells in one LDS round trip and four writes —
+// the shape k_obs is tuned around; the sliding modes on this layout go through lane_move<CodeCells>.
 __device__ inline void lane_move_codes(const Params &P, unsigned char *g, const EnvRegs &R, const int a[2],
                                        uint32_t flags, uint4 &rec_st, uint4 &rec_out)
 {
+    typedef CodeCells C;
     const int S = P.S, W = P.W;
-    uint32_t m = R.meta;
-    int r[2] = {(int)(int8_t)(R.pos), (int)(int8_t)(R.pos >> 16)};
-    int c[2] = {(int)(int8_t)(R.pos >> 8), (int)(int8_t)(R.pos >> 24)};
-    bool done = (m & META_DONE) != 0;
-    int winner = (int)((m >> 4) & 3u);
+    int r[2], c[2];
+    unpack_pos(R.pos, r, c);
+    bool done = (R.meta & META_DONE) != 0;
+    int winner = (int)((R.meta >> 4) & 3u);
     float rw0 = 0.0f, rw1 = 0.0f;
     uint32_t res = 0u;
     rec_st = make_uint4(R.pos, R.meta, R.eplen, R.tick);
 
     if (!done) {
         res |= RES_STEPPED;
-        constexpr int C_EMPTY = 1, C_P1_BODY = -2, C_P2_BODY = -3, C_P1_HEAD = 10, C_P2_HEAD = -10;
         int old[2], f[2], tf[2];
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
+            int dr, dc;
+            action_delta(a[p], dr, dc);
             old[p] = cell_index(S, r[p], c[p]);
-            r[p] += (a[p] == 0) ? -1 : (a[p] == 2) ? 1 : 0;          // UP / DOWN   (player.py:124-132)
-            c[p] += (a[p] == 1) ? 1 : (a[p] == 3) ? -1 : 0;          // RIGHT / LEFT
+            r[p] += dr;
+            c[p] += dc;
             f[p] = cell_index(S, r[p], c[p]);
         }
         tf[0] = (int)(int8_t)g[f[0]];                                  // one LDS round trip for both targets
         tf[1] = (int)(int8_t)g[f[1]];
-        // game.py:155-156 — heads turn into bodies BEFORE anyone moves: a target that is either
-        // old head is a body by now
+        plain_targets(old, f, tf, (int)C::P1_BODY, (int)C::P2_BODY, (int)C::P1_HEAD);
+        uint32_t alive = R.meta & 3u;
 #pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            if (f[p] == old[0]) tf[p] = C_P1_BODY;
-            if (f[p] == old[1]) tf[p] = C_P2_BODY;
-        }
-        if (f[1] == f[0]) tf[1] = C_P1_HEAD;                           // game.py:205-214: P2 tests after P1's head is down
-        uint32_t alive = m & 3u;
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const bool oob = r[p] < 0 || c[p] < 0 || r[p] >= W || c[p] >= W;
-            if (oob || tf[p] != C_EMPTY) alive &= ~(1u << p);
-        }
+        for (int p = 0; p < 2; ++p) alive = collide(alive, p, W, r[p], c[p], tf[p] == C::EMPTY);
         // writes in the reference's order: bodies, then P1's head, then P2's (an out-of-bounds
         // head lands on the border WALL cell; a same-cell head-on leaves P2's head)
-        g[old[0]] = (unsigned char)C_P1_BODY;
-        g[old[1]] = (unsigned char)C_P2_BODY;
-        g[f[0]] = (unsigned char)C_P1_HEAD;
-        g[f[1]] = (unsigned char)C_P2_HEAD;
+        g[old[0]] = (unsigned char)C::P1_BODY;
+        g[old[1]] = (unsigned char)C::P2_BODY;
+        g[f[0]] = (unsigned char)C::P1_HEAD;
+        g[f[1]] = (unsigned char)C::P2_HEAD;
 
-        // game.py:264-275 — done / winner (same cell => draw)
-        const int n_alive = (int)(alive & 1u) + (int)((alive >> 1) & 1u);
-        if (n_alive <= 1) {
-            if (n_alive == 1 && (r[0] != r[1] || c[0] != c[1]))
-                winner = (alive & 1u) ? 1 : 2;
-            done = true;
-        }
-        // rewards: util.py:87-94 / DDQN.py:289-305 / DQN.py:224-241
-        if (!done) {
-            rw0 = rw1 = P.r_index ? (float)R.eplen : P.r_step;
-        } else if (winner == 0) {
-            rw0 = rw1 = P.r_draw;
-        } else {
-            rw0 = (winner == 1) ? P.r_win : P.r_lose;
-            rw1 = (winner == 2) ? P.r_win : P.r_lose;
-        }
-        rec_st = make_uint4(pack_pos(r[0], c[0], r[1], c[1]),
-                            alive | (done ? META_DONE : 0u) | ((uint32_t)winner << 4) | ((uint32_t)(a[0] + 1) << 8) |
-                                ((uint32_t)(a[1] + 1) << 12),
-                            R.eplen + 1u, R.tick + 1u);
+        done = settle(alive, r, c, winner);
+        step_rewards(P, done, winner, R.eplen, rw0, rw1);
+        rec_st = stepped_st4(r, c, pack_meta(alive, done, winner, a[0], a[1]), R.eplen, R.tick);
         res |= RES_STORE_ST;
     }
-    if (done) res |= RES_DONE;
-
-    uint32_t restart = 0u;
-    if (done && (flags & TRON_STEP_AUTORESET)) {                      // ACKTR.py:307-310
-        rec_st = make_uint4(R.nstart, META_ALIVE0 | META_ALIVE1, 0u, rec_st.w);
-        res |= RES_STORE_ST | RES_RESET;
-        const int h1 = cell_index(S, (int)(int8_t)(R.nstart), (int)(int8_t)(R.nstart >> 8));
-        const int h2 = cell_index(S, (int)(int8_t)(R.nstart >> 16), (int)(int8_t)(R.nstart >> 24));
-        restart = 0x80000000u | (uint32_t)h1 | ((uint32_t)h2 << 14);
-    }
-    rec_out = make_uint4(res | ((uint32_t)winner << 4), __float_as_uint(rw0), __float_as_uint(rw1), restart);
+    move_records(S, R, flags, res, done, winner, rw0, rw1, 0u, rec_st, rec_out);
 }
 
 // ---- the sliding modes ("ice", "temper") on the observation-is-state layout ---------------------------------------------
@@ -686,143 +676,11 @@ __device__ inline void lane_move_codes(const Params &P, unsigned char *g, const 
 // number in st4.meta bits 16-29 (a restart rewrites meta: the log empties by itself) — which tron_get_grid replays:
 // a logged cell that still holds its player's body code is a slide tile.  The board-owning layout wrote every
 // dirty 16-byte chunk of the board back as a partial line instead: 153 MB per step against 121 (profiles/r04_temper_pmc.txt).
-constexpr uint32_t SLIDE_CNT_SHIFT = 16u, SLIDE_CNT_MASK = 0x3FFFu;      // (a mark takes a cell and so does the head behind it: <= W W / 2 marks; 14 bits cover every side the 15-bit cell index allows)
 __device__ __forceinline__ uint16_t *slide_log(const Params &P)
 {
     return reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(P.slide) + (((size_t)P.N * 8u + 255u) & ~(size_t)255u));
 }
 __host__ __device__ __forceinline__ int slide_log_len(int W) { return W * W; }   // a mark takes a cell of its own
-
-// lane_move (the board-owning layout's move, above) in code space; marks out: (cell + 1) of player 1's slide mark | (cell + 1)
-// << 14 of player 2's, 0 = none (rec_out.w when the env does not restart: a restarting env's marks die with its board)
-__device__ inline void lane_move_codes_slide(const Params &P, unsigned char *g, const EnvRegs &R, const int a[2], const float u[2],
-                                             uint32_t flags, uint4 &rec_st, uint4 &rec_out)
-{
-    constexpr int C_EMPTY = 1, C_WALL = -1, C_P1_BODY = -2, C_P2_BODY = -3, C_P1_HEAD = 10, C_P2_HEAD = -10;
-    const int S = P.S, W = P.W;
-    uint32_t m = R.meta;
-    int r[2] = {(int)(int8_t)(R.pos), (int)(int8_t)(R.pos >> 16)};
-    int c[2] = {(int)(int8_t)(R.pos >> 8), (int)(int8_t)(R.pos >> 24)};
-    bool done = (m & META_DONE) != 0;
-    int winner = (int)((m >> 4) & 3u);
-    float rw0 = 0.0f, rw1 = 0.0f;
-    uint32_t res = 0u, marks = 0u;
-    rec_st = make_uint4(R.pos, R.meta, R.eplen, R.tick);
-
-    float thr[2] = {0.0f, 0.0f};
-    bool thr_ok[2] = {false, false};
-    if (P.mode == TRON_MODE_TEMPER) {
-        const uint32_t di = (uint32_t)((int)(int8_t)(R.envp >> 16) + 30);
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const uint32_t wi = ((R.envp >> (8 * p)) & 0xFFu) - 40u;
-            thr_ok[p] = di < (uint32_t)RATE_DEG && wi < (uint32_t)RATE_W;
-            thr[p] = g_rate_thr[thr_ok[p] ? di * RATE_W + wi : 0u];
-        }
-    }
-    if (!done) {
-        res |= RES_STEPPED;
-        int dr[2], dc[2], n[2], sl[2], tn[2], ts[2];
-        bool inb[2];
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            dr[p] = (a[p] == 0) ? -1 : (a[p] == 2) ? 1 : 0;   // UP / DOWN
-            dc[p] = (a[p] == 1) ? 1 : (a[p] == 3) ? -1 : 0;   // RIGHT / LEFT
-            const int nr = r[p] + dr[p], nc = c[p] + dc[p];
-            inb[p] = nr >= 0 && nc >= 0 && nr < W && nc < W;
-            n[p] = cell_index(S, nr, nc);
-            sl[p] = inb[p] ? cell_index(S, nr + dr[p], nc + dc[p]) : n[p];
-        }
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            tn[p] = (int)(int8_t)g[n[p]];
-            ts[p] = (int)(int8_t)g[sl[p]];
-        }
-        int cells[6], vals[6];
-        cells[0] = cell_index(S, r[0], c[0]); vals[0] = C_P1_BODY;       // game.py:155-156: heads -> bodies first
-        cells[1] = cell_index(S, r[1], c[1]); vals[1] = C_P2_BODY;
-#pragma unroll
-        for (int k = 2; k < 6; ++k) { cells[k] = cells[k & 1]; vals[k] = vals[k & 1]; }
-        auto code_at = [&](int idx, int before, int upto) {
-            int v = before;
-#pragma unroll
-            for (int k = 0; k < 6; ++k)
-                if (k < upto && cells[k] == idx) v = vals[k];
-            return v;
-        };
-        int f[2], tf[2];
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            f[p] = n[p];
-            tf[p] = tn[p];
-            int nr = r[p] + dr[p], nc = c[p] + dc[p];
-            if (inb[p] && code_at(n[p], tn[p], 2 + p) == C_EMPTY) {       // the uniform is consulted only for an in-bounds EMPTY target (game.py:164-165)
-                bool slides;                                             // game.py:169: random.random() <= rate
-                if (P.mode == TRON_MODE_ICE) {
-                    slides = (double)u[p] <= R.slide;
-                } else if (thr_ok[p]) {
-                    slides = u[p] <= thr[p];
-                } else {
-                    slides = (double)u[p] <= get_rate((int)(int8_t)(R.envp >> 16), (int)((R.envp >> (8 * p)) & 0xFFu));
-                }
-                if (slides) {
-                    cells[2 + p] = n[p];
-                    vals[2 + p] = (p == 0) ? C_P1_BODY : C_P2_BODY;      // the slide tile, as Map.color shows it
-                    marks |= (uint32_t)(n[p] + 1) << (14 * p);
-                    f[p] = sl[p];
-                    tf[p] = ts[p];
-                    nr += dr[p];
-                    nc += dc[p];
-                }
-            }
-            r[p] = nr;
-            c[p] = nc;
-        }
-        uint32_t alive = m & 3u;
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const bool oob = r[p] < 0 || c[p] < 0 || r[p] >= W || c[p] >= W;
-            if (oob || code_at(f[p], tf[p], 4 + p) != C_EMPTY)
-                alive &= ~(1u << p);
-            cells[4 + p] = f[p];
-            vals[4 + p] = (p == 0) ? C_P1_HEAD : C_P2_HEAD;
-        }
-#pragma unroll
-        for (int k = 0; k < 6; ++k) g[cells[k]] = (unsigned char)vals[k];
-
-        const int n_alive = (int)(alive & 1u) + (int)((alive >> 1) & 1u);
-        if (n_alive <= 1) {
-            if (n_alive == 1 && (r[0] != r[1] || c[0] != c[1]))
-                winner = (alive & 1u) ? 1 : 2;
-            done = true;
-        }
-        if (!done) {
-            rw0 = rw1 = P.r_index ? (float)R.eplen : P.r_step;
-        } else if (winner == 0) {
-            rw0 = rw1 = P.r_draw;
-        } else {
-            rw0 = (winner == 1) ? P.r_win : P.r_lose;
-            rw1 = (winner == 2) ? P.r_win : P.r_lose;
-        }
-        const uint32_t cnt = ((m >> SLIDE_CNT_SHIFT) & SLIDE_CNT_MASK) + ((marks & 0x3FFFu) ? 1u : 0u) + ((marks >> 14) ? 1u : 0u);
-        rec_st = make_uint4(pack_pos(r[0], c[0], r[1], c[1]),
-                            alive | (done ? META_DONE : 0u) | ((uint32_t)winner << 4) | ((uint32_t)(a[0] + 1) << 8) |
-                                ((uint32_t)(a[1] + 1) << 12) | (cnt << SLIDE_CNT_SHIFT),
-                            R.eplen + 1u, R.tick + 1u);
-        res |= RES_STORE_ST;
-    }
-    if (done) res |= RES_DONE;
-
-    uint32_t restart = 0u;
-    if (done && (flags & TRON_STEP_AUTORESET)) {                      // ACKTR.py:307-310
-        rec_st = make_uint4(R.nstart, META_ALIVE0 | META_ALIVE1, 0u, rec_st.w);
-        res |= RES_STORE_ST | RES_RESET;
-        const int h1 = cell_index(S, (int)(int8_t)(R.nstart), (int)(int8_t)(R.nstart >> 8));
-        const int h2 = cell_index(S, (int)(int8_t)(R.nstart >> 16), (int)(int8_t)(R.nstart >> 24));
-        restart = 0x80000000u | (uint32_t)h1 | ((uint32_t)h2 << 14);
-    }
-    rec_out = make_uint4(res | ((uint32_t)winner << 4), __float_as_uint(rw0), __float_as_uint(rw1), restart ? restart : marks);
-}
 
 // One tile of E envs through one step; `smem` is the workgroup's dynamic LDS.  Shared by k_obs (one
 // tile per workgroup per launch) and k_obs_roll_walk / k_obs_roll_slide (workgroups that keep stepping their own tiles).
@@ -929,8 +787,9 @@ __device__ __forceinline__ void obs_tile(const Params &P, int E, uint32_t cpe, u
             uint4 rst = make_uint4(0u, 0u, 0u, 0u), ro = make_uint4(0u, 0u, 0u, 0u);
             if (mine) {
                 if (autoreset) R.nstart = rs_in[lane].z;
-                if (SLIDING) lane_move_codes_slide(P, reinterpret_cast<unsigned char *>(tile + (size_t)lane * cpe), R, a, u, flags, rst, ro);
-                else lane_move_codes(P, reinterpret_cast<unsigned char *>(tile + (size_t)lane * cpe), R, a, flags, rst, ro);
+                unsigned char *g = reinterpret_cast<unsigned char *>(tile + (size_t)lane * cpe);
+                if (SLIDING) lane_move(P, CodeCells{}, g, R, a, u, flags, rst, ro);
+                else lane_move_codes(P, g, R, a, flags, rst, ro);
             }
             if (lane < E) {
                 rec_st[lane] = rst;
@@ -953,7 +812,7 @@ __device__ __forceinline__ void obs_tile(const Params &P, int E, uint32_t cpe, u
             } else {
                 if (out.reward)
                     reinterpret_cast<float2 *>(out.reward)[env] = make_float2(__uint_as_float(ro.y), __uint_as_float(ro.z));
-                if (SLIDING && ro.w && !(ro.w >> 31)) {               // this step's slide marks go to the env's log (see lane_move_codes_slide)
+                if (SLIDING && ro.w && !is_restart(ro.w)) {           // this step's slide marks (CodeCells) go to the env's log
                     const uint32_t m0 = ro.w & 0x3FFFu, m1 = ro.w >> 14;
                     uint32_t at = ((rec_st[lane].y >> SLIDE_CNT_SHIFT) & SLIDE_CNT_MASK) - (m0 ? 1u : 0u) - (m1 ? 1u : 0u);
                     uint16_t *lg = slide_log(P) + (size_t)env * slide_log_len(P.W);
@@ -988,9 +847,9 @@ __device__ __forceinline__ void obs_tile(const Params &P, int E, uint32_t cpe, u
         const int nb = min(16, G - (int)c);
         uint4 t = tile[i];
         const uint32_t ri = rec_out[le].w;
-        if (ri >> 31) {                                                // restarted env: fresh board + heads
+        if (is_restart(ri)) {                                          // restarted env: fresh board + heads
             t = tmpl[k];
-            const uint32_t d1 = (ri & 0x3FFFu) - c, d2 = ((ri >> 14) & 0x3FFFu) - c;
+            const uint32_t d1 = restart_head(ri, 0) - c, d2 = restart_head(ri, 1) - c;
             // the head cells are EMPTY (code 1) in the template: XOR turns 1 into 10 / -10 (game.py:90-91)
             const uint32_t v1 = (uint32_t)(0x01 ^ 0x0A) << ((d1 & 3u) * 8u), v2 = (uint32_t)(0x01 ^ 0xF6) << ((d2 & 3u) * 8u);
             t.x ^= (d1 < 4u ? v1 : 0u) ^ (d2 < 4u ? v2 : 0u);
@@ -1195,7 +1054,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         const int S = P.S, W = P.W, G = P.G;
         STAMP(0);
 
-        // ---- the move: Game.next_frame + Game.step in code space (lane_move_codes) on the packed board
+        // ---- the move: lane_move_codes on the packed board (nibble reads, byte-sharing writes, the store mask)
         bool stepped = false, restart = false;
         bool done = (st.y & META_DONE) != 0u;
         int winner = (int)((st.y >> 4) & 3u);
@@ -1205,14 +1064,16 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         if (mine && !done) {
             stepped = true;
             const int a[2] = {draw_action(x0, (st.y >> 8) & 0xFu, nonrev), draw_action(x1, (st.y >> 12) & 0xFu, nonrev)};
-            int r[2] = {(int)(int8_t)(st.x), (int)(int8_t)(st.x >> 16)};
-            int c[2] = {(int)(int8_t)(st.x >> 8), (int)(int8_t)(st.x >> 24)};
+            int r[2], c[2];
+            unpack_pos(st.x, r, c);
             int cells[4];                                            // the old heads, the new ones
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
+                int dr, dc;
+                action_delta(a[p], dr, dc);
                 cells[p] = cell_index(S, r[p], c[p]);
-                r[p] += (a[p] == 0) ? -1 : (a[p] == 2) ? 1 : 0;          // UP / DOWN   (player.py:124-132)
-                c[p] += (a[p] == 1) ? 1 : (a[p] == 3) ? -1 : 0;          // RIGHT / LEFT
+                r[p] += dr;
+                c[p] += dc;
                 cells[2 + p] = cell_index(S, r[p], c[p]);
             }
             uint32_t b[4];                                           // one LDS round trip: the bytes of the four cells
@@ -1220,39 +1081,14 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
             for (int k = 0; k < 4; ++k) b[k] = cellb[cells[k] >> 1];
             uint32_t tf[2];
 #pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                tf[p] = (b[2 + p] >> ((cells[2 + p] & 1) * 4)) & 15u;
-                // game.py:155-156 — heads turn into bodies BEFORE anyone moves
-                if (cells[2 + p] == cells[0]) tf[p] = NIB_P1_BODY;
-                if (cells[2 + p] == cells[1]) tf[p] = NIB_P2_BODY;
-            }
-            if (cells[3] == cells[2]) tf[1] = NIB_P1_HEAD;           // game.py:205-214: P2 tests after P1's head is down
+            for (int p = 0; p < 2; ++p) tf[p] = (b[2 + p] >> ((cells[2 + p] & 1) * 4)) & 15u;
+            plain_targets(cells, cells + 2, tf, NIB_P1_BODY, NIB_P2_BODY, NIB_P1_HEAD);
             uint32_t alive = st.y & 3u;
 #pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const bool oob = r[p] < 0 || c[p] < 0 || r[p] >= W || c[p] >= W;
-                if (oob || tf[p] != NIB_EMPTY) alive &= ~(1u << p);
-            }
-            // game.py:264-275 — done / winner (same cell => draw)
-            const int n_alive = (int)(alive & 1u) + (int)((alive >> 1) & 1u);
-            if (n_alive <= 1) {
-                if (n_alive == 1 && (r[0] != r[1] || c[0] != c[1])) winner = (alive & 1u) ? 1 : 2;
-                done = true;
-            }
-            if (out.reward) {                                        // rewards: util.py:87-94 / DDQN.py:289-305 / DQN.py:224-241
-                if (!done) {
-                    rw0 = rw1 = P.r_index ? (float)st.z : P.r_step;
-                } else if (winner == 0) {
-                    rw0 = rw1 = P.r_draw;
-                } else {
-                    rw0 = (winner == 1) ? P.r_win : P.r_lose;
-                    rw1 = (winner == 2) ? P.r_win : P.r_lose;
-                }
-            }
-            st = make_uint4(pack_pos(r[0], c[0], r[1], c[1]),
-                            alive | (done ? META_DONE : 0u) | ((uint32_t)winner << 4) | ((uint32_t)(a[0] + 1) << 8) |
-                                ((uint32_t)(a[1] + 1) << 12),
-                            st.z + 1u, st.w + 1u);
+            for (int p = 0; p < 2; ++p) alive = collide(alive, p, W, r[p], c[p], tf[p] == NIB_EMPTY);
+            done = settle(alive, r, c, winner);
+            if (out.reward) step_rewards(P, done, winner, st.z, rw0, rw1);
+            st = stepped_st4(r, c, pack_meta(alive, done, winner, a[0], a[1]), st.z, st.w);
             st_dirty = true;
             if (!(done && autoreset)) {
                 // the writes in the reference's order: bodies, then P1's head, then P2's (an out-of-bounds head lands on
@@ -1277,10 +1113,9 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         }
         if (mine && done && autoreset) {                             // ACKTR.py:307-310
             restart = true;
-            st = make_uint4(rs.z, META_ALIVE0 | META_ALIVE1, 0u, st.w);
+            st = restarted_st4(rs.z, st.w);
             st_dirty = true;
-            h1 = (uint32_t)cell_index(S, (int)(int8_t)(rs.z), (int)(int8_t)(rs.z >> 8));
-            h2 = (uint32_t)cell_index(S, (int)(int8_t)(rs.z >> 16), (int)(int8_t)(rs.z >> 24));
+            start_cells(S, rs.z, h1, h2);
             const unsigned long long heads = (1ull << (h1 >> 4)) | (1ull << (h2 >> 4));
             sm = mask | heads;
             mask = heads;
@@ -1495,7 +1330,7 @@ __global__ __launch_bounds__(BLOCK) void k_inc(Params P, uint32_t cpe, const int
     __shared__ uint4 tmpl[640];                                   // fresh board as codes (same for both players)
     __shared__ uint4 rec_rs[WAVE];                                // new rs4 of an env, should it restart
     __shared__ uint32_t rec_nstart[WAVE];                         // its cached start positions (rs4.z)
-    __shared__ uint32_t rec_heads[WAVE];                          // restart word: 0x80000000 | head1 | head2 << 14
+    __shared__ uint32_t rec_heads[WAVE];                          // restart word (restart_word)
     const int G = P.G, S = P.S, W = P.W;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int env = blockIdx.x * WAVE + lane;
@@ -1525,9 +1360,10 @@ __global__ __launch_bounds__(BLOCK) void k_inc(Params P, uint32_t cpe, const int
     uint4 new_st = st;
     if (wave == 0) {
         int8_t *o1 = P.obs_state + (size_t)(mine ? env : 0) * 2u * G, *o2 = o1 + G;
+        typedef CodeCells C;
         uint32_t m = st.y;
-        int r[2] = {(int)(int8_t)(st.x), (int)(int8_t)(st.x >> 16)};
-        int c[2] = {(int)(int8_t)(st.x >> 8), (int)(int8_t)(st.x >> 24)};
+        int r[2], c[2];
+        unpack_pos(st.x, r, c);
         done = (m & META_DONE) != 0;
         stepped = mine && !done;
         winner = (int)((m >> 4) & 3u);
@@ -1543,51 +1379,33 @@ __global__ __launch_bounds__(BLOCK) void k_inc(Params P, uint32_t cpe, const int
                 a[0] = (int)(act & 3u);
                 a[1] = (int)((act >> 8) & 3u);
             }
+            // the move of lane_move_codes, its two target cells read from the player-1 plane in memory
             int old[2], f[2], tf[2];
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
+                int dr, dc;
+                action_delta(a[p], dr, dc);
                 old[p] = cell_index(S, r[p], c[p]);
-                r[p] += (a[p] == 0) ? -1 : (a[p] == 2) ? 1 : 0;          // player.py:124-132
-                c[p] += (a[p] == 1) ? 1 : (a[p] == 3) ? -1 : 0;
+                r[p] += dr;
+                c[p] += dc;
                 f[p] = cell_index(S, r[p], c[p]);
             }
             tf[0] = o1[f[0]];
             tf[1] = o1[f[1]];
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {                                // game.py:155-156: heads are bodies by now
-                if (f[p] == old[0]) tf[p] = -2;
-                if (f[p] == old[1]) tf[p] = -3;
-            }
-            if (f[1] == f[0]) tf[1] = 10;                                // game.py:205-214: P2 tests after P1's head is down
+            plain_targets(old, f, tf, (int)C::P1_BODY, (int)C::P2_BODY, (int)C::P1_HEAD);
             uint32_t alive = m & 3u;
 #pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const bool oob = r[p] < 0 || c[p] < 0 || r[p] >= W || c[p] >= W;
-                if (oob || tf[p] != 1) alive &= ~(1u << p);
-            }
-            const int n_alive = (int)(alive & 1u) + (int)((alive >> 1) & 1u);
-            if (n_alive <= 1) {                                          // game.py:264-275
-                if (n_alive == 1 && (r[0] != r[1] || c[0] != c[1])) winner = (alive & 1u) ? 1 : 2;
-                done = true;
-            }
-            if (!done) {
-                rw0 = rw1 = P.r_index ? (float)st.z : P.r_step;
-            } else if (winner == 0) {
-                rw0 = rw1 = P.r_draw;
-            } else {
-                rw0 = (winner == 1) ? P.r_win : P.r_lose;
-                rw1 = (winner == 2) ? P.r_win : P.r_lose;
-            }
-            new_st = make_uint4(pack_pos(r[0], c[0], r[1], c[1]),
-                                alive | (done ? META_DONE : 0u) | ((uint32_t)winner << 4) | ((uint32_t)(a[0] + 1) << 8) |
-                                    ((uint32_t)(a[1] + 1) << 12),
-                                st.z + 1u, st.w + 1u);
+            for (int p = 0; p < 2; ++p) alive = collide(alive, p, W, r[p], c[p], tf[p] == C::EMPTY);
+            done = settle(alive, r, c, winner);
+            step_rewards(P, done, winner, st.z, rw0, rw1);
+            new_st = stepped_st4(r, c, pack_meta(alive, done, winner, a[0], a[1]), st.z, st.w);
             if (!(done && autoreset)) {
-                // the four cells, reference order: bodies, P1's head, P2's head — in both planes
-                o1[old[0]] = -2; o2[old[0]] = -3;
-                o1[old[1]] = -3; o2[old[1]] = -2;
-                o1[f[0]] = 10;   o2[f[0]] = -10;
-                o1[f[1]] = -10;  o2[f[1]] = 10;
+                // the four cells, reference order: bodies, P1's head, P2's head — in both planes (the player-2 plane
+                // holds the other player's code)
+                o1[old[0]] = C::P1_BODY; o2[old[0]] = C::P2_BODY;
+                o1[old[1]] = C::P2_BODY; o2[old[1]] = C::P1_BODY;
+                o1[f[0]] = C::P1_HEAD;   o2[f[0]] = C::P2_HEAD;
+                o1[f[1]] = C::P2_HEAD;   o2[f[1]] = C::P1_HEAD;
                 P.st4[env] = new_st;
             }
         }
@@ -1614,10 +1432,9 @@ __global__ __launch_bounds__(BLOCK) void k_inc(Params P, uint32_t cpe, const int
         uint32_t hw = 0u;
         if (restart) {                                               // ACKTR.py:307-310; start cached one restart ago
             const uint32_t ns = rec_nstart[lane];
-            P.st4[env] = make_uint4(ns, META_ALIVE0 | META_ALIVE1, 0u, new_st.w);
+            P.st4[env] = restarted_st4(ns, new_st.w);
             P.rs4[env] = rec_rs[lane];
-            hw = 0x80000000u | (uint32_t)cell_index(S, (int)(int8_t)(ns), (int)(int8_t)(ns >> 8)) |
-                 ((uint32_t)cell_index(S, (int)(int8_t)(ns >> 16), (int)(int8_t)(ns >> 24)) << 14);
+            hw = restart_word(S, ns);
         }
         rec_heads[lane] = hw;
     }
@@ -1626,14 +1443,14 @@ __global__ __launch_bounds__(BLOCK) void k_inc(Params P, uint32_t cpe, const int
 
     // ---- restarting boards: both planes from the template, dealt round-robin to the four waves
     const uint32_t my_hw = rec_heads[lane];
-    unsigned long long rmask = __ballot((my_hw >> 31) != 0u);
+    unsigned long long rmask = __ballot(is_restart(my_hw));
     int nth = 0;
     while (rmask) {
         const int e = __ffsll((long long)rmask) - 1;
         rmask &= rmask - 1;
         if ((nth++ & 3) != wave) continue;
         const uint32_t hw = rec_heads[e];
-        const uint32_t a1 = hw & 0x3FFFu, a2 = (hw >> 14) & 0x3FFFu;
+        const uint32_t a1 = restart_head(hw, 0), a2 = restart_head(hw, 1);
         int8_t *q = P.obs_state + (size_t)(blockIdx.x * WAVE + e) * 2u * G;
         for (uint32_t j = (uint32_t)lane; j < 2u * cpe; j += WAVE) {      // chunk k of plane pl
             const uint32_t pl = j >= cpe ? 1u : 0u, k = j - pl * cpe, cc = k * 16u;
