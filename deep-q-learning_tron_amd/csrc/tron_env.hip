@@ -76,16 +76,25 @@ struct StepOut {
     unsigned long long *totals;
 };
 
-// Diagnostic build only (-DTRON_STAMPS): out.totals is then a stamp buffer [blocks][2][8] of
-// s_memrealtime ticks (100 MHz) for wave 0 and wave 1; never enabled in the shipped library.
+// Diagnostic build only (-DTRON_STAMPS): out.totals is then a stamp buffer of s_memrealtime ticks (100 MHz) for wave 0
+// and wave 1 of every workgroup; never enabled in the shipped library.  Two layouts: [blocks][2][8], one block of slots per
+// launch (STAMP: the per-tile kernels), and [blocks][2][TRON_ROLLOUT_CHUNK][4], one block per step (ROLL_STAMP:
+// roll_resident, read by scripts/roll_stamps.py).  blocks is the launch's grid: ceil(N / 64) when k_obs_roll runs one
+// wave per workgroup (roll_waves), where only wave 0's half is written.
 #ifdef TRON_STAMPS
 #define STAMP(slot)                                                                               \
     do {                                                                                          \
         if (out.totals && (tid == 0 || tid == 64))                                                \
             out.totals[((size_t)blockIdx.x * 2 + (tid >> 6)) * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); \
     } while (0)
+#define ROLL_STAMP(slot)                                                                          \
+    do {                                                                                          \
+        if (out.totals && (tid == 0 || tid == 64))                                                \
+            out.totals[(((size_t)blockIdx.x * 2 + (tid >> 6)) * TRON_ROLLOUT_CHUNK + s) * 4 + (slot)] = __builtin_amdgcn_s_memrealtime(); \
+    } while (0)
 #else
 #define STAMP(slot) do { } while (0)
+#define ROLL_STAMP(slot) do { } while (0)
 #endif
 
 struct __attribute__((packed, aligned(4))) U4A4 {   // 16 bytes at 4-byte alignment
@@ -948,10 +957,17 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 // template, whoever wrote it; a move stores and marks the chunks of its four cells; a restart stores the chunks in
 // mask | chunks of the two new heads from the template with the heads patched in, and the mask becomes the head chunks.
 // Nothing is compared in the loop, and a chunk outside the mask holds the template in memory and in LDS alike.
-// With one wave per SIMD nothing hides an instruction, so the two parts every wave runs in nearly every step are kept short:
-// a trip of the store loop is one LDS read from a per-lane source (board or template), a head patch that is zero for a
-// lane that did not restart, the player-2 nibbles (swap_nibbles8), four multiply-free expansions and two 16-byte stores, with
-// the plane's short last chunk in a branch of its own; and the next game of a restarted env is drawn by make_game, two
+// With one wave per SIMD nothing hides an instruction, so the two parts every wave runs in nearly every step are kept short.
+// The stores go through a wave-wide list: a third of the env-steps are restarts, which store a whole episode's chunks where an
+// env that goes on stores two to four, so the slowest of 64 lanes has about twice the wave's mean (scripts/roll_store_balance.py:
+// max 9 against ceil(sum / 64) = 4 at 24x24).  Each lane puts its (lane, chunk) entries, two bytes each, into the wave's list
+// in LDS at the prefix sum of the lanes' counts, and restart + the two head cells into its slot of 64 owner records; then lane
+// l of trip t takes entry 64 t + l, whoever owns it: one LDS read from the owner's board or the template, a head patch from
+// the owner's record, the write-back into the OWNER's board after a restart, the player-2 nibbles (swap_nibbles8), four
+// multiply-free expansions and two 16-byte stores.  The list is in (lane, chunk) order, so neighbouring lanes mostly store
+// neighbouring chunks of one env.  Lanes write boards they do not own here; LDS operations of one wave execute in order, and
+// wavefront-scope fences around the trips keep the compiler to that order (no barrier, no wait on memory).  The plane's
+// short last chunk has a branch of its own before the list.  The next game of a restarted env is drawn by make_game, two
 // Philox blocks and seven draws in a line, whose lanes go on into the general routine only when their two starts clash.
 // An env that restarts in the step it finishes in skips the move's four cell writes: its board is rebuilt from the mask
 // as it was before the move.  st4 / rs4 are written by the epilogue (same bytes as one store per step leaves behind).
@@ -964,6 +980,9 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
     const uint32_t sd = 2u * cpe + 1u;                              // dwords per board
     uint32_t *boards = reinterpret_cast<uint32_t *>(smem);          // [E][sd]
     uint32_t *tmpl = boards + (size_t)E * sd;                       // [2 cpe] fresh board, packed
+    // per wave: 64 owner records, then the store list of up to 64 cpe two-byte entries (the stores, below)
+    uint32_t *wrec = tmpl + 2u * cpe + (size_t)(threadIdx.x >> 6) * (64u + 32u * cpe);
+    uint16_t *wlist = reinterpret_cast<uint16_t *>(wrec + 64);
 
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
@@ -1015,7 +1034,9 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         const bool ck = (uint32_t)lane < cpe;
         const int nb = G - lane * 16;                               // valid cells of this lane's chunk (G % 4 == 0)
         const uint32_t t0 = ck ? tmpl[2 * lane] : 0u, t1 = ck ? tmpl[2 * lane + 1] : 0u;
-        constexpr int PF = 8;                                       // loads in flight (unconditional, so that they are: a lane or an env past the end reads chunk 0 / the last env again)
+        // Loads in flight (unconditional, so that they are: a lane or an env past the end reads chunk 0 / the last env again).
+        // 16 in flight (95 VGPRs) measured no faster than 8 in either form of the benchmark (profiles/r10_rollout_ab.txt).
+        constexpr int PF = 8;
         for (int e = 0; e < ne; e += PF) {
             uint4 v[PF];
 #pragma unroll
@@ -1052,7 +1073,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         Params P;                                                   // re-read per step: see k_obs_roll
         load_params_scalar(P, kp);
         const int S = P.S, W = P.W, G = P.G;
-        STAMP(0);
+        ROLL_STAMP(0);
 
         // ---- the move: lane_move_codes on the packed board (nibble reads, byte-sharing writes, the store mask)
         bool stepped = false, restart = false;
@@ -1120,39 +1141,32 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
             sm = mask | heads;
             mask = heads;
         }
-        STAMP(1);
+        ROLL_STAMP(1);
 
         // ---- the stores: both planes of the chunks in sm, from the board — or, for a restarted env, from the template
-        // with the heads in, which goes back into the board as well.  One read per trip, from a per-lane source; the head
-        // patch is zero for a lane that did not restart (its head chunks are chunk ~0), and only the board write-back is
-        // under `restart`.  The short last chunk (G % 16 cells: border wall, stored after a head died on it and by the
-        // restart that clears it) has its own branch, so the loop's stores are whole 16-byte ones.
+        // with the heads in, which goes back into the board as well.  The short last chunk (G % 16 cells: border wall,
+        // stored after a head died on it and by the restart that clears it) has its own branch, per lane; the whole
+        // chunks go through the wave's list, so their stores are whole 16-byte ones.
         {
-            const uint32_t src = restart ? (uint32_t)(tmpl - board) : 0u;       // dwords from the lane's board
-            const uint32_t hk1 = restart ? h1 >> 4 : ~0u, hk2 = restart ? h2 >> 4 : ~0u;
-            // the head cells are EMPTY in the template: XOR turns that nibble into the head's (game.py:90-91)
-            const unsigned long long v1 = (unsigned long long)(NIB_EMPTY ^ NIB_P1_HEAD) << ((h1 & 15u) * 4u);
-            const unsigned long long v2 = (unsigned long long)(NIB_EMPTY ^ NIB_P2_HEAD) << ((h2 & 15u) * 4u);
-            int8_t *const o1 = oenv, *const o2 = oenv + G;
-            auto chunk = [&](uint32_t k, uint32_t (&w1)[4], uint32_t (&w2)[4]) {
-                const unsigned long long v = (k == hk1 ? v1 : 0ull) ^ (k == hk2 ? v2 : 0ull);
-                const uint32_t p0 = board[src + 2u * k] ^ (uint32_t)v, p1 = board[src + 2u * k + 1u] ^ (uint32_t)(v >> 32);
+            const uint32_t tail = (uint32_t)G & 15u;                            // cells of the last chunk if it is short: 4, 8 or 12
+            if (tail && ((sm >> (cpe - 1u)) & 1ull)) {
+                sm &= ~(1ull << (cpe - 1u));
+                const uint32_t k = cpe - 1u, cb = k * 16u;
+                // the head cells are EMPTY in the template: XOR turns that nibble into the head's (game.py:90-91)
+                const unsigned long long v = (restart && k == (h1 >> 4) ? (unsigned long long)(NIB_EMPTY ^ NIB_P1_HEAD) << ((h1 & 15u) * 4u) : 0ull) ^
+                                             (restart && k == (h2 >> 4) ? (unsigned long long)(NIB_EMPTY ^ NIB_P2_HEAD) << ((h2 & 15u) * 4u) : 0ull);
+                const uint32_t *const sp = restart ? tmpl + 2u * k : board + 2u * k;
+                const uint32_t p0 = sp[0] ^ (uint32_t)v, p1 = sp[1] ^ (uint32_t)(v >> 32);
                 if (restart) {
                     board[2u * k] = p0;
                     board[2u * k + 1u] = p1;
                 }
+                uint32_t w1[4], w2[4];
                 expand_codes8(p0, w1[0], w1[1]);
                 expand_codes8(p1, w1[2], w1[3]);
                 expand_codes8(swap_nibbles8(p0), w2[0], w2[1]);
                 expand_codes8(swap_nibbles8(p1), w2[2], w2[3]);
-            };
-            const uint32_t tail = (uint32_t)G & 15u;                            // cells of the last chunk if it is short: 4, 8 or 12
-            if (tail && ((sm >> (cpe - 1u)) & 1ull)) {
-                sm &= ~(1ull << (cpe - 1u));
-                const uint32_t cb = (cpe - 1u) * 16u;
-                uint32_t w1[4], w2[4];
-                chunk(cpe - 1u, w1, w2);
-                uint32_t *q1 = reinterpret_cast<uint32_t *>(o1 + cb), *q2 = reinterpret_cast<uint32_t *>(o2 + cb);
+                uint32_t *q1 = reinterpret_cast<uint32_t *>(oenv + cb), *q2 = reinterpret_cast<uint32_t *>(oenv + G + cb);
                 q1[0] = w1[0];                                                   // never past G: the next plane starts there
                 q2[0] = w2[0];
                 if (tail > 4u) {
@@ -1164,16 +1178,67 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
                     q2[2] = w2[2];
                 }
             }
-            while (sm) {
-                const uint32_t k = (uint32_t)__ffsll((long long)sm) - 1u;
-                sm &= sm - 1ull;
-                uint32_t w1[4], w2[4];
-                chunk(k, w1, w2);
-                *reinterpret_cast<U4A4 *>(o1 + k * 16u) = U4A4{w1[0], w1[1], w1[2], w1[3]};
-                *reinterpret_cast<U4A4 *>(o2 + k * 16u) = U4A4{w2[0], w2[1], w2[2], w2[3]};
+            // The whole chunks go through a wave-wide list, so that the wave runs ceil(T / 64) trips of the expensive body
+            // and not its slowest lane's count.  Every lane's place in the list is the prefix sum of the lanes' counts, taken
+            // bit by bit from ballots (counts are at most 64: seven bits); the entries are (owner lane, chunk) in ascending
+            // order, so neighbouring lanes of a trip mostly hold neighbouring chunks of one env.
+            const uint32_t cnt = (uint32_t)__popcll(sm);
+            uint32_t pos = 0u, T = 0u;
+#pragma unroll
+            for (uint32_t b = 0; b < 7u; ++b) {
+                const unsigned long long m = __ballot(((cnt >> b) & 1u) != 0u);
+                pos += __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)) << b;
+                T += (uint32_t)__popcll(m) << b;
+            }
+            if (T) {
+                // what a consumer needs of the owner: restart and the two head cells (chunk 255 for an env that goes on)
+                wrec[lane] = restart ? 0x80000000u | (h1 << 12) | h2 : 0x00FFFFFFu;
+                for (uint32_t p = pos; sm; ++p) {
+                    wlist[p] = (uint16_t)(((uint32_t)lane << 6) | ((uint32_t)__ffsll((long long)sm) - 1u));
+                    sm &= sm - 1ull;
+                }
+                // Same-wave LDS operations execute in order; the fence holds the compiler to that order as well.
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                int8_t *const obase = P.obs_state + (size_t)e0 * 2u * G;       // this wave's first env
+                // An entry and its owner's record are read one trip ahead: with one wave per SIMD nothing else hides
+                // the two dependent LDS reads in front of the chunk's own.
+                uint32_t idx = (uint32_t)lane;
+                uint32_t ent = wlist[min(idx, T - 1u)];
+                uint32_t rec = wrec[ent >> 6];
+                while (idx < T) {
+                    const uint32_t own = ent >> 6, k = ent & 63u;
+                    const bool rst = (rec >> 31) != 0u;
+                    uint32_t *const ob = wboards + __umul24(own, sd) + 2u * k;    // the owner's board, written back by this lane
+                    const uint32_t *const sp = rst ? tmpl + 2u * k : ob;
+                    uint32_t p0 = sp[0], p1 = sp[1];
+                    idx += 64u;
+                    ent = wlist[min(idx, T - 1u)];
+                    const uint32_t g1 = (rec >> 12) & 0xFFFu, g2 = rec & 0xFFFu;
+                    const unsigned long long v = (k == (g1 >> 4) ? (unsigned long long)(NIB_EMPTY ^ NIB_P1_HEAD) << ((g1 & 15u) * 4u) : 0ull) ^
+                                                 (k == (g2 >> 4) ? (unsigned long long)(NIB_EMPTY ^ NIB_P2_HEAD) << ((g2 & 15u) * 4u) : 0ull);
+                    p0 ^= (uint32_t)v;
+                    p1 ^= (uint32_t)(v >> 32);
+                    if (rst) {
+                        ob[0] = p0;
+                        ob[1] = p1;
+                    }
+                    rec = wrec[ent >> 6];
+                    uint32_t w1[4], w2[4];
+                    expand_codes8(p0, w1[0], w1[1]);
+                    expand_codes8(p1, w1[2], w1[3]);
+                    expand_codes8(swap_nibbles8(p0), w2[0], w2[1]);
+                    expand_codes8(swap_nibbles8(p1), w2[2], w2[3]);
+                    int8_t *const q = obase + (__umul24(own, 2u * (uint32_t)G) + k * 16u);
+                    *reinterpret_cast<U4A4 *>(q) = U4A4{w1[0], w1[1], w1[2], w1[3]};
+                    *reinterpret_cast<U4A4 *>(q + G) = U4A4{w2[0], w2[1], w2[2], w2[3]};
+                }
+                // the next step's move reads boards that other lanes wrote, and its list overwrites this one
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
             }
         }
-        STAMP(2);
+        ROLL_STAMP(2);
 
         // ---- the records and the totals
         if (mine) {
@@ -1201,7 +1266,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
             x0 = x[0];
             x1 = x[1];
         }
-        STAMP(3);
+        ROLL_STAMP(3);
     }
 
     // ---- epilogue: the state words, and the wave's totals in one atomic per counter
@@ -2133,8 +2198,8 @@ int roll_tile_envs(const tron_env *h)
 // profiles/r07_rollout_ab.txt):  64 x 1: 6.90   64 x 2: 8.41   64 x 4: 6.66   32 x 1: 7.85   32 x 2: 7.92   32 x 4: 7.84
 // 16 x 1: 11.04   16 x 2: 11.03   16 x 4: 10.99
 // Full waves win: the step is bound by the instructions a SIMD issues, and a wave of 16 or 32 envs issues as many as one of
-// 64, so two or four narrow waves per SIMD cost what they were meant to hide.  Four waves of 64 per workgroup take 89 KB of
-// LDS at 24x24: one workgroup per CU and one wave per SIMD wherever the dispatcher puts them, where 1 024 one-wave or 512
+// 64, so two or four narrow waves per SIMD cost what they were meant to hide.  Four waves of 64 per workgroup take 110 KB of
+// LDS at 24x24 (89 KB of boards, 22 KB of store lists): one workgroup per CU and one wave per SIMD wherever the dispatcher puts them, where 1 024 one-wave or 512
 // two-wave workgroups land unevenly (64 x 2: some CUs hold three).  Repeated runs of 64 x 1 against 64 x 4 are in
 // profiles/r07_rollout_ab.txt.  A batch with no more 64-env waves than the chip has CUs gets one wave per workgroup, so that
 // it spreads over the CUs: a rule of thumb, not measured (the sweep is at 65 536 envs only).  Chosen once per handle.
@@ -2149,6 +2214,12 @@ int roll_waves(tron_env *h)
     return h->roll_waves;
 }
 
+// LDS of k_obs_roll (roll_resident): the packed boards, the template, and per wave 64 owner records + the store list
+size_t roll_smem(const tron_env *h, int E, int waves)
+{
+    return ((size_t)E * (2u * h->cpe + 1u) + 2u * h->cpe + (size_t)waves * (64u + 32u * h->cpe)) * 4u;
+}
+
 int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipStream_t st, int E, int waves, int chunk)
 {
     if (waves < 1) waves = 1;
@@ -2156,7 +2227,7 @@ int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipS
     if (waves > BLOCK / WAVE) return TRON_ERR_BAD_ARG;
     const int epw = (E + waves - 1) / waves;
     const int grid = (h->P.N + E - 1) / E;
-    const size_t smem = ((size_t)E * (2u * h->cpe + 1u) + 2u * h->cpe) * 4u;    // the packed boards + the template (roll_resident)
+    const size_t smem = roll_smem(h, E, waves);
     if (smem > 160u * 1024u) return TRON_ERR_BAD_ARG;
     static uint64_t prepared = 0;
     allow_big_lds(reinterpret_cast<const void *>(k_obs_roll), h->device, prepared);
@@ -2193,7 +2264,10 @@ int rollout_persistent(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out
     if (!sliding && h->cpe <= 64u) {
         // TRON_ROLL_E stays envs per workgroup, TRON_ROLL_WAVES its waves; a TRON_ROLL_GRID below the workgroup count asks for
         // the walking kernel below
-        const int waves = env_waves > 0 ? env_waves : roll_waves(h);
+        int waves = env_waves > 0 ? env_waves : roll_waves(h);
+        // 30x30 (64 chunks): four waves' boards and lists are past the 160 KB of a CU, three fit.  TRON_ROLL_WAVES is clamped
+        // the same way; a TRON_ROLL_E that needs more waves than fit (256 envs at 30x30) is TRON_ERR_BAD_ARG in rollout_wave.
+        while (env_e <= 0 && waves > 1 && roll_smem(h, waves * ROLL_EPW, waves) > 160u * 1024u) --waves;
         const int E = env_e > 0 ? env_e : waves * ROLL_EPW;
         if (!(env_grid > 0 && env_grid < (h->P.N + E - 1) / E)) return rollout_wave(h, k_steps, flags, out, st, E, waves, chunk);
     }
