@@ -30,9 +30,11 @@
 //   k_obs_roll, k_tile_roll tron_rollout_random: up to TRON_ROLLOUT_CHUNK steps in ONE launch.  k_obs_roll (roll_resident):
 //                           one lane per env and a wave on its own for the whole launch — no barrier in the step loop,
 //                           boards in LDS at 4 bits per cell (the whole batch resident in one round), memory read in the
-//                           prologue only, a step stores the chunks of a per-env mask (both planes from the packed
-//                           board, the player-2 one swapped in nibble space), a restart draws its next game as
-//                           straight-line code (make_game).  k_tile_roll, k_obs_roll_walk
+//                           prologue only and WRITTEN IN THE EPILOGUE ONLY: a step touches LDS and registers, and the
+//                           launch's end stores the chunks its steps touched (both planes from the packed board, the
+//                           player-2 one swapped in nibble space); a restart rebuilds its board in LDS and draws its next
+//                           game as straight-line code (make_game).  The per-step forms (k_obs, TRON_ROLLOUT_PER_STEP,
+//                           the kernels below) have every step's planes in memory.  k_tile_roll, k_obs_roll_walk
 //                           (boards of more than 64 chunks, TRON_ROLL_GRID) and k_obs_roll_slide: the per-tile step
 //                           (tile_step / obs_tile), each workgroup stepping its own tiles
 //   k_inc                   TRON_STEP_INCREMENTAL: writes only the touched cells + restarted boards
@@ -47,7 +49,7 @@
 //   k_obs_slide, k_obs_roll_slide             lane_move<CodeCells>   the same body on player-1 code bytes, slide marks
 //   k_obs, k_obs_roll_walk                    lane_move_codes        mode None: two reads, four writes of code bytes in LDS
 //   k_inc                                     inline in the kernel   lane_move_codes' steps on code bytes in global memory
-//   k_obs_roll                                inline in roll_resident  the same steps on 4-bit codes in LDS, with the store mask
+//   k_obs_roll                                inline in roll_resident  the same steps on 4-bit codes in LDS, with the chunk masks
 #include "tron_device.hpp"
 #include "tron_minimax.hpp"
 #include "../../include/tron_hip.h"
@@ -78,8 +80,9 @@ struct StepOut {
 
 // Diagnostic build only (-DTRON_STAMPS): out.totals is then a stamp buffer of s_memrealtime ticks (100 MHz) for wave 0
 // and wave 1 of every workgroup; never enabled in the shipped library.  Two layouts: [blocks][2][8], one block of slots per
-// launch (STAMP: the per-tile kernels), and [blocks][2][TRON_ROLLOUT_CHUNK][4], one block per step (ROLL_STAMP:
-// roll_resident, read by scripts/roll_stamps.py).  blocks is the launch's grid: ceil(N / 64) when k_obs_roll runs one
+// launch (STAMP: the per-tile kernels), and [blocks][2][TRON_ROLLOUT_CHUNK + 1][4], one block per step (ROLL_STAMP) and a
+// last one for the launch (ROLL_STAMP_LAUNCH: 0 kernel entry, 1 step loop left, 2 plane stores issued, 3 kernel end), both
+// of roll_resident, read by scripts/roll_stamps.py.  blocks is the launch's grid: ceil(N / 64) when k_obs_roll runs one
 // wave per workgroup (roll_waves), where only wave 0's half is written.
 #ifdef TRON_STAMPS
 #define STAMP(slot)                                                                               \
@@ -90,11 +93,17 @@ struct StepOut {
 #define ROLL_STAMP(slot)                                                                          \
     do {                                                                                          \
         if (out.totals && (tid == 0 || tid == 64))                                                \
-            out.totals[(((size_t)blockIdx.x * 2 + (tid >> 6)) * TRON_ROLLOUT_CHUNK + s) * 4 + (slot)] = __builtin_amdgcn_s_memrealtime(); \
+            out.totals[(((size_t)blockIdx.x * 2 + (tid >> 6)) * (TRON_ROLLOUT_CHUNK + 1) + s) * 4 + (slot)] = __builtin_amdgcn_s_memrealtime(); \
+    } while (0)
+#define ROLL_STAMP_LAUNCH(slot)                                                                   \
+    do {                                                                                          \
+        if (out.totals && (tid == 0 || tid == 64))                                                \
+            out.totals[(((size_t)blockIdx.x * 2 + (tid >> 6)) * (TRON_ROLLOUT_CHUNK + 1) + TRON_ROLLOUT_CHUNK) * 4 + (slot)] = __builtin_amdgcn_s_memrealtime(); \
     } while (0)
 #else
 #define STAMP(slot) do { } while (0)
 #define ROLL_STAMP(slot) do { } while (0)
+#define ROLL_STAMP_LAUNCH(slot) do { } while (0)
 #endif
 
 struct __attribute__((packed, aligned(4))) U4A4 {   // 16 bytes at 4-byte alignment
@@ -939,38 +948,44 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 }
 
 // The steps of a persistent launch (k_obs_roll): ONE LANE = ONE ENV for the whole launch, and a wave owns its envs from the
-// prologue to the epilogue.  Nobody else touches an env's planes or state words during the launch, so everything a step
-// reads is carried from the step before: st4, rs4 and the Philox words of the coming step's actions in the lane's
-// registers, the board in the lane's own region of LDS (4 bits per cell, above).  The wave does the move, the plane
-// stores, the records, the totals' ballots, the Philox block of step s + 1 and make_game for the lanes that restarted,
-// all by itself: there is no workgroup barrier in the step loop and no LDS record between waves; the waves of a workgroup
-// share the fresh-board template only, built in the prologue.  Memory is read in the prologue only: a global load in the
-// loop would make the wave wait (vmcnt counts loads and stores in issue order) for every plane store it has issued.
-// The parameters are re-read per step with scalar loads (load_params_scalar).
+// prologue to the epilogue.  Nobody else touches an env's planes or state words during the launch, and nobody can read them
+// before it ends, so everything a step reads or writes is carried from the step before: st4, rs4 and the Philox words of the
+// coming step's actions in the lane's registers, the board in the lane's own region of LDS (4 bits per cell, above).  The
+// wave does the move, a restarted env's board, the records, the totals' ballots, the Philox block of step s + 1 and
+// make_game for the lanes that restarted, all by itself: there is no workgroup barrier in the step loop, no LDS record
+// between waves and no lane that touches another lane's board; the waves of a workgroup share the fresh-board template only,
+// built in the prologue.  Memory is read in the prologue only and the planes are written in the epilogue only: the loop holds
+// no global load, no s_waitcnt vmcnt and no plane store (with every CU storing 8 scattered 16-byte chunks per env-step the
+// shared store path set the launch time: profiles/r10_rollout_ab.txt, r11_rollout_ab.txt).  The parameters are re-read per
+// step with scalar loads (load_params_scalar).
+// What the caller sees: when the launch completes on its stream the buffer holds the observations of its last step, exactly
+// the bytes one store per step would have left; until a wave's epilogue its envs' planes hold what the launch began with.
 // LDS: an env's board takes 2 cpe + 1 dwords — odd, so that the same dword of the boards of the 64 lanes falls on 64
 // different banks (any power-of-two bank count) — and 65 536 boards of 24x24 are 22.8 MB: the whole batch is resident at
 // once, the launch is one round (rollout_persistent).
-// Sparse stores, computed: the planes in memory already hold what the prologue read (every writer of the API leaves the
-// player-2 plane the swap_codes4 image of the player-1 plane, and the caller never writes the buffer), and each env carries
-// a 64-bit mask of the chunks of its player-1 plane that differ from the fresh-board template (cpe <= 64: boards up to
-// 30x30; the host sends wider ones to k_obs_roll_walk).  The prologue builds the mask by comparing what it reads with the
-// template, whoever wrote it; a move stores and marks the chunks of its four cells; a restart stores the chunks in
-// mask | chunks of the two new heads from the template with the heads patched in, and the mask becomes the head chunks.
-// Nothing is compared in the loop, and a chunk outside the mask holds the template in memory and in LDS alike.
-// With one wave per SIMD nothing hides an instruction, so the two parts every wave runs in nearly every step are kept short.
-// The stores go through a wave-wide list: a third of the env-steps are restarts, which store a whole episode's chunks where an
-// env that goes on stores two to four, so the slowest of 64 lanes has about twice the wave's mean (scripts/roll_store_balance.py:
-// max 9 against ceil(sum / 64) = 4 at 24x24).  Each lane puts its (lane, chunk) entries, two bytes each, into the wave's list
-// in LDS at the prefix sum of the lanes' counts, and restart + the two head cells into its slot of 64 owner records; then lane
-// l of trip t takes entry 64 t + l, whoever owns it: one LDS read from the owner's board or the template, a head patch from
-// the owner's record, the write-back into the OWNER's board after a restart, the player-2 nibbles (swap_nibbles8), four
-// multiply-free expansions and two 16-byte stores.  The list is in (lane, chunk) order, so neighbouring lanes mostly store
-// neighbouring chunks of one env.  Lanes write boards they do not own here; LDS operations of one wave execute in order, and
-// wavefront-scope fences around the trips keep the compiler to that order (no barrier, no wait on memory).  The plane's
-// short last chunk has a branch of its own before the list.  The next game of a restarted env is drawn by make_game, two
-// Philox blocks and seven draws in a line, whose lanes go on into the general routine only when their two starts clash.
-// An env that restarts in the step it finishes in skips the move's four cell writes: its board is rebuilt from the mask
-// as it was before the move.  st4 / rs4 are written by the epilogue (same bytes as one store per step leaves behind).
+// Two 64-bit chunk masks per env (cpe <= 64: boards up to 30x30; the host sends wider ones to k_obs_roll_walk).  mask: the
+// chunks of the player-1 plane that may differ from the fresh-board template.  The prologue builds it by comparing what it
+// reads with the template, whoever wrote it (every writer of the API leaves the player-2 plane the swap_codes4 image of the
+// player-1 plane, and the caller never writes the buffer); a move marks the chunks of its four cells; a restart rewrites the
+// chunks in mask | chunks of the two new heads from the template, XORs the two head nibbles in, and the mask becomes the
+// head chunks.  Nothing is compared in the loop, and a chunk outside the mask holds the template.  dirty: the chunks whose
+// bytes in memory may differ from the board in LDS — 0 after the prologue, then everything a move marks and everything a
+// restart rewrites.  The restart's rewrite is a per-lane loop over the lane's own chunks (two LDS writes per chunk): lanes
+// write only boards they own, so the loop needs no fence and no wave barrier.
+// The epilogue stores dirty & (mask | mask0), mask0 being the mask the prologue built: a chunk outside both is the template
+// in LDS and was the template in memory when the launch began, so a restart has wiped what the launch drew there and the
+// bytes are equal.  That is what keeps the set small: a third of the env-steps are restarts at fresh places, so over 64 steps
+// dirty grows to nearly every chunk of a 24x24 board, while mask | mask0 is two episodes' trails.  The stores go through a
+// wave-wide list, because the lanes' counts differ: each lane puts its (lane, chunk) entries, two bytes each, into the
+// wave's list in LDS at the prefix sum of the lanes' counts; then lane l of trip t takes entry 64 t + l, whoever owns it:
+// one LDS read from the owner's board, the player-2 nibbles (swap_nibbles8), four multiply-free expansions and two 16-byte
+// stores.  The list is in (lane, chunk) order, so neighbouring lanes mostly store neighbouring chunks of one env.  Lanes
+// read boards they do not own here; LDS operations of one wave execute in order, and a wavefront-scope fence in front of the
+// trips keeps the compiler to that order (no barrier, no wait on memory).  The plane's short last chunk has a branch of its
+// own before the list.  The next game of a restarted env is drawn by make_game, two Philox blocks and seven draws in a
+// line, whose lanes go on into the general routine only when their two starts clash.  An env that restarts in the step it
+// finishes in skips the move's four cell writes: its board is rebuilt from the mask as it was before the move.  st4 / rs4
+// are written by the epilogue as well (same bytes as one store per step leaves behind).
 // Not reachable through the API today: tron_rollout_random always sets TRON_STEP_AUTORESET and passes out.totals only, so
 // the !autoreset branches and the out.done / out.winner / out.reward stores below (kept as the per-step kernels have them,
 // uniform branches) are run by no caller and no test.
@@ -980,9 +995,8 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
     const uint32_t sd = 2u * cpe + 1u;                              // dwords per board
     uint32_t *boards = reinterpret_cast<uint32_t *>(smem);          // [E][sd]
     uint32_t *tmpl = boards + (size_t)E * sd;                       // [2 cpe] fresh board, packed
-    // per wave: 64 owner records, then the store list of up to 64 cpe two-byte entries (the stores, below)
-    uint32_t *wrec = tmpl + 2u * cpe + (size_t)(threadIdx.x >> 6) * (64u + 32u * cpe);
-    uint16_t *wlist = reinterpret_cast<uint16_t *>(wrec + 64);
+    // per wave: the store list of up to 64 cpe two-byte entries (the epilogue)
+    uint16_t *wlist = reinterpret_cast<uint16_t *>(tmpl + 2u * cpe + (size_t)(threadIdx.x >> 6) * (32u * cpe));
 
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
@@ -998,9 +1012,11 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
     uint4 st = make_uint4(0u, 0u, 0u, 0u), rs = make_uint4(0u, 0u, 0u, 0u);
     uint32_t x0 = 0u, x1 = 0u;                                      // the Philox words of the coming step's actions
     unsigned long long mask = 0ull;                                 // chunks of the player-1 plane that differ from the template
+    unsigned long long dirty = 0ull;                                // chunks whose bytes in memory may differ from the board in LDS
     bool st_dirty = false, rs_dirty = false;
     uint32_t n_steps = 0u, n_w1 = 0u, n_w2 = 0u, n_draw = 0u;        // this wave's totals (uniform)
 
+    ROLL_STAMP_LAUNCH(0);
     // ---- prologue: the only loads from memory of the launch
     {
         Params P;
@@ -1068,6 +1084,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         }
         __syncthreads();                                            // the boards are in LDS before their lanes read them
     }
+    const unsigned long long mask0 = mask;                          // chunks that differ from the template IN MEMORY until the epilogue
 
     for (int s = 0; s < k_steps; ++s) {
         Params P;                                                   // re-read per step: see k_obs_roll
@@ -1075,12 +1092,12 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         const int S = P.S, W = P.W, G = P.G;
         ROLL_STAMP(0);
 
-        // ---- the move: lane_move_codes on the packed board (nibble reads, byte-sharing writes, the store mask)
+        // ---- the move: lane_move_codes on the packed board (nibble reads, byte-sharing writes, the chunk masks)
         bool stepped = false, restart = false;
         bool done = (st.y & META_DONE) != 0u;
         int winner = (int)((st.y >> 4) & 3u);
         float rw0 = 0.0f, rw1 = 0.0f;
-        unsigned long long sm = 0ull;                               // chunks this step stores
+        unsigned long long rb = 0ull;                               // chunks a restart rebuilds in the board
         uint32_t h1 = 0u, h2 = 0u;                                  // a restart's head cells
         if (mine && !done) {
             stepped = true;
@@ -1124,12 +1141,14 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
                     for (int j = k + 1; j < 4; ++j)
                         if ((cells[j] >> 1) == (cells[k] >> 1)) b[j] = b[k];
                 }
+                unsigned long long sm = 0ull;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     cellb[cells[k] >> 1] = (unsigned char)b[k];
                     sm |= 1ull << (cells[k] >> 4);
                 }
                 mask |= sm;
+                dirty |= sm;
             }
         }
         if (mine && done && autoreset) {                             // ACKTR.py:307-310
@@ -1138,105 +1157,26 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
             st_dirty = true;
             start_cells(S, rs.z, h1, h2);
             const unsigned long long heads = (1ull << (h1 >> 4)) | (1ull << (h2 >> 4));
-            sm = mask | heads;
+            rb = mask | heads;
+            dirty |= rb;
             mask = heads;
         }
         ROLL_STAMP(1);
 
-        // ---- the stores: both planes of the chunks in sm, from the board — or, for a restarted env, from the template
-        // with the heads in, which goes back into the board as well.  The short last chunk (G % 16 cells: border wall,
-        // stored after a head died on it and by the restart that clears it) has its own branch, per lane; the whole
-        // chunks go through the wave's list, so their stores are whole 16-byte ones.
-        {
-            const uint32_t tail = (uint32_t)G & 15u;                            // cells of the last chunk if it is short: 4, 8 or 12
-            if (tail && ((sm >> (cpe - 1u)) & 1ull)) {
-                sm &= ~(1ull << (cpe - 1u));
-                const uint32_t k = cpe - 1u, cb = k * 16u;
-                // the head cells are EMPTY in the template: XOR turns that nibble into the head's (game.py:90-91)
-                const unsigned long long v = (restart && k == (h1 >> 4) ? (unsigned long long)(NIB_EMPTY ^ NIB_P1_HEAD) << ((h1 & 15u) * 4u) : 0ull) ^
-                                             (restart && k == (h2 >> 4) ? (unsigned long long)(NIB_EMPTY ^ NIB_P2_HEAD) << ((h2 & 15u) * 4u) : 0ull);
-                const uint32_t *const sp = restart ? tmpl + 2u * k : board + 2u * k;
-                const uint32_t p0 = sp[0] ^ (uint32_t)v, p1 = sp[1] ^ (uint32_t)(v >> 32);
-                if (restart) {
-                    board[2u * k] = p0;
-                    board[2u * k + 1u] = p1;
-                }
-                uint32_t w1[4], w2[4];
-                expand_codes8(p0, w1[0], w1[1]);
-                expand_codes8(p1, w1[2], w1[3]);
-                expand_codes8(swap_nibbles8(p0), w2[0], w2[1]);
-                expand_codes8(swap_nibbles8(p1), w2[2], w2[3]);
-                uint32_t *q1 = reinterpret_cast<uint32_t *>(oenv + cb), *q2 = reinterpret_cast<uint32_t *>(oenv + G + cb);
-                q1[0] = w1[0];                                                   // never past G: the next plane starts there
-                q2[0] = w2[0];
-                if (tail > 4u) {
-                    q1[1] = w1[1];
-                    q2[1] = w2[1];
-                }
-                if (tail > 8u) {
-                    q1[2] = w1[2];
-                    q2[2] = w2[2];
-                }
+        // ---- a restart's board: the template's two dwords for every chunk that differed from it or takes a new head, then
+        // the two heads.  A head cell is EMPTY in the template: XOR turns that nibble into the head's (game.py:90-91); the
+        // two heads are different cells, possibly of one dword (same-lane LDS operations keep their order).  A head on the
+        // short last chunk is no special case here: the chunk's padding nibbles are 0 in the template and stay 0.  Each
+        // lane loops over its own chunks and writes only its own board: no fence, no wave barrier.
+        if (restart) {
+            for (; rb; rb &= rb - 1ull) {
+                const uint32_t k = (uint32_t)__ffsll((long long)rb) - 1u;
+                const uint32_t t0 = tmpl[2u * k], t1 = tmpl[2u * k + 1u];      // both reads, then both writes: one LDS round trip
+                board[2u * k] = t0;
+                board[2u * k + 1u] = t1;
             }
-            // The whole chunks go through a wave-wide list, so that the wave runs ceil(T / 64) trips of the expensive body
-            // and not its slowest lane's count.  Every lane's place in the list is the prefix sum of the lanes' counts, taken
-            // bit by bit from ballots (counts are at most 64: seven bits); the entries are (owner lane, chunk) in ascending
-            // order, so neighbouring lanes of a trip mostly hold neighbouring chunks of one env.
-            const uint32_t cnt = (uint32_t)__popcll(sm);
-            uint32_t pos = 0u, T = 0u;
-#pragma unroll
-            for (uint32_t b = 0; b < 7u; ++b) {
-                const unsigned long long m = __ballot(((cnt >> b) & 1u) != 0u);
-                pos += __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)) << b;
-                T += (uint32_t)__popcll(m) << b;
-            }
-            if (T) {
-                // what a consumer needs of the owner: restart and the two head cells (chunk 255 for an env that goes on)
-                wrec[lane] = restart ? 0x80000000u | (h1 << 12) | h2 : 0x00FFFFFFu;
-                for (uint32_t p = pos; sm; ++p) {
-                    wlist[p] = (uint16_t)(((uint32_t)lane << 6) | ((uint32_t)__ffsll((long long)sm) - 1u));
-                    sm &= sm - 1ull;
-                }
-                // Same-wave LDS operations execute in order; the fence holds the compiler to that order as well.
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                int8_t *const obase = P.obs_state + (size_t)e0 * 2u * G;       // this wave's first env
-                // An entry and its owner's record are read one trip ahead: with one wave per SIMD nothing else hides
-                // the two dependent LDS reads in front of the chunk's own.
-                uint32_t idx = (uint32_t)lane;
-                uint32_t ent = wlist[min(idx, T - 1u)];
-                uint32_t rec = wrec[ent >> 6];
-                while (idx < T) {
-                    const uint32_t own = ent >> 6, k = ent & 63u;
-                    const bool rst = (rec >> 31) != 0u;
-                    uint32_t *const ob = wboards + __umul24(own, sd) + 2u * k;    // the owner's board, written back by this lane
-                    const uint32_t *const sp = rst ? tmpl + 2u * k : ob;
-                    uint32_t p0 = sp[0], p1 = sp[1];
-                    idx += 64u;
-                    ent = wlist[min(idx, T - 1u)];
-                    const uint32_t g1 = (rec >> 12) & 0xFFFu, g2 = rec & 0xFFFu;
-                    const unsigned long long v = (k == (g1 >> 4) ? (unsigned long long)(NIB_EMPTY ^ NIB_P1_HEAD) << ((g1 & 15u) * 4u) : 0ull) ^
-                                                 (k == (g2 >> 4) ? (unsigned long long)(NIB_EMPTY ^ NIB_P2_HEAD) << ((g2 & 15u) * 4u) : 0ull);
-                    p0 ^= (uint32_t)v;
-                    p1 ^= (uint32_t)(v >> 32);
-                    if (rst) {
-                        ob[0] = p0;
-                        ob[1] = p1;
-                    }
-                    rec = wrec[ent >> 6];
-                    uint32_t w1[4], w2[4];
-                    expand_codes8(p0, w1[0], w1[1]);
-                    expand_codes8(p1, w1[2], w1[3]);
-                    expand_codes8(swap_nibbles8(p0), w2[0], w2[1]);
-                    expand_codes8(swap_nibbles8(p1), w2[2], w2[3]);
-                    int8_t *const q = obase + (__umul24(own, 2u * (uint32_t)G) + k * 16u);
-                    *reinterpret_cast<U4A4 *>(q) = U4A4{w1[0], w1[1], w1[2], w1[3]};
-                    *reinterpret_cast<U4A4 *>(q + G) = U4A4{w2[0], w2[1], w2[2], w2[3]};
-                }
-                // the next step's move reads boards that other lanes wrote, and its list overwrites this one
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            }
+            board[h1 >> 3] ^= (NIB_EMPTY ^ NIB_P1_HEAD) << ((h1 & 7u) * 4u);
+            board[h2 >> 3] ^= (NIB_EMPTY ^ NIB_P2_HEAD) << ((h2 & 7u) * 4u);
         }
         ROLL_STAMP(2);
 
@@ -1269,13 +1209,87 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         ROLL_STAMP(3);
     }
 
-    // ---- epilogue: the state words, and the wave's totals in one atomic per counter
+    ROLL_STAMP_LAUNCH(1);
+    // ---- epilogue: both planes of the chunks in dirty, from the boards (every board in LDS is final), the state words, and
+    // the wave's totals in one atomic per counter
     {
         Params P;
         load_params_scalar(P, kp);
+        const int G = P.G;
+        // A touched chunk that is the template again (outside mask) and was the template when the prologue read it (outside
+        // mask0) holds the same bytes in memory and in LDS: a restart wiped what the launch itself had drawn there.
+        dirty &= mask | mask0;
+        // The short last chunk (G % 16 cells: border wall, touched after a head died on it and by the restart that clears
+        // it) has its own branch, per lane, with dword stores; the whole chunks go through the wave's list, so their stores
+        // are whole 16-byte ones.
+        const uint32_t tail = (uint32_t)G & 15u;                                // cells of the last chunk if it is short: 4, 8 or 12
+        if (tail && ((dirty >> (cpe - 1u)) & 1ull)) {
+            dirty &= ~(1ull << (cpe - 1u));
+            const uint32_t k = cpe - 1u, cb = k * 16u;
+            const uint32_t p0 = board[2u * k], p1 = board[2u * k + 1u];
+            uint32_t w1[4], w2[4];
+            expand_codes8(p0, w1[0], w1[1]);
+            expand_codes8(p1, w1[2], w1[3]);
+            expand_codes8(swap_nibbles8(p0), w2[0], w2[1]);
+            expand_codes8(swap_nibbles8(p1), w2[2], w2[3]);
+            uint32_t *q1 = reinterpret_cast<uint32_t *>(oenv + cb), *q2 = reinterpret_cast<uint32_t *>(oenv + G + cb);
+            q1[0] = w1[0];                                                       // never past G: the next plane starts there
+            q2[0] = w2[0];
+            if (tail > 4u) {
+                q1[1] = w1[1];
+                q2[1] = w2[1];
+            }
+            if (tail > 8u) {
+                q1[2] = w1[2];
+                q2[2] = w2[2];
+            }
+        }
+        // The whole chunks go through a wave-wide list, so that the wave runs ceil(T / 64) trips of the expensive body and
+        // not its slowest lane's count.  Every lane's place in the list is the prefix sum of the lanes' counts, taken bit by
+        // bit from ballots (counts are at most 64: seven bits); the entries are (owner lane, chunk) in ascending order, so
+        // neighbouring lanes of a trip mostly hold neighbouring chunks of one env.
+        const uint32_t cnt = (uint32_t)__popcll(dirty);
+        uint32_t pos = 0u, T = 0u;
+#pragma unroll
+        for (uint32_t b = 0; b < 7u; ++b) {
+            const unsigned long long m = __ballot(((cnt >> b) & 1u) != 0u);
+            pos += __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)) << b;
+            T += (uint32_t)__popcll(m) << b;
+        }
+        if (T) {
+            for (uint32_t p = pos; dirty; ++p) {
+                wlist[p] = (uint16_t)(((uint32_t)lane << 6) | ((uint32_t)__ffsll((long long)dirty) - 1u));
+                dirty &= dirty - 1ull;
+            }
+            // Lanes read the list and boards that other lanes wrote.  Same-wave LDS operations execute in order; the fence
+            // holds the compiler to that order as well.
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            int8_t *const obase = P.obs_state + (size_t)e0 * 2u * G;           // this wave's first env
+            // An entry is read one trip ahead of the board read that depends on it.
+            uint32_t idx = (uint32_t)lane;
+            uint32_t ent = wlist[min(idx, T - 1u)];
+            while (idx < T) {
+                const uint32_t own = ent >> 6, k = ent & 63u;
+                const uint32_t *const ob = wboards + __umul24(own, sd) + 2u * k;   // the owner's board
+                const uint32_t p0 = ob[0], p1 = ob[1];
+                idx += 64u;
+                ent = wlist[min(idx, T - 1u)];
+                uint32_t w1[4], w2[4];
+                expand_codes8(p0, w1[0], w1[1]);
+                expand_codes8(p1, w1[2], w1[3]);
+                expand_codes8(swap_nibbles8(p0), w2[0], w2[1]);
+                expand_codes8(swap_nibbles8(p1), w2[2], w2[3]);
+                int8_t *const q = obase + (__umul24(own, 2u * (uint32_t)G) + k * 16u);
+                *reinterpret_cast<U4A4 *>(q) = U4A4{w1[0], w1[1], w1[2], w1[3]};
+                *reinterpret_cast<U4A4 *>(q + G) = U4A4{w2[0], w2[1], w2[2], w2[3]};
+            }
+        }
+        ROLL_STAMP_LAUNCH(2);
         if (mine && st_dirty) P.st4[env] = st;
         if (mine && rs_dirty) P.rs4[env] = rs;
     }
+    ROLL_STAMP_LAUNCH(3);
 #ifndef TRON_STAMPS
     if (out.totals && lane == 0) {
         if (n_steps) atomicAdd(&out.totals[0], (unsigned long long)n_steps);
@@ -1288,7 +1302,8 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
 
 // The random-action rollout as ONE launch for k_steps steps (tron_rollout_random): envs never interact, so a wave can
 // step its own envs k_steps times without waiting for anybody else — there is no drain of the whole chip between steps
-// and no barrier between the waves of a workgroup.  The same results, bit for bit, as k_steps launches of k_obs.
+// and no barrier between the waves of a workgroup.  The same results, bit for bit, as k_steps launches of k_obs, in memory
+// when the launch ends: the planes and the state words are written by its epilogue, not by its steps.
 // E envs per workgroup, epw (<= 64) per wave, blockDim.x / 64 waves; gridDim.x == ceil(N / E).  Mode None, int8 codes,
 // even side, cpe <= 64 (roll_resident).  TRON_ROLLOUT_RESIDENT asks for what this kernel does by itself; the flag is
 // accepted for its callers' sake.
@@ -2199,7 +2214,7 @@ int roll_tile_envs(const tron_env *h)
 // 16 x 1: 11.04   16 x 2: 11.03   16 x 4: 10.99
 // Full waves win: the step is bound by the instructions a SIMD issues, and a wave of 16 or 32 envs issues as many as one of
 // 64, so two or four narrow waves per SIMD cost what they were meant to hide.  Four waves of 64 per workgroup take 110 KB of
-// LDS at 24x24 (89 KB of boards, 22 KB of store lists): one workgroup per CU and one wave per SIMD wherever the dispatcher puts them, where 1 024 one-wave or 512
+// LDS at 24x24 (89 KB of boards, 22 KB of store lists: 111 448 B): one workgroup per CU and one wave per SIMD wherever the dispatcher puts them, where 1 024 one-wave or 512
 // two-wave workgroups land unevenly (64 x 2: some CUs hold three).  Repeated runs of 64 x 1 against 64 x 4 are in
 // profiles/r07_rollout_ab.txt.  A batch with no more 64-env waves than the chip has CUs gets one wave per workgroup, so that
 // it spreads over the CUs: a rule of thumb, not measured (the sweep is at 65 536 envs only).  Chosen once per handle.
@@ -2214,10 +2229,10 @@ int roll_waves(tron_env *h)
     return h->roll_waves;
 }
 
-// LDS of k_obs_roll (roll_resident): the packed boards, the template, and per wave 64 owner records + the store list
+// LDS of k_obs_roll (roll_resident): the packed boards, the template, and per wave the epilogue's store list
 size_t roll_smem(const tron_env *h, int E, int waves)
 {
-    return ((size_t)E * (2u * h->cpe + 1u) + 2u * h->cpe + (size_t)waves * (64u + 32u * h->cpe)) * 4u;
+    return ((size_t)E * (2u * h->cpe + 1u) + 2u * h->cpe + (size_t)waves * (32u * h->cpe)) * 4u;
 }
 
 int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipStream_t st, int E, int waves, int chunk)
@@ -2265,7 +2280,7 @@ int rollout_persistent(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out
         // TRON_ROLL_E stays envs per workgroup, TRON_ROLL_WAVES its waves; a TRON_ROLL_GRID below the workgroup count asks for
         // the walking kernel below
         int waves = env_waves > 0 ? env_waves : roll_waves(h);
-        // 30x30 (64 chunks): four waves' boards and lists are past the 160 KB of a CU, three fit.  TRON_ROLL_WAVES is clamped
+        // 30x30 (64 chunks): four waves' boards and lists (165 376 B) are past the 160 KB of a CU, three fit (124 160 B).  TRON_ROLL_WAVES is clamped
         // the same way; a TRON_ROLL_E that needs more waves than fit (256 envs at 30x30) is TRON_ERR_BAD_ARG in rollout_wave.
         while (env_e <= 0 && waves > 1 && roll_smem(h, waves * ROLL_EPW, waves) > 160u * 1024u) --waves;
         const int E = env_e > 0 ? env_e : waves * ROLL_EPW;

@@ -184,7 +184,9 @@ class VecTron:
                        resident=False):
         """k_steps random-action steps with autoreset (the BASELINE synthetic rollout): persistent launches of
         up to 64 steps each, or — per_step_launches=True — one launch per step, or — two_streams=True — one launch
-        per step and per half of the envs on two streams (same results every way).  resident=True (observation-is-state
+        per step and per half of the envs on two streams (same results every way).  self.obs holds the observations of the
+        last step once the call's work completes on the stream: a persistent launch in mode None writes them at its end, and
+        only per_step_launches=True puts every step's observations into memory.  resident=True (observation-is-state
         storage): inside a persistent launch the boards stay in LDS between steps instead of being re-read from the
         observation buffer — same results, a third less HBM traffic."""
         flags = ((nat.STEP_NONREVERSING if nonreversing else 0) | (nat.ROLLOUT_PER_STEP if per_step_launches else 0) |

@@ -62,14 +62,14 @@ enum {
                                    * of from all four — the longer-episode synthetic policy of SURVEY.md §8(d) */
 
 #define TRON_ROLLOUT_CHUNK 64     /* steps per persistent rollout launch (tron_rollout_random) */
-#define TRON_ROLLOUT_PER_STEP 8u  /* tron_rollout_random flag: one launch per step instead (for A/B measurements) */
+#define TRON_ROLLOUT_PER_STEP 8u  /* tron_rollout_random flag: one launch per step instead (for A/B measurements); the
+                                   * form in which every step's observations are in memory, one after the other     */
 #define TRON_ROLLOUT_RESIDENT 32u  /* tron_rollout_random flag, attached observation buffer only: within a persistent launch
                                     * the boards stay in LDS from step to step instead of being read back from the
                                     * observation buffer each step.  Mode None does this by itself (boards and state words
-                                    * are read in the first step of a launch only, G bytes per env once per launch, and a
-                                    * step writes only the 16-byte chunks of both planes that it can change: the chunks of
-                                    * the cells a move touches and those where a restarted board differs, about 8 chunks
-                                    * per env-step at 24x24); there the flag changes nothing.  The sliding modes honour it.
+                                    * are read at the start of a launch only, G bytes per env once per launch, and the
+                                    * launch writes at its end, once, the 16-byte chunks of both planes that its steps
+                                    * changed); there the flag changes nothing.  The sliding modes honour it.
                                     * Same results either way; ignored where it does not apply.                        */
 #define TRON_ROLLOUT_TWO_STREAMS 16u /* tron_rollout_random flag: one launch per step and per HALF of the envs, the two
                                       * halves on two streams (the handle owns the second one), so one half's launch
@@ -167,7 +167,13 @@ int tron_encode(tron_handle h, int32_t obs_fmt, void *obs, void *stream);
  * between steps — same results, bit for bit, as one launch per step (the other
  * storage modes / formats do launch per step).  flags: 0 or TRON_STEP_NONREVERSING.
  * totals u64[4] (device, may be NULL) accumulates {env_steps, p1_wins,
- * p2_wins, draws}.                                                            */
+ * p2_wins, draws}.
+ * The attached buffer holds the observations of the LAST step when the call's
+ * work completes on `stream`.  A persistent launch in mode None keeps its boards on
+ * the chip and writes the planes (and the state words) at its end, so nothing that
+ * runs beside it — another stream, the host through a mapped buffer — sees the steps
+ * in between; work queued behind the call on `stream` sees the last step as before.
+ * TRON_ROLLOUT_PER_STEP is the form whose every step is in memory.               */
 int tron_rollout_random(tron_handle h, int32_t k_steps, uint32_t flags, int32_t obs_fmt, void *obs,
                         unsigned long long *totals, void *stream);
 

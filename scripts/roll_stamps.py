@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """Per-step phase times of k_obs_roll (roll_resident) from a -DTRON_STAMPS diagnostic build (development tool).
 Build:  csrc/build.sh -DTRON_STAMPS  (or one such libtron_hip.so named by TRON_HIP_LIB), then run this on the GPU.
-The build stamps every step of a launch: [workgroups][2 waves][TRON_ROLLOUT_CHUNK steps][4 slots] of s_memrealtime ticks
-(100 MHz).  Slots: 0 step start, 1 move done, 2 stores issued, 3 records + make_game + the next step's Philox block done.
-usage: roll_stamps.py [--envs N] [--launches L]"""
+The build stamps every step of a launch and the launch itself: [workgroups][2 waves][TRON_ROLLOUT_CHUNK + 1][4 slots] of
+s_memrealtime ticks (100 MHz).  Slots of a step: 0 step start, 1 move done, 2 a restarted env's board rebuilt (before the
+planes were written once per launch: the step's plane stores issued), 3 records + make_game + the next step's Philox block
+done.  Slots of the last block: 0 kernel entry, 1 step loop left, 2 the launch's plane stores issued, 3 kernel end.
+--old-layout reads a library from before that block existed ([TRON_ROLLOUT_CHUNK][4] per wave).
+usage: roll_stamps.py [--envs N] [--launches L] [--old-layout]"""
 import argparse
 import os
 import sys
@@ -21,8 +24,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=65536)
     ap.add_argument("--launches", type=int, default=4)
+    ap.add_argument("--old-layout", action="store_true")
     a = ap.parse_args()
     N, W, K = a.envs, 24, 64
+    R = K if a.old_layout else K + 1                                # stamp blocks per wave
     env = tv.VecTron(N, W, seed=0x5EED, obs_format="codes")
     env.reset()
     for _ in range(3):
@@ -33,10 +38,10 @@ def main():
     blocks = (N + 63) // 64
     runs = []
     for _ in range(a.launches):
-        buf = torch.zeros(blocks * 2 * K * 4, dtype=torch.int64, device="cuda")
+        buf = torch.zeros(blocks * 2 * R * 4, dtype=torch.int64, device="cuda")
         env.rollout_random(K, buf)
         torch.cuda.synchronize()
-        r = buf.cpu().numpy().reshape(blocks * 2, K, 4)
+        r = buf.cpu().numpy().reshape(blocks * 2, R, 4)
         runs.append(r[r[:, 0, 0] > 0].astype(np.float64) * 0.01)    # us
     waves = len(runs[0])
     assert waves > 0 and all(len(r) == waves for r in runs), "no stamps: is the library a -DTRON_STAMPS build?"
@@ -46,7 +51,7 @@ def main():
         x = x.reshape(-1)
         print(f"  {name:44s} {np.median(x):6.2f} [{np.percentile(x, 10):6.2f} {np.percentile(x, 90):6.2f}]  mean {x.mean():6.2f}")
 
-    phases = [("move (0->1)", 0, 1), ("stores (1->2)", 1, 2), ("records + make_game + Philox (2->3)", 2, 3), ("whole (0->3)", 0, 3)]
+    phases = [("move (0->1)", 0, 1), ("stores / restart rebuild (1->2)", 1, 2), ("records + make_game + Philox (2->3)", 2, 3), ("whole (0->3)", 0, 3)]
     print(f"{N} envs x {W}x{W}, {waves} stamped waves, {a.launches} launches of {K} steps; us, median [p10 p90], mean")
     for label, steps in (("step 0 (first of the launch)", [0]), ("steps 1..62", list(range(1, K - 1))), ("step 63 (last: no Philox block after it)", [K - 1])):
         print(label)
@@ -55,11 +60,19 @@ def main():
     print("step period, start to start (0 -> 0'), steps 1..62")
     row("period", t[:, :, 2:K - 1, 0] - t[:, :, 1:K - 2, 0])
     row("gap between steps (3 -> 0')", t[:, :, 2:K - 1, 0] - t[:, :, 1:K - 2, 3])
-    print("stores phase (1->2) by step, median us:")
+    print("phase 1->2 by step, median us:")
     med = np.median((t[:, :, :, 2] - t[:, :, :, 1]).reshape(-1, K), 0)
     print("  " + " ".join(f"{x:.2f}" for x in med))
     span = t[:, :, K - 1, 3].reshape(a.launches, -1).max(1) - t[:, :, 0, 0].reshape(a.launches, -1).min(1)
-    print("launch span, first step start -> last stamp (the prologue is before it): " + " ".join(f"{x:.1f}" for x in span) + " us")
+    print("launch span, first step start -> last step's last stamp (the prologue is before it): " + " ".join(f"{x:.1f}" for x in span) + " us")
+    if not a.old_layout:
+        print("the launch, per wave")
+        row("prologue (kernel entry -> first step)", t[:, :, 0, 0] - t[:, :, K, 0])
+        row("step loop (first step -> loop left)", t[:, :, K, 1] - t[:, :, 0, 0])
+        row("epilogue: plane stores issued", t[:, :, K, 2] - t[:, :, K, 1])
+        row("epilogue: state words", t[:, :, K, 3] - t[:, :, K, 2])
+        whole = t[:, :, K, 3].reshape(a.launches, -1).max(1) - t[:, :, K, 0].reshape(a.launches, -1).min(1)
+        print("first kernel entry -> last kernel end: " + " ".join(f"{x:.1f}" for x in whole) + " us")
 
 
 if __name__ == "__main__":
