@@ -963,29 +963,43 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 // LDS: an env's board takes 2 cpe + 1 dwords — odd, so that the same dword of the boards of the 64 lanes falls on 64
 // different banks (any power-of-two bank count) — and 65 536 boards of 24x24 are 22.8 MB: the whole batch is resident at
 // once, the launch is one round (rollout_persistent).
-// Two 64-bit chunk masks per env (cpe <= 64: boards up to 30x30; the host sends wider ones to k_obs_roll_walk).  mask: the
-// chunks of the player-1 plane that may differ from the fresh-board template.  The prologue builds it by comparing what it
-// reads with the template, whoever wrote it (every writer of the API leaves the player-2 plane the swap_codes4 image of the
-// player-1 plane, and the caller never writes the buffer); a move marks the chunks of its four cells; a restart rewrites the
-// chunks in mask | chunks of the two new heads from the template, XORs the two head nibbles in, and the mask becomes the
-// head chunks.  Nothing is compared in the loop, and a chunk outside the mask holds the template.  dirty: the chunks whose
-// bytes in memory may differ from the board in LDS — 0 after the prologue, then everything a move marks and everything a
-// restart rewrites.  The restart's rewrite is a per-lane loop over the lane's own chunks (two LDS writes per chunk): lanes
-// write only boards they own, so the loop needs no fence and no wave barrier.
+// Three 64-bit chunk masks per env (cpe <= 64: boards up to 30x30; the host sends wider ones to k_obs_roll_walk).
+//   mask:  the chunks of the player-1 plane that may differ from the fresh-board template.
+//   stale: the chunks whose bytes in the lane's LDS board are garbage (a finished game's trail) and whose content IS the
+//          template.
+//   dirty: the chunks whose bytes in memory may differ from the env's board — 0 after the prologue.
+// Invariants: stale & mask == 0; a chunk outside mask | stale holds the template in LDS; stale is a subset of dirty.
+// The prologue builds mask by comparing what it reads with the template, whoever wrote it (every writer of the API leaves the
+// player-2 plane the swap_codes4 image of the player-1 plane, and the caller never writes the buffer); stale starts at 0.
+// Nothing is compared in the loop.
+// A restart wipes nothing: stale |= mask & ~heads, dirty |= mask | heads, mask = heads (the chunks of the two new heads), and
+// only the head chunks are written, straight-line — the template's two dwords each, the head nibbles XORed in in registers —
+// and leave stale.  Most of a trail's chunks are never looked at again before the next restart; the few that are, are known
+// at the moment they are looked at:
+// A move reads four cells, and only the two new heads can lie in a stale chunk (the old heads' chunks are in mask).  The
+// template's chunks of the two new heads are read in the same LDS round trip as the four bytes; where the chunk is stale the
+// cell's byte is taken from the template, and the chunk is refreshed (the template's two dwords) in front of the four cell
+// writes and leaves stale.  plain_targets and collide so see what the wiped board would have shown, an out-of-bounds head on
+// the border wall and both heads in one stale chunk included.  A move marks the chunks of its four cells in mask and dirty.
+// A lane writes only its own board in the loop, so the loop needs no fence and no wave barrier.
 // The epilogue stores dirty & (mask | mask0), mask0 being the mask the prologue built: a chunk outside both is the template
-// in LDS and was the template in memory when the launch began, so a restart has wiped what the launch drew there and the
-// bytes are equal.  That is what keeps the set small: a third of the env-steps are restarts at fresh places, so over 64 steps
-// dirty grows to nearly every chunk of a 24x24 board, while mask | mask0 is two episodes' trails.  The stores go through a
-// wave-wide list, because the lanes' counts differ: each lane puts its (lane, chunk) entries, two bytes each, into the
-// wave's list in LDS at the prefix sum of the lanes' counts; then lane l of trip t takes entry 64 t + l, whoever owns it:
-// one LDS read from the owner's board, the player-2 nibbles (swap_nibbles8), four multiply-free expansions and two 16-byte
-// stores.  The list is in (lane, chunk) order, so neighbouring lanes mostly store neighbouring chunks of one env.  Lanes
-// read boards they do not own here; LDS operations of one wave execute in order, and a wavefront-scope fence in front of the
-// trips keeps the compiler to that order (no barrier, no wait on memory).  The plane's short last chunk has a branch of its
-// own before the list.  The next game of a restarted env is drawn by make_game, two Philox blocks and seven draws in a
-// line, whose lanes go on into the general routine only when their two starts clash.  An env that restarts in the step it
-// finishes in skips the move's four cell writes: its board is rebuilt from the mask as it was before the move.  st4 / rs4
-// are written by the epilogue as well (same bytes as one store per step leaves behind).
+// (in LDS or as a stale chunk) and was the template in memory when the launch began, so the bytes are equal.  That filter
+// keeps the set small: a third of the env-steps are restarts at fresh places, so over 64 steps dirty grows to nearly every
+// chunk of a 24x24 board, while mask | mask0 is two episodes' trails.  A stored chunk that is still stale — one of mask0 that
+// no later game touched — is stored FROM THE TEMPLATE: bit 12 of its list entry selects the source in the trip body (about
+// three instructions per entry written and per trip; the alternative, the per-lane copy loop once per launch over
+// stale & mask0 in front of the list, is 17 per chunk of the wave's slowest lane).  The stores go through a wave-wide list,
+// because the lanes' counts differ: each lane puts its (source, lane, chunk) entries, two bytes each, into the wave's list
+// in LDS at the prefix sum of the lanes' counts; then lane l of trip t takes entry 64 t + l, whoever owns it: one LDS read
+// from the owner's board or the template, the player-2 nibbles (swap_nibbles8), four multiply-free expansions and two
+// 16-byte stores.  The list is in (lane, chunk) order, so neighbouring lanes mostly store neighbouring chunks of one env.
+// Lanes read boards they do not own here; LDS operations of one wave execute in order, and a wavefront-scope fence in front
+// of the trips keeps the compiler to that order (no barrier, no wait on memory).  The plane's short last chunk has a branch
+// of its own before the list, with the same choice of source.  The next game of a restarted env is drawn by make_game, two
+// Philox blocks and seven draws in a line, whose lanes go on into the general routine only when their two starts clash.
+// An env that restarts in the step it finishes in skips the move's four cell writes and its refreshes: its trail goes stale
+// by the mask as it was before the move.  st4 / rs4 are written by the epilogue as well (same bytes as one store per step
+// leaves behind).
 // Not reachable through the API today: tron_rollout_random always sets TRON_STEP_AUTORESET and passes out.totals only, so
 // the !autoreset branches and the out.done / out.winner / out.reward stores below (kept as the per-step kernels have them,
 // uniform branches) are run by no caller and no test.
@@ -1013,6 +1027,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
     uint32_t x0 = 0u, x1 = 0u;                                      // the Philox words of the coming step's actions
     unsigned long long mask = 0ull;                                 // chunks of the player-1 plane that differ from the template
     unsigned long long dirty = 0ull;                                // chunks whose bytes in memory may differ from the board in LDS
+    unsigned long long stale = 0ull;                                // chunks that ARE the template, whatever their bytes in LDS say
     bool st_dirty = false, rs_dirty = false;
     uint32_t n_steps = 0u, n_w1 = 0u, n_w2 = 0u, n_draw = 0u;        // this wave's totals (uniform)
 
@@ -1097,7 +1112,6 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         bool done = (st.y & META_DONE) != 0u;
         int winner = (int)((st.y >> 4) & 3u);
         float rw0 = 0.0f, rw1 = 0.0f;
-        unsigned long long rb = 0ull;                               // chunks a restart rebuilds in the board
         uint32_t h1 = 0u, h2 = 0u;                                  // a restart's head cells
         if (mine && !done) {
             stepped = true;
@@ -1114,9 +1128,26 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
                 c[p] += dc;
                 cells[2 + p] = cell_index(S, r[p], c[p]);
             }
-            uint32_t b[4];                                           // one LDS round trip: the bytes of the four cells
+            // One LDS round trip: the bytes of the four cells and the template's chunks of the two new heads.  Only a new
+            // head can lie in a stale chunk (the old heads' chunks are in mask); its byte then comes from the template, which
+            // is what the chunk holds once it is refreshed below.
+            uint32_t b[4], tc[2][2];
+            bool sl[2];
 #pragma unroll
             for (int k = 0; k < 4; ++k) b[k] = cellb[cells[k] >> 1];
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const uint32_t k = (uint32_t)cells[2 + p] >> 4;
+                tc[p][0] = tmpl[2u * k];
+                tc[p][1] = tmpl[2u * k + 1u];
+                sl[p] = ((stale >> k) & 1ull) != 0ull;
+            }
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const uint32_t bi = ((uint32_t)cells[2 + p] >> 1) & 7u;          // the cell's byte within its chunk
+                const uint32_t tb = (uint32_t)((((unsigned long long)tc[p][1] << 32) | tc[p][0]) >> (bi * 8u)) & 0xFFu;
+                b[2 + p] = sl[p] ? tb : b[2 + p];
+            }
             uint32_t tf[2];
 #pragma unroll
             for (int p = 0; p < 2; ++p) tf[p] = (b[2 + p] >> ((cells[2 + p] & 1) * 4)) & 15u;
@@ -1132,6 +1163,17 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
                 // the writes in the reference's order: bodies, then P1's head, then P2's (an out-of-bounds head lands on
                 // the border WALL cell; a same-cell head-on leaves P2's head).  Cells that share a byte: a later write
                 // starts from the earlier one's byte, and same-lane LDS writes keep their order.
+                // A new head's stale chunk is refreshed first: the template's two dwords, then the cell writes on top (both
+                // heads in one stale chunk write the same dwords twice).
+#pragma unroll
+                for (int p = 0; p < 2; ++p) {
+                    const uint32_t k = (uint32_t)cells[2 + p] >> 4;
+                    if (sl[p]) {
+                        board[2u * k] = tc[p][0];
+                        board[2u * k + 1u] = tc[p][1];
+                        stale &= ~(1ull << k);
+                    }
+                }
                 const uint32_t nib[4] = {NIB_P1_BODY, NIB_P2_BODY, NIB_P1_HEAD, NIB_P2_HEAD};
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -1157,26 +1199,35 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
             st_dirty = true;
             start_cells(S, rs.z, h1, h2);
             const unsigned long long heads = (1ull << (h1 >> 4)) | (1ull << (h2 >> 4));
-            rb = mask | heads;
-            dirty |= rb;
+            dirty |= mask | heads;
+            stale = (stale | mask) & ~heads;                         // the old trail is not wiped: its chunks go stale
             mask = heads;
         }
         ROLL_STAMP(1);
 
-        // ---- a restart's board: the template's two dwords for every chunk that differed from it or takes a new head, then
-        // the two heads.  A head cell is EMPTY in the template: XOR turns that nibble into the head's (game.py:90-91); the
-        // two heads are different cells, possibly of one dword (same-lane LDS operations keep their order).  A head on the
-        // short last chunk is no special case here: the chunk's padding nibbles are 0 in the template and stay 0.  Each
-        // lane loops over its own chunks and writes only its own board: no fence, no wave barrier.
+        // ---- a restart's board: the two head chunks only, straight-line (everything else the old game drew went stale
+        // above).  One LDS round trip reads the template's two dwords of each head chunk; the heads go in in registers — a
+        // head cell is EMPTY in the template: XOR turns that nibble into the head's (game.py:90-91); the two heads are
+        // different cells, possibly of one chunk or one dword, and then both chunks' words take both XORs and the two
+        // writes store the same bytes — and the two chunks are written.  A head on the short last chunk is no special
+        // case: the chunk's padding nibbles are 0 in the template and stay 0.  A lane writes only its own board: no fence,
+        // no wave barrier.
         if (restart) {
-            for (; rb; rb &= rb - 1ull) {
-                const uint32_t k = (uint32_t)__ffsll((long long)rb) - 1u;
-                const uint32_t t0 = tmpl[2u * k], t1 = tmpl[2u * k + 1u];      // both reads, then both writes: one LDS round trip
-                board[2u * k] = t0;
-                board[2u * k + 1u] = t1;
+            const uint32_t k1 = h1 >> 4, k2 = h2 >> 4;
+            uint32_t a[2] = {tmpl[2u * k1], tmpl[2u * k1 + 1u]}, c[2] = {tmpl[2u * k2], tmpl[2u * k2 + 1u]};
+            const uint32_t hx1 = (NIB_EMPTY ^ NIB_P1_HEAD) << ((h1 & 7u) * 4u), hx2 = (NIB_EMPTY ^ NIB_P2_HEAD) << ((h2 & 7u) * 4u);
+            const uint32_t d1 = (h1 >> 3) & 1u, d2 = (h2 >> 3) & 1u;
+            const bool same = k1 == k2;
+#pragma unroll
+            for (uint32_t d = 0; d < 2u; ++d) {
+                const uint32_t y1 = d1 == d ? hx1 : 0u, y2 = d2 == d ? hx2 : 0u;
+                a[d] ^= y1 ^ (same ? y2 : 0u);
+                c[d] ^= y2 ^ (same ? y1 : 0u);
             }
-            board[h1 >> 3] ^= (NIB_EMPTY ^ NIB_P1_HEAD) << ((h1 & 7u) * 4u);
-            board[h2 >> 3] ^= (NIB_EMPTY ^ NIB_P2_HEAD) << ((h2 & 7u) * 4u);
+            board[2u * k1] = a[0];
+            board[2u * k1 + 1u] = a[1];
+            board[2u * k2] = c[0];
+            board[2u * k2 + 1u] = c[1];
         }
         ROLL_STAMP(2);
 
@@ -1226,7 +1277,8 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         if (tail && ((dirty >> (cpe - 1u)) & 1ull)) {
             dirty &= ~(1ull << (cpe - 1u));
             const uint32_t k = cpe - 1u, cb = k * 16u;
-            const uint32_t p0 = board[2u * k], p1 = board[2u * k + 1u];
+            const uint32_t *const src = ((stale >> k) & 1ull) ? tmpl : board;      // a stale chunk is stored as the template
+            const uint32_t p0 = src[2u * k], p1 = src[2u * k + 1u];
             uint32_t w1[4], w2[4];
             expand_codes8(p0, w1[0], w1[1]);
             expand_codes8(p1, w1[2], w1[3]);
@@ -1258,7 +1310,8 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         }
         if (T) {
             for (uint32_t p = pos; dirty; ++p) {
-                wlist[p] = (uint16_t)(((uint32_t)lane << 6) | ((uint32_t)__ffsll((long long)dirty) - 1u));
+                const uint32_t k = (uint32_t)__ffsll((long long)dirty) - 1u;
+                wlist[p] = (uint16_t)(((uint32_t)(stale >> k) & 1u) << 12 | ((uint32_t)lane << 6) | k);   // bit 12: the source is the template
                 dirty &= dirty - 1ull;
             }
             // Lanes read the list and boards that other lanes wrote.  Same-wave LDS operations execute in order; the fence
@@ -1270,8 +1323,8 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
             uint32_t idx = (uint32_t)lane;
             uint32_t ent = wlist[min(idx, T - 1u)];
             while (idx < T) {
-                const uint32_t own = ent >> 6, k = ent & 63u;
-                const uint32_t *const ob = wboards + __umul24(own, sd) + 2u * k;   // the owner's board
+                const uint32_t own = (ent >> 6) & 63u, k = ent & 63u;
+                const uint32_t *const ob = ((ent >> 12) ? tmpl : wboards + __umul24(own, sd)) + 2u * k;   // the owner's board, or the template for a stale chunk
                 const uint32_t p0 = ob[0], p1 = ob[1];
                 idx += 64u;
                 ent = wlist[min(idx, T - 1u)];
