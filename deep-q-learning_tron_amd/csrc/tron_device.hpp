@@ -244,6 +244,24 @@ __device__ inline NewGame make_game_general(uint32_t seed, uint32_t stream, int 
     return g;
 }
 
+// The two start positions from the stream's first words u (four without `fair`, six with it).
+__device__ __forceinline__ void straight_starts(const uint32_t *u, int W, int fair, NewGame &g)
+{
+    if (!fair) {                                            // util.py:64-74
+        g.r1 = randint_u32(u[0], 0, W - 1);
+        g.c1 = randint_u32(u[1], 0, W - 1);
+        g.r2 = randint_u32(u[2], 0, W - 1);
+        g.c2 = randint_u32(u[3], 0, W - 1);
+    } else {                                                // util.py:49-62: boxes around a point and its mirror image
+        const int py = randint_u32(u[0], 0, W - 1), px = randint_u32(u[1], 0, W - 1);
+        const int lb1x = max(0, px - 1), ub1x = min(W - 1, px + 1);
+        const int lb1y = max(0, py - 1), ub1y = min(W - 1, py + 1);
+        g.r1 = randint_u32(u[2], lb1x, ub1x);
+        g.c1 = randint_u32(u[3], lb1y, ub1y);
+        g.r2 = randint_u32(u[4], W - 1 - ub1x, W - 1 - lb1x);
+        g.c2 = randint_u32(u[5], W - 1 - ub1y, W - 1 - lb1y);
+    }
+}
 // The same game as make_game_general, drawn as straight-line code.  Without a clash the draws sit at
 // fixed positions of the stream: x1, y1, x2, y2, weight0, weight1, degree are words 0..6 (blocks 0
 // and 1); with `fair`, point_y and point_x come first and the seven are words 2..8 (blocks 0..2).
@@ -255,29 +273,31 @@ __device__ __forceinline__ NewGame make_game(uint32_t seed, uint32_t stream, int
     philox4x32_10(env, episode, RNG_RESET, 0u, seed, stream, u);
     philox4x32_10(env, episode, RNG_RESET, 1u, seed, stream, u + 4);
     NewGame g;
-    if (!fair) {                                            // util.py:64-74, game.py:83,87
-        g.r1 = randint_u32(u[0], 0, W - 1);
-        g.c1 = randint_u32(u[1], 0, W - 1);
-        g.r2 = randint_u32(u[2], 0, W - 1);
-        g.c2 = randint_u32(u[3], 0, W - 1);
+    straight_starts(u, W, fair, g);
+    if (!fair) {                                            // game.py:83,87
         g.w0 = randint_u32(u[4], 40, 101);
         g.w1 = randint_u32(u[5], 40, 101);
         g.degree = randint_u32(u[6], -30, 30);
-    } else {                                                // util.py:49-62: boxes around a point and its mirror image
+    } else {
         philox4x32_10(env, episode, RNG_RESET, 2u, seed, stream, u + 8);
-        const int py = randint_u32(u[0], 0, W - 1), px = randint_u32(u[1], 0, W - 1);
-        const int lb1x = max(0, px - 1), ub1x = min(W - 1, px + 1);
-        const int lb1y = max(0, py - 1), ub1y = min(W - 1, py + 1);
-        g.r1 = randint_u32(u[2], lb1x, ub1x);
-        g.c1 = randint_u32(u[3], lb1y, ub1y);
-        g.r2 = randint_u32(u[4], W - 1 - ub1x, W - 1 - lb1x);
-        g.c2 = randint_u32(u[5], W - 1 - ub1y, W - 1 - lb1y);
         g.w0 = randint_u32(u[6], 40, 101);
         g.w1 = randint_u32(u[7], 40, 101);
         g.degree = randint_u32(u[8], -30, 30);
     }
     if (g.r1 == g.r2 && g.c1 == g.c2) g = make_game_general(seed, stream, W, fair, env, episode);
     return g;
+}
+// make_game's start positions alone (pack_pos), for a caller that has no use for the weights and the degree yet: one
+// Philox block (two with `fair`) instead of two (three).  A clash goes through the general routine as in make_game.
+__device__ __forceinline__ uint32_t make_game_starts(uint32_t seed, uint32_t stream, int W, int fair, uint32_t env, uint32_t episode)
+{
+    uint32_t u[8];
+    philox4x32_10(env, episode, RNG_RESET, 0u, seed, stream, u);
+    if (fair) philox4x32_10(env, episode, RNG_RESET, 1u, seed, stream, u + 4);
+    NewGame g;
+    straight_starts(u, W, fair, g);
+    if (g.r1 == g.r2 && g.c1 == g.c2) g = make_game_general(seed, stream, W, fair, env, episode);
+    return pack_pos(g.r1, g.c1, g.r2, g.c2);
 }
 
 // Game.get_rate(player) in float64, same operation order as game.py:100-102.

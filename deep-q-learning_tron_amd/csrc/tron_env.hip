@@ -33,7 +33,8 @@
 //                           prologue only and WRITTEN IN THE EPILOGUE ONLY: a step touches LDS and registers, and the
 //                           launch's end stores the chunks its steps touched (both planes from the packed board, the
 //                           player-2 one swapped in nibble space); a restart rebuilds its board in LDS and draws its next
-//                           game as straight-line code (make_game).  The per-step forms (k_obs, TRON_ROLLOUT_PER_STEP,
+//                           game's starts as straight-line code (make_game_starts; the weights and the degree are drawn
+//                           in the epilogue).  The per-step forms (k_obs, TRON_ROLLOUT_PER_STEP,
 //                           the kernels below) have every step's planes in memory.  k_tile_roll, k_obs_roll_walk
 //                           (boards of more than 64 chunks, TRON_ROLL_GRID) and k_obs_roll_slide: the per-tile step
 //                           (tile_step / obs_tile), each workgroup stepping its own tiles
@@ -951,8 +952,8 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 // prologue to the epilogue.  Nobody else touches an env's planes or state words during the launch, and nobody can read them
 // before it ends, so everything a step reads or writes is carried from the step before: st4, rs4 and the Philox words of the
 // coming step's actions in the lane's registers, the board in the lane's own region of LDS (4 bits per cell, above).  The
-// wave does the move, a restarted env's board, the records, the totals' ballots, the Philox block of step s + 1 and
-// make_game for the lanes that restarted, all by itself: there is no workgroup barrier in the step loop, no LDS record
+// wave does the move, a restarted env's board and the starts of its next game, the records, the totals' ballots and the
+// Philox block of step s + 1, all by itself: there is no workgroup barrier in the step loop, no LDS record
 // between waves and no lane that touches another lane's board; the waves of a workgroup share the fresh-board template only,
 // built in the prologue.  Memory is read in the prologue only and the planes are written in the epilogue only: the loop holds
 // no global load, no s_waitcnt vmcnt and no plane store (with every CU storing 8 scattered 16-byte chunks per env-step the
@@ -995,8 +996,18 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 // 16-byte stores.  The list is in (lane, chunk) order, so neighbouring lanes mostly store neighbouring chunks of one env.
 // Lanes read boards they do not own here; LDS operations of one wave execute in order, and a wavefront-scope fence in front
 // of the trips keeps the compiler to that order (no barrier, no wait on memory).  The plane's short last chunk has a branch
-// of its own before the list, with the same choice of source.  The next game of a restarted env is drawn by make_game, two
-// Philox blocks and seven draws in a line, whose lanes go on into the general routine only when their two starts clash.
+// of its own before the list, with the same choice of source.
+// The next game of a restarted env.  CONTRACT: no step of mode None reads rs4.envp or rs4.nenvp (the weights and the degree
+// act in the sliding modes only, and this kernel is launched for mode None alone: tron_rollout_random sends every other
+// mode to k_obs_roll_slide / k_tile_roll).  They matter as the bytes of rs4 the epilogue stores, so the loop draws what a
+// step does read and no more: a restart moves rs4.episode on and draws rs4.nstart with make_game_starts — one Philox block
+// and four draws in a line (two blocks with `fair`), whose lanes go on into the general routine only when their two
+// starts clash — and counts the env's restarts (0, 1, 2 for two and more).  The epilogue then sets the two words from the
+// final episode e: nenvp is make_game(env, e)'s; envp is untouched without a restart, the nenvp the prologue read after
+// one, make_game(env, e - 1)'s after two and more — what rotating the words at every restart left there, tron_set_weight_
+// degree's values in envp until the first restart included.  Both through the full make_game, clash path and all.  A third
+// of the env-steps of a 24x24 batch are restarts, so some lane of a wave restarts in nearly every step and the wave ran
+// make_game's second block, with a third of its lanes active, in nearly every step (profiles/r13_rollout_ab.txt).
 // An env that restarts in the step it finishes in skips the move's four cell writes and its refreshes: its trail goes stale
 // by the mask as it was before the move.  st4 / rs4 are written by the epilogue as well (same bytes as one store per step
 // leaves behind).
@@ -1028,7 +1039,8 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
     unsigned long long mask = 0ull;                                 // chunks of the player-1 plane that differ from the template
     unsigned long long dirty = 0ull;                                // chunks whose bytes in memory may differ from the board in LDS
     unsigned long long stale = 0ull;                                // chunks that ARE the template, whatever their bytes in LDS say
-    bool st_dirty = false, rs_dirty = false;
+    bool st_dirty = false;
+    uint32_t n_restarts = 0u;                                       // this env's restarts in the launch: 0, 1, or 2 for two and more
     uint32_t n_steps = 0u, n_w1 = 0u, n_w2 = 0u, n_draw = 0u;        // this wave's totals (uniform)
 
     ROLL_STAMP_LAUNCH(0);
@@ -1108,11 +1120,10 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         ROLL_STAMP(0);
 
         // ---- the move: lane_move_codes on the packed board (nibble reads, byte-sharing writes, the chunk masks)
-        bool stepped = false, restart = false;
+        bool stepped = false;
         bool done = (st.y & META_DONE) != 0u;
         int winner = (int)((st.y >> 4) & 3u);
         float rw0 = 0.0f, rw1 = 0.0f;
-        uint32_t h1 = 0u, h2 = 0u;                                  // a restart's head cells
         if (mine && !done) {
             stepped = true;
             const int a[2] = {draw_action(x0, (st.y >> 8) & 0xFu, nonrev), draw_action(x1, (st.y >> 12) & 0xFu, nonrev)};
@@ -1193,27 +1204,27 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
                 dirty |= sm;
             }
         }
-        if (mine && done && autoreset) {                             // ACKTR.py:307-310
-            restart = true;
+        ROLL_STAMP(1);
+
+        // ---- a restart (ACKTR.py:307-310), one divergent region: the state words, the board, the next game's starts.
+        // The board: the two head chunks only, straight-line (everything else the old game drew goes stale).  One LDS
+        // round trip reads the template's two dwords of each head chunk; the heads go in in registers — a head cell is
+        // EMPTY in the template: XOR turns that nibble into the head's (game.py:90-91); the two heads are different
+        // cells, possibly of one chunk or one dword, and then both chunks' words take both XORs and the two writes store
+        // the same bytes — and the two chunks are written.  A head on the short last chunk is no special case: the
+        // chunk's padding nibbles are 0 in the template and stay 0.  A lane writes only its own board: no fence, no wave
+        // barrier.  The next game: rs4.episode moves on and rs4.nstart is drawn, one Philox block (make_game_starts);
+        // rs4.envp and rs4.nenvp stay as the prologue read them until the epilogue (no step of mode None reads them).
+        if (mine && done && autoreset) {
             st = restarted_st4(rs.z, st.w);
             st_dirty = true;
+            uint32_t h1, h2;                                         // the new heads' cells
             start_cells(S, rs.z, h1, h2);
-            const unsigned long long heads = (1ull << (h1 >> 4)) | (1ull << (h2 >> 4));
+            const uint32_t k1 = h1 >> 4, k2 = h2 >> 4;
+            const unsigned long long heads = (1ull << k1) | (1ull << k2);
             dirty |= mask | heads;
             stale = (stale | mask) & ~heads;                         // the old trail is not wiped: its chunks go stale
             mask = heads;
-        }
-        ROLL_STAMP(1);
-
-        // ---- a restart's board: the two head chunks only, straight-line (everything else the old game drew went stale
-        // above).  One LDS round trip reads the template's two dwords of each head chunk; the heads go in in registers — a
-        // head cell is EMPTY in the template: XOR turns that nibble into the head's (game.py:90-91); the two heads are
-        // different cells, possibly of one chunk or one dword, and then both chunks' words take both XORs and the two
-        // writes store the same bytes — and the two chunks are written.  A head on the short last chunk is no special
-        // case: the chunk's padding nibbles are 0 in the template and stay 0.  A lane writes only its own board: no fence,
-        // no wave barrier.
-        if (restart) {
-            const uint32_t k1 = h1 >> 4, k2 = h2 >> 4;
             uint32_t a[2] = {tmpl[2u * k1], tmpl[2u * k1 + 1u]}, c[2] = {tmpl[2u * k2], tmpl[2u * k2 + 1u]};
             const uint32_t hx1 = (NIB_EMPTY ^ NIB_P1_HEAD) << ((h1 & 7u) * 4u), hx2 = (NIB_EMPTY ^ NIB_P2_HEAD) << ((h2 & 7u) * 4u);
             const uint32_t d1 = (h1 >> 3) & 1u, d2 = (h2 >> 3) & 1u;
@@ -1228,6 +1239,9 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
             board[2u * k1 + 1u] = a[1];
             board[2u * k2] = c[0];
             board[2u * k2 + 1u] = c[1];
+            rs.y += 1u;
+            rs.z = make_game_starts(P.seed, P.stream, W, P.fair, (uint32_t)env, rs.y);
+            n_restarts = min(n_restarts + 1u, 2u);
         }
         ROLL_STAMP(2);
 
@@ -1245,12 +1259,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
             n_draw += (uint32_t)__popcll(__ballot(wn == 0));
         }
 
-        // ---- the next start of the envs that restarted (rs4 moves on one game), then the coming step's Philox words
-        if (restart) {
-            const NewGame ng = make_game(P.seed, P.stream, W, P.fair, (uint32_t)env, rs.y + 1u);
-            rs = make_uint4(rs.w, rs.y + 1u, pack_pos(ng.r1, ng.c1, ng.r2, ng.c2), pack_envp(ng.w0, ng.w1, ng.degree));
-            rs_dirty = true;
-        }
+        // ---- the coming step's Philox words
         if (mine && s + 1 < k_steps) {
             uint32_t x[4];
             philox4x32_10((uint32_t)env, st.w, RNG_STEP, 0u, P.seed, P.stream, x);
@@ -1340,7 +1349,21 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         }
         ROLL_STAMP_LAUNCH(2);
         if (mine && st_dirty) P.st4[env] = st;
-        if (mine && rs_dirty) P.rs4[env] = rs;
+        // rs4.envp / rs4.nenvp of an env that restarted, drawn here once instead of at every restart: nenvp belongs to the
+        // game at the final `episode`; envp is what nenvp was before the env's last restart — the word the prologue read
+        // after one restart (so what tron_set_weight_degree put into envp leaves with the first restart, as it always
+        // did), the game at episode - 1 after two and more.  The full make_game, clash path included.
+        if (mine && n_restarts) {
+            uint32_t envp = rs.w;
+#pragma nounroll
+            for (uint32_t back = n_restarts - 1u; (int)back >= 0; --back) {
+                const NewGame ng = make_game(P.seed, P.stream, P.W, P.fair, (uint32_t)env, rs.y - back);
+                if (back) envp = pack_envp(ng.w0, ng.w1, ng.degree);
+                else rs.w = pack_envp(ng.w0, ng.w1, ng.degree);
+            }
+            rs.x = envp;
+            P.rs4[env] = rs;
+        }
     }
     ROLL_STAMP_LAUNCH(3);
 #ifndef TRON_STAMPS
@@ -2330,6 +2353,7 @@ int rollout_persistent(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out
     }
     const bool sliding = h->P.mode != TRON_MODE_NONE;
     if (!sliding && h->cpe <= 64u) {
+        // (mode None ONLY: k_obs_roll leaves rs4.envp / rs4.nenvp alone until its epilogue, which no sliding step could bear)
         // TRON_ROLL_E stays envs per workgroup, TRON_ROLL_WAVES its waves; a TRON_ROLL_GRID below the workgroup count asks for
         // the walking kernel below
         int waves = env_waves > 0 ? env_waves : roll_waves(h);

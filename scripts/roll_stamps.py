@@ -2,9 +2,10 @@
 """Per-step phase times of k_obs_roll (roll_resident) from a -DTRON_STAMPS diagnostic build (development tool).
 Build:  csrc/build.sh -DTRON_STAMPS  (or one such libtron_hip.so named by TRON_HIP_LIB), then run this on the GPU.
 The build stamps every step of a launch and the launch itself: [workgroups][2 waves][TRON_ROLLOUT_CHUNK + 1][4 slots] of
-s_memrealtime ticks (100 MHz).  Slots of a step: 0 step start, 1 move done, 2 a restarted env's board rebuilt (before the
-planes were written once per launch: the step's plane stores issued), 3 records + make_game + the next step's Philox block
-done.  Slots of the last block: 0 kernel entry, 1 step loop left, 2 the launch's plane stores issued, 3 kernel end.
+s_memrealtime ticks (100 MHz).  Slots of a step: 0 step start, 1 move done, 2 a restarted env's state words, board and next
+starts done (before the restart was one region: its board rebuilt, the next game drawn in 2->3; before the planes were
+written once per launch: the step's plane stores issued), 3 records + the next step's Philox block done.  Compare 1->3
+across libraries of both kinds.  Slots of the last block: 0 kernel entry, 1 step loop left, 2 the launch's plane stores issued, 3 kernel end.
 --old-layout reads a library from before that block existed ([TRON_ROLLOUT_CHUNK][4] per wave).
 usage: roll_stamps.py [--envs N] [--launches L] [--old-layout]"""
 import argparse
@@ -51,7 +52,8 @@ def main():
         x = x.reshape(-1)
         print(f"  {name:44s} {np.median(x):6.2f} [{np.percentile(x, 10):6.2f} {np.percentile(x, 90):6.2f}]  mean {x.mean():6.2f}")
 
-    phases = [("move (0->1)", 0, 1), ("stores / restart rebuild (1->2)", 1, 2), ("records + make_game + Philox (2->3)", 2, 3), ("whole (0->3)", 0, 3)]
+    phases = [("move (0->1)", 0, 1), ("restart: state, board, next starts (1->2)", 1, 2), ("records + Philox (2->3)", 2, 3), ("restart + records + Philox (1->3)", 1, 3),
+              ("whole (0->3)", 0, 3)]
     print(f"{N} envs x {W}x{W}, {waves} stamped waves, {a.launches} launches of {K} steps; us, median [p10 p90], mean")
     for label, steps in (("step 0 (first of the launch)", [0]), ("steps 1..62", list(range(1, K - 1))), ("step 63 (last: no Philox block after it)", [K - 1])):
         print(label)
