@@ -168,6 +168,18 @@ __device__ __forceinline__ int draw_action(uint32_t x, uint32_t last, bool nonre
     if (nonreversing && last) return (int)((last - 1u + 3u + __umulhi(x, 3u)) & 3u);
     return (int)(x & 3u);
 }
+// All that draw_action takes from a step's two Philox words, as one byte: x0 & 3, x1 & 3, __umulhi(x0, 3) and
+// __umulhi(x1, 3) in bits 0-1, 2-3, 4-5, 6-7.  draw_action_byte(action_byte(x0, x1), p, ...) == draw_action(xp, ...) for
+// both policies: whoever draws the words need not know the policy or the players' last moves.
+__device__ __forceinline__ uint32_t action_byte(uint32_t x0, uint32_t x1)
+{
+    return (x0 & 3u) | ((x1 & 3u) << 2) | (__umulhi(x0, 3u) << 4) | (__umulhi(x1, 3u) << 6);
+}
+__device__ __forceinline__ int draw_action_byte(uint32_t byte, int p, uint32_t last, bool nonreversing)
+{
+    if (nonreversing && last) return (int)((last - 1u + 3u + ((byte >> (4 + 2 * p)) & 3u)) & 3u);
+    return (int)((byte >> (2 * p)) & 3u);
+}
 
 // util.make_game start placement + Game.__init__ draws (util.py:46-84, game.py:83,87) over the
 // reset stream of (env, episode): u32 number n is word n%4 of Philox(ctr = {env, episode,

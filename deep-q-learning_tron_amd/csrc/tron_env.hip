@@ -28,12 +28,14 @@
 //   k_obs / obs_tile        observation-is-state (mode None, int8 codes, even side): the caller's
 //                           attached obs buffer is the env state; read G, write 2G per env-step
 //   k_obs_roll, k_tile_roll tron_rollout_random: up to TRON_ROLLOUT_CHUNK steps in ONE launch.  k_obs_roll (roll_resident):
-//                           one lane per env and a wave on its own for the whole launch — no barrier in the step loop,
+//                           one lane per env and a game wave that owns its envs for the whole launch, with a helper wave
+//                           beside it on its SIMD that draws every Philox word of the launch into LDS rings (one
+//                           workgroup barrier per block of ROLL_R steps, none inside a block: roll_helper),
 //                           boards in LDS at 4 bits per cell (the whole batch resident in one round), memory read in the
 //                           prologue only and WRITTEN IN THE EPILOGUE ONLY: a step touches LDS and registers, and the
 //                           launch's end stores the chunks its steps touched (both planes from the packed board, the
-//                           player-2 one swapped in nibble space); a restart rebuilds its board in LDS and draws its next
-//                           game's starts as straight-line code (make_game_starts; the weights and the degree are drawn
+//                           player-2 one swapped in nibble space); a restart rebuilds its board in LDS and takes its next
+//                           game's starts from the helper's ring (make_game_starts; the weights and the degree are drawn
 //                           in the epilogue).  The per-step forms (k_obs, TRON_ROLLOUT_PER_STEP,
 //                           the kernels below) have every step's planes in memory.  k_tile_roll, k_obs_roll_walk
 //                           (boards of more than 64 chunks, TRON_ROLL_GRID) and k_obs_roll_slide: the per-tile step
@@ -93,12 +95,12 @@ struct StepOut {
     } while (0)
 #define ROLL_STAMP(slot)                                                                          \
     do {                                                                                          \
-        if (out.totals && (tid == 0 || tid == 64))                                                \
+        if (out.totals && (tid == 0 || (tid == 64 && gw > 1)))                                              \
             out.totals[(((size_t)blockIdx.x * 2 + (tid >> 6)) * (TRON_ROLLOUT_CHUNK + 1) + s) * 4 + (slot)] = __builtin_amdgcn_s_memrealtime(); \
     } while (0)
 #define ROLL_STAMP_LAUNCH(slot)                                                                   \
     do {                                                                                          \
-        if (out.totals && (tid == 0 || tid == 64))                                                \
+        if (out.totals && (tid == 0 || (tid == 64 && gw > 1)))                                              \
             out.totals[(((size_t)blockIdx.x * 2 + (tid >> 6)) * (TRON_ROLLOUT_CHUNK + 1) + TRON_ROLLOUT_CHUNK) * 4 + (slot)] = __builtin_amdgcn_s_memrealtime(); \
     } while (0)
 #else
@@ -951,11 +953,12 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 // The steps of a persistent launch (k_obs_roll): ONE LANE = ONE ENV for the whole launch, and a wave owns its envs from the
 // prologue to the epilogue.  Nobody else touches an env's planes or state words during the launch, and nobody can read them
 // before it ends, so everything a step reads or writes is carried from the step before: st4, rs4 and the Philox words of the
-// coming step's actions in the lane's registers, the board in the lane's own region of LDS (4 bits per cell, above).  The
-// wave does the move, a restarted env's board and the starts of its next game, the records, the totals' ballots and the
-// Philox block of step s + 1, all by itself: there is no workgroup barrier in the step loop, no LDS record
-// between waves and no lane that touches another lane's board; the waves of a workgroup share the fresh-board template only,
-// built in the prologue.  Memory is read in the prologue only and the planes are written in the epilogue only: the loop holds
+// block's actions in the lane's registers, the board in the lane's own region of LDS (4 bits per cell, above).  The game
+// wave does the move, a restarted env's board, the records and the lane's tally of the totals; what is random — the actions
+// of every step and the starts of every restarted env's next game — its helper wave draws ahead of it into rings in LDS
+// (roll_helper above: the rings, their invariants and the barriers).  The step loop has ONE workgroup barrier per block of
+// ROLL_R steps and none inside a block; no lane touches another lane's board, and the game waves of a workgroup share the
+// fresh-board template only, built in the prologue.  Memory is read in the prologue only and the planes are written in the epilogue only: the loop holds
 // no global load, no s_waitcnt vmcnt and no plane store (with every CU storing 8 scattered 16-byte chunks per env-step the
 // shared store path set the launch time: profiles/r10_rollout_ab.txt, r11_rollout_ab.txt).  The parameters are re-read per
 // step with scalar loads (load_params_scalar).
@@ -1002,7 +1005,8 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 // mode to k_obs_roll_slide / k_tile_roll).  They matter as the bytes of rs4 the epilogue stores, so the loop draws what a
 // step does read and no more: a restart moves rs4.episode on and draws rs4.nstart with make_game_starts — one Philox block
 // and four draws in a line (two blocks with `fair`), whose lanes go on into the general routine only when their two
-// starts clash — and counts the env's restarts (0, 1, 2 for two and more).  The epilogue then sets the two words from the
+// starts clash, drawn by the helper since round 14 and read from its ring at the restart's ordinal — and counts the env's
+// restarts (the epilogue asks: 0, 1, or two and more).  The epilogue then sets the two words from the
 // final episode e: nenvp is make_game(env, e)'s; envp is untouched without a restart, the nenvp the prologue read after
 // one, make_game(env, e - 1)'s after two and more — what rotating the words at every restart left there, tron_set_weight_
 // degree's values in envp until the first restart included.  Both through the full make_game, clash path and all.  A third
@@ -1014,17 +1018,121 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 // Not reachable through the API today: tron_rollout_random always sets TRON_STEP_AUTORESET and passes out.totals only, so
 // the !autoreset branches and the out.done / out.winner / out.reward stores below (kept as the per-step kernels have them,
 // uniform branches) are run by no caller and no test.
+// ---- the helper wave of k_obs_roll -------------------------------------------------------------------------------------------
+// A launch's steps come in blocks of ROLL_R.  Per game wave the helper keeps two rings in LDS:
+//   actions  [2][64] x ROLL_R bytes: action_byte of step s of env `lane` is byte s % ROLL_R of slot (s / ROLL_R) & 1
+//   starts   [2 ROLL_R][64] dwords: make_game_starts(env, episode0 + j), the start of the game the env's j-th restart of
+//            the launch draws, in slot j % (2 ROLL_R)
+// and reads one word per env and block, counts[64]: the env's restarts so far.
+constexpr int ROLL_R = 8;
+constexpr size_t ROLL_RING_DWORDS = 4 * WAVE + 2 * ROLL_R * WAVE + 2 * WAVE;
+static_assert(ROLL_R == 8 && TRON_ROLLOUT_CHUNK % ROLL_R == 0, "a block's action bytes are one qword; blocks tile a launch");
+
+// The wave's share of out.totals: the lanes' byte counts (steps, player-1 wins, player-2 wins, draws; at most 255 each)
+// summed over the wave into the uniform counters.
+__device__ __forceinline__ void roll_flush_tally(uint32_t &tally, uint32_t &n_steps, uint32_t &n_w1, uint32_t &n_w2, uint32_t &n_draw)
+{
+    uint32_t a = tally & 0x00FF00FFu, b = (tally >> 8) & 0x00FF00FFu;   // steps | wins 2 << 16,  wins 1 | draws << 16
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+        a += (uint32_t)__shfl_xor((int)a, o);
+        b += (uint32_t)__shfl_xor((int)b, o);
+    }
+    a = __builtin_amdgcn_readfirstlane(a);                             // every lane holds the sums
+    b = __builtin_amdgcn_readfirstlane(b);
+    n_steps += a & 0xFFFFu;
+    n_w2 += a >> 16;
+    n_w1 += b & 0xFFFFu;
+    n_draw += b >> 16;
+    tally = 0u;
+}
+
+// The helper: lane l draws for env l of its game wave, from the state words the launch began with and the env's restart
+// count alone.  It touches no board and no memory after its two loads (st, rs: the caller's).
+// Actions.  Under autoreset every env moves in every step, so step s draws with tick st.w + s; an env that enters the launch
+// finished restarts in step 0 without a move and is one tick behind from then on.  Without autoreset a finished env draws
+// nothing more, and a live one is at st.w + s as long as it is live.  The bytes are a function of (env, tick0, s).
+// Starts.  The game lane reads ordinal nres at its nres-th restart of the launch.  It restarts at most once per step, so with
+// c_b its count when block b begins (c_0 = 0, c_b <= c_(b+1) <= c_b + ROLL_R) block b reads ordinals in (c_b, c_b + ROLL_R]
+// only.  The lane publishes c_b in front of B_b (counts slot b & 1: written before B_b, read by the helper after it, and
+// written again only before B_(b+2), which the helper cannot have passed), and the helper then draws (c_b + ROLL_R, c_b +
+// 2 ROLL_R] for block b + 1; the prologue draws (0, 2 ROLL_R].  Invariant: at B_b the ring holds all of (c_(b-1), c_(b-1) +
+// 2 ROLL_R], which contains (c_b, c_b + ROLL_R].  It holds at P for b = 0 and 1 (the prologue's draws; block 0 adds none).
+// During block b the helper writes the slots of (c_b + ROLL_R, c_b + 2 ROLL_R] alone: they are not the slots block b reads,
+// both sets lying in one window of 2 ROLL_R consecutive ordinals, and the ordinals they held before were at most c_b:
+// consumed.  So at B_(b+1) the ring holds (c_b, c_b + 2 ROLL_R].  A count-blind helper (ordinals by block number alone)
+// would need a ring as deep as the launch: an env that has not restarted yet still needs ordinal 1 in the last block.  ROLL_R
+// draws per env and block, most of them for nothing (some again: the same values), no divergence but a clash's general routine.
+// The last block, a partial one included, reads what was drawn during the block before it (or the prologue), and the
+// epilogue's rs4.nstart is the word the lane's last restart read.
+// Barriers.  P ends the prologue; B_b opens block b >= 1.  Every wave of the workgroup executes P and B_1 .. B_(nb-1),
+// nb = ceil(k_steps / ROLL_R), whatever its role and however many envs it has.  Action block b is written before B_b
+// (blocks 0 and 1 before P, block b + 1 >= 2 during block b, into the slot block b - 1 was read from before B_b) and read
+// after it.  The helper draws nothing for a block that will not be played.
+__device__ __forceinline__ void roll_helper(const Params &P, int env, bool autoreset, const uint4 &st, const uint4 &rs, int k_steps,
+                                            int lane, uint2 *aring, uint32_t *sring, const uint32_t *cring)
+{
+    const uint32_t seed = P.seed, stream = P.stream;
+    const int W = P.W, fair = P.fair;
+    const uint32_t tick0 = st.w - ((autoreset && (st.y & META_DONE)) ? 1u : 0u), ep0 = rs.y;
+    const int nb = (k_steps + ROLL_R - 1) / ROLL_R;
+    uint32_t *abytes = reinterpret_cast<uint32_t *>(aring);
+    for (int b = 0; b < nb; ++b) {
+        uint32_t j0 = 0u;
+        int nj = 2 * ROLL_R, ablk = 0, nab = min(2, nb);            // the prologue: blocks 0 and 1, ordinals 1 .. 2 ROLL_R
+        if (b) {
+            __syncthreads();                                        // B_b
+            if (b + 1 >= nb) break;
+            j0 = cring[(b & 1) * WAVE + lane] + (uint32_t)ROLL_R;   // for block b + 1
+            nj = ROLL_R;
+            ablk = b + 1;
+            nab = 1;
+        }
+#pragma nounroll
+        for (int d = 0; d < nab * (ROLL_R / 4); ++d) {              // four steps' bytes, one dword
+            const uint32_t s0 = (uint32_t)(ablk * ROLL_R + d * 4);
+            uint32_t v = 0u;
+#pragma unroll
+            for (uint32_t i = 0; i < 4u; ++i) {
+                uint32_t x[4];
+                philox4x32_10((uint32_t)env, tick0 + s0 + i, RNG_STEP, 0u, seed, stream, x);
+                v |= action_byte(x[0], x[1]) << (8u * i);
+            }
+            abytes[(((s0 / ROLL_R) & 1u) * WAVE + (uint32_t)lane) * (ROLL_R / 4) + ((s0 / 4u) & (ROLL_R / 4 - 1))] = v;
+        }
+        if (autoreset) {
+#pragma nounroll
+            for (int i = 1; i <= nj; ++i) {
+                const uint32_t j = j0 + (uint32_t)i;
+                sring[(j & (2u * ROLL_R - 1u)) * WAVE + (uint32_t)lane] = make_game_starts(seed, stream, W, fair, (uint32_t)env, ep0 + j);
+            }
+        }
+        if (b == 0) __syncthreads();                                // P
+    }
+}
+
 __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uint32_t cpe, uint32_t flags, const StepOut &out,
                                               int k_steps, unsigned char *smem)
 {
     const uint32_t sd = 2u * cpe + 1u;                              // dwords per board
     uint32_t *boards = reinterpret_cast<uint32_t *>(smem);          // [E][sd]
     uint32_t *tmpl = boards + (size_t)E * sd;                       // [2 cpe] fresh board, packed
-    // per wave: the store list of up to 64 cpe two-byte entries (the epilogue)
-    uint16_t *wlist = reinterpret_cast<uint16_t *>(tmpl + 2u * cpe + (size_t)(threadIdx.x >> 6) * (32u * cpe));
 
     const int tid = threadIdx.x;
-    const int wave = tid >> 6, lane = tid & 63;
+    const int lane = tid & 63;
+    // The workgroup is gw game waves (the low half of the wave indices) and gw helper waves; helper gw + w serves game
+    // wave w's envs.  The role is wave-uniform and fixed here.
+    const int gw = (int)(blockDim.x >> 7);
+    const int hw_wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool helper = hw_wave >= gw;
+    const int wave = helper ? hw_wave - gw : hw_wave;               // the game wave (of this wave, or the one this helper serves)
+    // per game wave: the store list of up to 64 cpe two-byte entries (the epilogue)
+    uint16_t *wlist = reinterpret_cast<uint16_t *>(tmpl + 2u * cpe + (size_t)wave * (32u * cpe));
+    // per game wave: the helper's rings (roll_rings) and the restart counts the game lanes publish per block
+    uint32_t *rings = tmpl + ((2u * cpe + (size_t)gw * (32u * cpe) + 1u) & ~(size_t)1u) + (size_t)wave * ROLL_RING_DWORDS;
+    uint2 *aring = reinterpret_cast<uint2 *>(rings);                // [2][64]: a block's ROLL_R action bytes per env
+    uint32_t *sring = rings + 4 * WAVE;                             // [2 ROLL_R][64]: pack_pos of restart ordinal j in slot j % (2 ROLL_R)
+    uint32_t *cring = sring + 2 * ROLL_R * WAVE;                    // [2][64]: the env's restarts in the launch before block b, in slot b & 1
     const bool autoreset = (flags & TRON_STEP_AUTORESET) != 0u, nonrev = (flags & TRON_STEP_NONREVERSING) != 0u;
     const int we0 = wave * epw;                                     // this wave's first env within the workgroup
     const int e0 = (int)blockIdx.x * E + we0;
@@ -1035,13 +1143,14 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
     bool mine;
     int8_t *oenv;                                                   // this env's [2][G] planes
     uint4 st = make_uint4(0u, 0u, 0u, 0u), rs = make_uint4(0u, 0u, 0u, 0u);
-    uint32_t x0 = 0u, x1 = 0u;                                      // the Philox words of the coming step's actions
+    uint2 ab = make_uint2(0u, 0u);                                  // the action bytes of the block being played
     unsigned long long mask = 0ull;                                 // chunks of the player-1 plane that differ from the template
     unsigned long long dirty = 0ull;                                // chunks whose bytes in memory may differ from the board in LDS
     unsigned long long stale = 0ull;                                // chunks that ARE the template, whatever their bytes in LDS say
     bool st_dirty = false;
-    uint32_t n_restarts = 0u;                                       // this env's restarts in the launch: 0, 1, or 2 for two and more
+    uint32_t nres = 0u;                                             // this env's restarts in the launch
     uint32_t n_steps = 0u, n_w1 = 0u, n_w2 = 0u, n_draw = 0u;        // this wave's totals (uniform)
+    uint32_t tally = 0u;                                            // this env's share of them, a byte each, since the last flush
 
     ROLL_STAMP_LAUNCH(0);
     // ---- prologue: the only loads from memory of the launch
@@ -1069,6 +1178,10 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
             tmpl[d] = v;
         }
         __syncthreads();
+        if (helper) {
+            roll_helper(P, env, autoreset, st, rs, k_steps, lane, aring, sring, cring);
+            return;
+        }
         // The wave reads its envs' player-1 planes one env at a time, lane = chunk (coalesced), packs them into the env's
         // board and compares with the template: the ballot is the env's mask.  A plane byte outside the six codes cannot
         // occur in mode None: the planes are written by k_obs_reset and the attach (code1 of a tile value: six codes, the
@@ -1103,17 +1216,22 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
                 if (lane == e + j) mask = diff;
             }
         }
-        if (mine) {
-            uint32_t x[4];
-            philox4x32_10((uint32_t)env, st.w, RNG_STEP, 0u, P.seed, P.stream, x);
-            x0 = x[0];
-            x1 = x[1];
-        }
-        __syncthreads();                                            // the boards are in LDS before their lanes read them
+        __syncthreads();                                            // the boards and the helpers' first blocks are in LDS before anyone reads them
     }
     const unsigned long long mask0 = mask;                          // chunks that differ from the template IN MEMORY until the epilogue
 
     for (int s = 0; s < k_steps; ++s) {
+        if ((s & (ROLL_R - 1)) == 0) {
+            // ---- a block begins.  The one barrier per block: behind it the helper has this block's action bytes and the
+            // starts of the restart ordinals up to nres + ROLL_R in the rings, and may overwrite what the block before
+            // read; in front of it this lane publishes its restart count for the helper's next draws.
+            if (s) {
+                if (out.totals && (s & 127) == 0) roll_flush_tally(tally, n_steps, n_w1, n_w2, n_draw);
+                cring[((s / ROLL_R) & 1) * WAVE + lane] = nres;
+                __syncthreads();
+            }
+            ab = aring[((s / ROLL_R) & 1) * WAVE + lane];
+        }
         Params P;                                                   // re-read per step: see k_obs_roll
         load_params_scalar(P, kp);
         const int S = P.S, W = P.W, G = P.G;
@@ -1126,7 +1244,8 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         float rw0 = 0.0f, rw1 = 0.0f;
         if (mine && !done) {
             stepped = true;
-            const int a[2] = {draw_action(x0, (st.y >> 8) & 0xFu, nonrev), draw_action(x1, (st.y >> 12) & 0xFu, nonrev)};
+            const uint32_t abyte = (uint32_t)(((((unsigned long long)ab.y) << 32) | ab.x) >> ((uint32_t)(s & (ROLL_R - 1)) * 8u)) & 0xFFu;
+            const int a[2] = {draw_action_byte(abyte, 0, (st.y >> 8) & 0xFu, nonrev), draw_action_byte(abyte, 1, (st.y >> 12) & 0xFu, nonrev)};
             int r[2], c[2];
             unpack_pos(st.x, r, c);
             int cells[4];                                            // the old heads, the new ones
@@ -1240,8 +1359,8 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
             board[2u * k2] = c[0];
             board[2u * k2 + 1u] = c[1];
             rs.y += 1u;
-            rs.z = make_game_starts(P.seed, P.stream, W, P.fair, (uint32_t)env, rs.y);
-            n_restarts = min(n_restarts + 1u, 2u);
+            nres += 1u;
+            rs.z = sring[(nres & (2u * ROLL_R - 1u)) * WAVE + lane];  // make_game_starts(env, rs.y), drawn by the helper
         }
         ROLL_STAMP(2);
 
@@ -1251,21 +1370,8 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
             if (out.winner) out.winner[env] = (int8_t)winner;
             if (out.reward) reinterpret_cast<float2 *>(out.reward)[env] = make_float2(rw0, rw1);
         }
-        if (out.totals) {
-            const int wn = (stepped && done) ? winner : -1;
-            n_steps += (uint32_t)__popcll(__ballot(stepped));
-            n_w1 += (uint32_t)__popcll(__ballot(wn == 1));
-            n_w2 += (uint32_t)__popcll(__ballot(wn == 2));
-            n_draw += (uint32_t)__popcll(__ballot(wn == 0));
-        }
-
-        // ---- the coming step's Philox words
-        if (mine && s + 1 < k_steps) {
-            uint32_t x[4];
-            philox4x32_10((uint32_t)env, st.w, RNG_STEP, 0u, P.seed, P.stream, x);
-            x0 = x[0];
-            x1 = x[1];
-        }
+        // per lane, a byte each: steps, player 1 wins, player 2 wins, draws; summed over the wave at a flush
+        if (out.totals && stepped) tally += 1u + (done ? 1u << (winner ? 8 * winner : 24) : 0u);
         ROLL_STAMP(3);
     }
 
@@ -1353,10 +1459,10 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         // game at the final `episode`; envp is what nenvp was before the env's last restart — the word the prologue read
         // after one restart (so what tron_set_weight_degree put into envp leaves with the first restart, as it always
         // did), the game at episode - 1 after two and more.  The full make_game, clash path included.
-        if (mine && n_restarts) {
+        if (mine && nres) {
             uint32_t envp = rs.w;
 #pragma nounroll
-            for (uint32_t back = n_restarts - 1u; (int)back >= 0; --back) {
+            for (uint32_t back = min(nres, 2u) - 1u; (int)back >= 0; --back) {
                 const NewGame ng = make_game(P.seed, P.stream, P.W, P.fair, (uint32_t)env, rs.y - back);
                 if (back) envp = pack_envp(ng.w0, ng.w1, ng.degree);
                 else rs.w = pack_envp(ng.w0, ng.w1, ng.degree);
@@ -1367,6 +1473,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
     }
     ROLL_STAMP_LAUNCH(3);
 #ifndef TRON_STAMPS
+    if (out.totals) roll_flush_tally(tally, n_steps, n_w1, n_w2, n_draw);
     if (out.totals && lane == 0) {
         if (n_steps) atomicAdd(&out.totals[0], (unsigned long long)n_steps);
         if (n_w1) atomicAdd(&out.totals[1], (unsigned long long)n_w1);
@@ -1383,7 +1490,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
 // E envs per workgroup, epw (<= 64) per wave, blockDim.x / 64 waves; gridDim.x == ceil(N / E).  Mode None, int8 codes,
 // even side, cpe <= 64 (roll_resident).  TRON_ROLLOUT_RESIDENT asks for what this kernel does by itself; the flag is
 // accepted for its callers' sake.
-__global__ __launch_bounds__(BLOCK) void k_obs_roll(Params P, int E, int epw, uint32_t cpe, uint32_t flags, StepOut out, int k_steps)
+__global__ __launch_bounds__(2 * BLOCK) void k_obs_roll(Params P, int E, int epw, uint32_t cpe, uint32_t flags, StepOut out, int k_steps)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // The step's parameters are re-read from the kernel-argument segment at every step (scalar loads through a pointer the
@@ -2305,10 +2412,11 @@ int roll_waves(tron_env *h)
     return h->roll_waves;
 }
 
-// LDS of k_obs_roll (roll_resident): the packed boards, the template, and per wave the epilogue's store list
+// LDS of k_obs_roll (roll_resident): the packed boards, the template, and per game wave the epilogue's store list and the
+// helper's rings (on an even dword: one of padding)
 size_t roll_smem(const tron_env *h, int E, int waves)
 {
-    return ((size_t)E * (2u * h->cpe + 1u) + 2u * h->cpe + (size_t)waves * (32u * h->cpe)) * 4u;
+    return ((size_t)E * (2u * h->cpe + 1u) + 2u * h->cpe + (size_t)waves * (32u * h->cpe) + 1u + (size_t)waves * ROLL_RING_DWORDS) * 4u;
 }
 
 int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipStream_t st, int E, int waves, int chunk)
@@ -2327,14 +2435,14 @@ int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipS
         report = false;
         int per_cu = 0;
         hipDeviceProp_t prop;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_obs_roll, waves * WAVE, smem) == hipSuccess &&
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_obs_roll, 2 * waves * WAVE, smem) == hipSuccess &&
             hipGetDeviceProperties(&prop, h->device) == hipSuccess)
-            fprintf(stderr, "k_obs_roll: %d envs per workgroup, %d waves of %d envs, %zu B of LDS, grid %d; %d workgroups per CU x %d CUs = %d resident\n",
+            fprintf(stderr, "k_obs_roll: %d envs per workgroup, %d game waves of %d envs and as many helper waves, %zu B of LDS, grid %d; %d workgroups per CU x %d CUs = %d resident\n",
                     E, waves, epw, smem, grid, per_cu, prop.multiProcessorCount, per_cu * prop.multiProcessorCount);
         (void)hipGetLastError();
     }
     for (int left = k_steps; left > 0; left -= chunk) {
-        hipLaunchKernelGGL(k_obs_roll, dim3(grid), dim3(waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, out, left < chunk ? left : chunk);
+        hipLaunchKernelGGL(k_obs_roll, dim3(grid), dim3(2 * waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, out, left < chunk ? left : chunk);
         if (launch_status() != TRON_OK) return TRON_ERR_LAUNCH;
     }
     return TRON_OK;

@@ -4,10 +4,15 @@ Build:  csrc/build.sh -DTRON_STAMPS  (or one such libtron_hip.so named by TRON_H
 The build stamps every step of a launch and the launch itself: [workgroups][2 waves][TRON_ROLLOUT_CHUNK + 1][4 slots] of
 s_memrealtime ticks (100 MHz).  Slots of a step: 0 step start, 1 move done, 2 a restarted env's state words, board and next
 starts done (before the restart was one region: its board rebuilt, the next game drawn in 2->3; before the planes were
-written once per launch: the step's plane stores issued), 3 records + the next step's Philox block done.  Compare 1->3
-across libraries of both kinds.  Slots of the last block: 0 kernel entry, 1 step loop left, 2 the launch's plane stores issued, 3 kernel end.
---old-layout reads a library from before that block existed ([TRON_ROLLOUT_CHUNK][4] per wave).
-usage: roll_stamps.py [--envs N] [--launches L] [--old-layout]"""
+written once per launch: the step's plane stores issued), 3 records done (before the helper waves: + the next step's Philox
+block).  Compare 1->3 across libraries of both kinds.  Slots of the last block: 0 kernel entry, 1 step loop left, 2 the
+launch's plane stores issued, 3 kernel end.
+The workgroup is game waves (the low half of its wave indices) and as many helper waves; only game waves stamp: waves 0 and 1
+of a four-wave-shape workgroup, wave 0 of a one-wave-shape one (its wave 1 is the helper).  The one barrier per block of
+--block steps (ROLL_R) sits between slot 3 of the block's last step and slot 0 of the next one: the gap 3 -> 0' is printed for
+those steps and for the others; a library from before the helper waves shows the same gap in both rows.
+--old-layout reads a library from before the launch block existed ([TRON_ROLLOUT_CHUNK][4] per wave).
+usage: roll_stamps.py [--envs N] [--launches L] [--block R] [--old-layout]"""
 import argparse
 import os
 import sys
@@ -25,6 +30,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=65536)
     ap.add_argument("--launches", type=int, default=4)
+    ap.add_argument("--block", type=int, default=8)
     ap.add_argument("--old-layout", action="store_true")
     a = ap.parse_args()
     N, W, K = a.envs, 24, 64
@@ -34,8 +40,8 @@ def main():
     for _ in range(3):
         env.rollout_random(K)                                       # (the stamped build leaves a totals pointer alone when it is None)
     # The buffer is sized for the largest grid the host can choose, one 64-env wave per workgroup; with four waves per
-    # workgroup (256 envs) the grid is a quarter of that.  Slots nobody wrote (a workgroup past the grid, wave 1 of a
-    # one-wave workgroup) are told by a zero first stamp and left out.
+    # workgroup (256 envs) the grid is a quarter of that.  Slots nobody wrote (a workgroup past the grid, the helper wave
+    # that is wave 1 of a one-wave-shape workgroup) are told by a zero first stamp and left out.
     blocks = (N + 63) // 64
     runs = []
     for _ in range(a.launches):
@@ -52,7 +58,7 @@ def main():
         x = x.reshape(-1)
         print(f"  {name:44s} {np.median(x):6.2f} [{np.percentile(x, 10):6.2f} {np.percentile(x, 90):6.2f}]  mean {x.mean():6.2f}")
 
-    phases = [("move (0->1)", 0, 1), ("restart: state, board, next starts (1->2)", 1, 2), ("records + Philox (2->3)", 2, 3), ("restart + records + Philox (1->3)", 1, 3),
+    phases = [("move (0->1)", 0, 1), ("restart: state, board, next starts (1->2)", 1, 2), ("records (+ Philox) (2->3)", 2, 3), ("restart + records (+ Philox) (1->3)", 1, 3),
               ("whole (0->3)", 0, 3)]
     print(f"{N} envs x {W}x{W}, {waves} stamped waves, {a.launches} launches of {K} steps; us, median [p10 p90], mean")
     for label, steps in (("step 0 (first of the launch)", [0]), ("steps 1..62", list(range(1, K - 1))), ("step 63 (last: no Philox block after it)", [K - 1])):
@@ -61,7 +67,10 @@ def main():
             row(name, t[:, :, steps, j] - t[:, :, steps, i])
     print("step period, start to start (0 -> 0'), steps 1..62")
     row("period", t[:, :, 2:K - 1, 0] - t[:, :, 1:K - 2, 0])
-    row("gap between steps (3 -> 0')", t[:, :, 2:K - 1, 0] - t[:, :, 1:K - 2, 3])
+    gap = t[:, :, 1:K, 0] - t[:, :, 0:K - 1, 3]                     # gap[:, :, s - 1]: in front of step s
+    first = np.arange(1, K) % a.block == 0
+    row(f"gap 3 -> 0' in front of a block (s % {a.block} == 0: the barrier)", gap[:, :, first])
+    row("gap 3 -> 0' inside a block", gap[:, :, ~first])
     print("phase 1->2 by step, median us:")
     med = np.median((t[:, :, :, 2] - t[:, :, :, 1]).reshape(-1, K), 0)
     print("  " + " ".join(f"{x:.2f}" for x in med))
