@@ -87,7 +87,17 @@ struct StepOut {
 // last one for the launch (ROLL_STAMP_LAUNCH: 0 kernel entry, 1 step loop left, 2 plane stores issued, 3 kernel end), both
 // of roll_resident, read by scripts/roll_stamps.py.  blocks is the launch's grid: ceil(N / 64) when k_obs_roll runs one
 // wave per workgroup (roll_waves), where only wave 0's half is written.
+// Behind that region, at ceil(N / 64) * 2 * (TRON_ROLLOUT_CHUNK + 1) * 4 whatever the grid, the helpers of the stamped game
+// waves have their own: [blocks][2][ROLL_HSTAMPS] (ROLL_HSTAMP: 0 kernel entry, 1 prologue draws done, 2 arrival at P, 3
+// departure from P, 2 + 2 b / 3 + 2 b arrival at / departure from B_b; the last slot is the GAME wave's arrival at P, which
+// its own layout has no place for).
 #ifdef TRON_STAMPS
+constexpr int ROLL_HSTAMPS = 4 + 2 * (TRON_ROLLOUT_CHUNK / 8);
+#define ROLL_HSTAMP(slot)                                                                         \
+    do {                                                                                          \
+        if (out.totals && lane == 0 && wave < (gw > 1 ? 2 : 1))                                   \
+            out.totals[((size_t)((P.N + 63) / 64) * 2 * (TRON_ROLLOUT_CHUNK + 1)) * 4 + ((size_t)blockIdx.x * 2 + wave) * ROLL_HSTAMPS + (slot)] = __builtin_amdgcn_s_memrealtime(); \
+    } while (0)
 #define STAMP(slot)                                                                               \
     do {                                                                                          \
         if (out.totals && (tid == 0 || tid == 64))                                                \
@@ -107,6 +117,7 @@ struct StepOut {
 #define STAMP(slot) do { } while (0)
 #define ROLL_STAMP(slot) do { } while (0)
 #define ROLL_STAMP_LAUNCH(slot) do { } while (0)
+#define ROLL_HSTAMP(slot) do { } while (0)
 #endif
 
 struct __attribute__((packed, aligned(4))) U4A4 {   // 16 bytes at 4-byte alignment
@@ -1027,6 +1038,9 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 constexpr int ROLL_R = 8;
 constexpr size_t ROLL_RING_DWORDS = 4 * WAVE + 2 * ROLL_R * WAVE + 2 * WAVE;
 static_assert(ROLL_R == 8 && TRON_ROLLOUT_CHUNK % ROLL_R == 0, "a block's action bytes are one qword; blocks tile a launch");
+#ifdef TRON_STAMPS
+static_assert(ROLL_HSTAMPS == 4 + 2 * (TRON_ROLLOUT_CHUNK / ROLL_R), "two helper stamps per block barrier");
+#endif
 
 // The wave's share of out.totals: the lanes' byte counts (steps, player-1 wins, player-2 wins, draws; at most 255 each)
 // summed over the wave into the uniform counters.
@@ -1053,44 +1067,53 @@ __device__ __forceinline__ void roll_flush_tally(uint32_t &tally, uint32_t &n_st
 // finished restarts in step 0 without a move and is one tick behind from then on.  Without autoreset a finished env draws
 // nothing more, and a live one is at st.w + s as long as it is live.  The bytes are a function of (env, tick0, s).
 // Starts.  The game lane reads ordinal nres at its nres-th restart of the launch.  It restarts at most once per step, so with
-// c_b its count when block b begins (c_0 = 0, c_b <= c_(b+1) <= c_b + ROLL_R) block b reads ordinals in (c_b, c_b + ROLL_R]
-// only.  The lane publishes c_b in front of B_b (counts slot b & 1: written before B_b, read by the helper after it, and
-// written again only before B_(b+2), which the helper cannot have passed), and the helper then draws (c_b + ROLL_R, c_b +
-// 2 ROLL_R] for block b + 1; the prologue draws (0, 2 ROLL_R].  Invariant: at B_b the ring holds all of (c_(b-1), c_(b-1) +
-// 2 ROLL_R], which contains (c_b, c_b + ROLL_R].  It holds at P for b = 0 and 1 (the prologue's draws; block 0 adds none).
-// During block b the helper writes the slots of (c_b + ROLL_R, c_b + 2 ROLL_R] alone: they are not the slots block b reads,
-// both sets lying in one window of 2 ROLL_R consecutive ordinals, and the ordinals they held before were at most c_b:
-// consumed.  So at B_(b+1) the ring holds (c_b, c_b + 2 ROLL_R].  A count-blind helper (ordinals by block number alone)
-// would need a ring as deep as the launch: an env that has not restarted yet still needs ordinal 1 in the last block.  ROLL_R
-// draws per env and block, most of them for nothing (some again: the same values), no divergence but a clash's general routine.
+// c_b its count when block b begins (c_0 = 0, c_b <= c_(b+1) <= c_b + len_b, len_b <= ROLL_R the block's steps) block b reads
+// ordinals in (c_b, c_b + len_b] only.  The lane publishes c_b in front of B_b (counts slot b & 1: written before B_b, read by
+// the helper after it, and written again only before B_(b+2), which the helper cannot have passed).  The helper carries per
+// lane hi, the highest ordinal it has drawn, and TOPS THE RING UP: during block b (behind B_b; behind P for block 0, where
+// c_0 = 0 needs no read) it draws (hi, c_b + ROLL_R + len_(b+1)] and sets hi — everything block b + 1 can read, and in
+// steady state c_b - c_(b-1) draws: what block b - 1 consumed (2.8 per env and block at 24x24, the slowest lane of a wave
+// 4.8, where drawing every block's ROLL_R anew was 8).  The prologue draws (0, len_0]: hi = len_0 at P.
+// Invariant: at B_(b+1) the ring holds (c_b, hi] with hi >= c_b + ROLL_R + len_(b+1), which contains block b + 1's (c_(b+1),
+// c_(b+1) + len_(b+1)].  Induction: at B_b (P for b = 0) the ring holds (c_(b-1), hi] with hi >= c_(b-1) + ROLL_R + len_b >=
+// c_b + len_b (full blocks but the last: hi >= c_b + ROLL_R wherever a block b + 1 exists).  During block b the helper
+// writes the ordinals of (hi, c_b + 2 ROLL_R] alone, a subset of (c_b + ROLL_R, c_b + 2 ROLL_R]: not the slots block b
+// reads — (c_b, c_b + ROLL_R] and the written set lie in one window of 2 ROLL_R consecutive ordinals — and not the slots
+// of (c_b, hi], by the same window; the ordinals those slots held before are 2 ROLL_R lower, at most c_b: consumed.  A
+// count-blind helper (ordinals by block number alone) would need a ring as deep as the launch: an env that has not
+// restarted yet still needs ordinal 1 in the last block.  The lanes' counts differ, so the draw loop runs the wave's
+// slowest lane's count, the others masked; a clash's general routine runs in it as before, for a third of the draws.
 // The last block, a partial one included, reads what was drawn during the block before it (or the prologue), and the
 // epilogue's rs4.nstart is the word the lane's last restart read.
 // Barriers.  P ends the prologue; B_b opens block b >= 1.  Every wave of the workgroup executes P and B_1 .. B_(nb-1),
 // nb = ceil(k_steps / ROLL_R), whatever its role and however many envs it has.  Action block b is written before B_b
-// (blocks 0 and 1 before P, block b + 1 >= 2 during block b, into the slot block b - 1 was read from before B_b) and read
-// after it.  The helper draws nothing for a block that will not be played.
+// (block 0 before P, block b + 1 during block b, into the slot block b - 1 was read from before B_b — free from the start
+// for block 1) and read after it.  The helper draws nothing for a block that will not be played: a launch of one block
+// draws block 0 alone, and the last block's starts stop at what its steps can consume.
 __device__ __forceinline__ void roll_helper(const Params &P, int env, bool autoreset, const uint4 &st, const uint4 &rs, int k_steps,
-                                            int lane, uint2 *aring, uint32_t *sring, const uint32_t *cring)
+                                            int lane, uint2 *aring, uint32_t *sring, const uint32_t *cring, const StepOut &out,
+                                            int wave, int gw)
 {
+    ROLL_HSTAMP(0);
     const uint32_t seed = P.seed, stream = P.stream;
     const int W = P.W, fair = P.fair;
     const uint32_t tick0 = st.w - ((autoreset && (st.y & META_DONE)) ? 1u : 0u), ep0 = rs.y;
     const int nb = (k_steps + ROLL_R - 1) / ROLL_R;
     uint32_t *abytes = reinterpret_cast<uint32_t *>(aring);
-    for (int b = 0; b < nb; ++b) {
-        uint32_t j0 = 0u;
-        int nj = 2 * ROLL_R, ablk = 0, nab = min(2, nb);            // the prologue: blocks 0 and 1, ordinals 1 .. 2 ROLL_R
-        if (b) {
+    uint32_t hi = 0u;                                               // this lane's highest ordinal drawn
+    for (int b = -1; b < nb; ++b) {                                 // pass b draws for block b + 1: before P, then during block b
+        uint32_t base = 0u;                                         // c_b + ROLL_R: what block b can have consumed at the most
+        if (b > 0) {
+            ROLL_HSTAMP(2 + 2 * b);
             __syncthreads();                                        // B_b
-            if (b + 1 >= nb) break;
-            j0 = cring[(b & 1) * WAVE + lane] + (uint32_t)ROLL_R;   // for block b + 1
-            nj = ROLL_R;
-            ablk = b + 1;
-            nab = 1;
+            ROLL_HSTAMP(3 + 2 * b);
         }
+        if (b + 1 >= nb) break;
+        if (b >= 0) base = (b ? cring[(b & 1) * WAVE + lane] : 0u) + (uint32_t)ROLL_R;
+        const uint32_t to = base + (uint32_t)min(ROLL_R, k_steps - (b + 1) * ROLL_R);
 #pragma nounroll
-        for (int d = 0; d < nab * (ROLL_R / 4); ++d) {              // four steps' bytes, one dword
-            const uint32_t s0 = (uint32_t)(ablk * ROLL_R + d * 4);
+        for (int d = 0; d < ROLL_R / 4; ++d) {                      // four steps' bytes, one dword
+            const uint32_t s0 = (uint32_t)((b + 1) * ROLL_R + d * 4);
             uint32_t v = 0u;
 #pragma unroll
             for (uint32_t i = 0; i < 4u; ++i) {
@@ -1102,12 +1125,16 @@ __device__ __forceinline__ void roll_helper(const Params &P, int env, bool autor
         }
         if (autoreset) {
 #pragma nounroll
-            for (int i = 1; i <= nj; ++i) {
-                const uint32_t j = j0 + (uint32_t)i;
+            for (uint32_t j = hi + 1u; j <= to; ++j)                // (per lane: nothing where hi >= to)
                 sring[(j & (2u * ROLL_R - 1u)) * WAVE + (uint32_t)lane] = make_game_starts(seed, stream, W, fair, (uint32_t)env, ep0 + j);
-            }
+            hi = max(hi, to);
         }
-        if (b == 0) __syncthreads();                                // P
+        if (b < 0) {
+            ROLL_HSTAMP(1);
+            ROLL_HSTAMP(2);
+            __syncthreads();                                        // P
+            ROLL_HSTAMP(3);
+        }
     }
 }
 
@@ -1179,7 +1206,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         }
         __syncthreads();
         if (helper) {
-            roll_helper(P, env, autoreset, st, rs, k_steps, lane, aring, sring, cring);
+            roll_helper(P, env, autoreset, st, rs, k_steps, lane, aring, sring, cring, out, wave, gw);
             return;
         }
         // The wave reads its envs' player-1 planes one env at a time, lane = chunk (coalesced), packs them into the env's
@@ -1216,7 +1243,8 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
                 if (lane == e + j) mask = diff;
             }
         }
-        __syncthreads();                                            // the boards and the helpers' first blocks are in LDS before anyone reads them
+        ROLL_HSTAMP(ROLL_HSTAMPS - 1);                              // (the game wave's arrival at P, in its helper's region)
+        __syncthreads();                                           // the boards and the helpers' block 0 are in LDS before anyone reads them
     }
     const unsigned long long mask0 = mask;                          // chunks that differ from the template IN MEMORY until the epilogue
 

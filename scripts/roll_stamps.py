@@ -7,11 +7,17 @@ starts done (before the restart was one region: its board rebuilt, the next game
 written once per launch: the step's plane stores issued), 3 records done (before the helper waves: + the next step's Philox
 block).  Compare 1->3 across libraries of both kinds.  Slots of the last block: 0 kernel entry, 1 step loop left, 2 the
 launch's plane stores issued, 3 kernel end.
-The workgroup is game waves (the low half of its wave indices) and as many helper waves; only game waves stamp: waves 0 and 1
+The workgroup is game waves (the low half of its wave indices) and as many helper waves; these rows are the game waves': waves 0 and 1
 of a four-wave-shape workgroup, wave 0 of a one-wave-shape one (its wave 1 is the helper).  The one barrier per block of
 --block steps (ROLL_R) sits between slot 3 of the block's last step and slot 0 of the next one: the gap 3 -> 0' is printed for
 those steps and for the others; a library from before the helper waves shows the same gap in both rows.
 --old-layout reads a library from before the launch block existed ([TRON_ROLLOUT_CHUNK][4] per wave).
+Helper rows (a library whose helpers stamp; none are printed for an older one).  Behind the game waves' region, at ceil(N / 64)
+* 2 * (TRON_ROLLOUT_CHUNK + 1) * 4, the helper of each stamped game wave has 4 + 2 * TRON_ROLLOUT_CHUNK / ROLL_R slots: 0
+kernel entry, 1 prologue draws done, 2 arrival at P, 3 departure from P, 2 + 2 b / 3 + 2 b arrival at / departure from the
+barrier B_b in front of block b; the last slot is the game wave's arrival at P.  A game wave arrives at B_b with slot 3 of
+step b R - 1 and leaves it with slot 0 of step b R.  Printed per role: the work of a block (release of B_b -> arrival at
+B_(b+1)), the wait at the barriers, and per barrier which role of a pair arrives last and by how much (helper - game).
 usage: roll_stamps.py [--envs N] [--launches L] [--block R] [--old-layout]"""
 import argparse
 import os
@@ -43,13 +49,18 @@ def main():
     # workgroup (256 envs) the grid is a quarter of that.  Slots nobody wrote (a workgroup past the grid, the helper wave
     # that is wave 1 of a one-wave-shape workgroup) are told by a zero first stamp and left out.
     blocks = (N + 63) // 64
-    runs = []
+    HS = 4 + 2 * (K // a.block)                                     # helper slots per stamped wave
+    nh = 0 if a.old_layout else blocks * 2 * HS
+    runs, hruns = [], []
     for _ in range(a.launches):
-        buf = torch.zeros(blocks * 2 * R * 4, dtype=torch.int64, device="cuda")
+        buf = torch.zeros(blocks * 2 * R * 4 + nh, dtype=torch.int64, device="cuda")
         env.rollout_random(K, buf)
         torch.cuda.synchronize()
-        r = buf.cpu().numpy().reshape(blocks * 2, R, 4)
+        flat = buf.cpu().numpy()
+        r = flat[:blocks * 2 * R * 4].reshape(blocks * 2, R, 4)
         runs.append(r[r[:, 0, 0] > 0].astype(np.float64) * 0.01)    # us
+        if nh:
+            hruns.append(flat[blocks * 2 * R * 4:].reshape(blocks * 2, HS)[r[:, 0, 0] > 0].astype(np.float64) * 0.01)
     waves = len(runs[0])
     assert waves > 0 and all(len(r) == waves for r in runs), "no stamps: is the library a -DTRON_STAMPS build?"
     t = np.stack(runs, 0)                                           # [launches, stamped waves, K, 4]
@@ -84,6 +95,34 @@ def main():
         row("epilogue: state words", t[:, :, K, 3] - t[:, :, K, 2])
         whole = t[:, :, K, 3].reshape(a.launches, -1).max(1) - t[:, :, K, 0].reshape(a.launches, -1).min(1)
         print("first kernel entry -> last kernel end: " + " ".join(f"{x:.1f}" for x in whole) + " us")
+    if hruns and all((h[:, 0] > 0).all() for h in hruns):
+        h = np.stack(hruns, 0)                                      # [launches, stamped waves, HS]
+        nb = K // a.block
+        bs = np.arange(1, nb)                                       # the barriers B_1 .. B_(nb-1)
+        g_arr, g_dep = t[:, :, bs * a.block - 1, 3], t[:, :, bs * a.block, 0]
+        h_arr, h_dep = h[:, :, 2 + 2 * bs], h[:, :, 3 + 2 * bs]
+        print("the helper beside its game wave")
+        row("helper: prologue draws (entry -> done)", h[:, :, 1] - h[:, :, 0])
+        row("helper: wait at P", h[:, :, 3] - h[:, :, 2])
+        row("game: entry -> arrival at P", h[:, :, HS - 1] - t[:, :, K, 0])
+        row("game: wait at P (arrival -> first step)", t[:, :, 0, 0] - h[:, :, HS - 1])
+        late = h[:, :, 2] - h[:, :, HS - 1]
+        row("P: helper's arrival - game's", late)
+        print(f"    the helper is the later one at P in {100.0 * (late > 0).mean():.0f} % of the pairs")
+        row("game: block's work (release -> next arrival)", g_arr[:, :, 1:] - g_dep[:, :, :-1])
+        row("helper: block's work (release -> next arrival)", h_arr[:, :, 1:] - h_dep[:, :, :-1])
+        row("helper: block 0's work (P -> arrival at B_1)", h_arr[:, :, 0] - h[:, :, 3])
+        row("game: wait at a block barrier", g_dep - g_arr)
+        row("helper: wait at a block barrier", h_dep - h_arr)
+        late = h_arr - g_arr
+        row("B_b: helper's arrival - game's", late)
+        print(f"    the helper is the later one in {100.0 * (late > 0).mean():.0f} % of the pair-barriers; by barrier, median us: "
+              + " ".join(f"{x:.2f}" for x in np.median(late.reshape(-1, nb - 1), 0)))
+        # the last of the stamped waves of a workgroup (two game waves and their helpers in the four-wave shape)
+        last = np.maximum(g_arr, h_arr)
+        row("B_b: release - the pair's later arrival (waiting for others)", np.minimum(g_dep, h_dep) - last)
+    elif not a.old_layout:
+        print("no helper stamps (a library from before the helpers stamped)")
 
 
 if __name__ == "__main__":
