@@ -40,6 +40,8 @@
 //                           the kernels below) have every step's planes in memory.  k_tile_roll, k_obs_roll_walk
 //                           (boards of more than 64 chunks, TRON_ROLL_GRID) and k_obs_roll_slide: the per-tile step
 //                           (tile_step / obs_tile), each workgroup stepping its own tiles
+//   k_obs_roll_tape         tron_rollout_actions: k_obs_roll's launch (roll_resident<true>) whose helper wave copies the
+//                           action bytes from the caller's tape into the ring instead of drawing them
 //   k_inc                   TRON_STEP_INCREMENTAL: writes only the touched cells + restarted boards
 //   k_reset, k_obs_reset, k_obs_to_grid, k_obs_planes, k_get_state, k_encode_codes, k_pop_up, ...
 //                           resets, read-back and stateless encodes
@@ -52,7 +54,7 @@
 //   k_obs_slide, k_obs_roll_slide             lane_move<CodeCells>   the same body on player-1 code bytes, slide marks
 //   k_obs, k_obs_roll_walk                    lane_move_codes        mode None: two reads, four writes of code bytes in LDS
 //   k_inc                                     inline in the kernel   lane_move_codes' steps on code bytes in global memory
-//   k_obs_roll                                inline in roll_resident  the same steps on 4-bit codes in LDS, with the chunk masks
+//   k_obs_roll, k_obs_roll_tape               inline in roll_resident  the same steps on 4-bit codes in LDS, with the chunk masks
 #include "tron_device.hpp"
 #include "tron_minimax.hpp"
 #include "../../include/tron_hip.h"
@@ -1090,9 +1092,18 @@ __device__ __forceinline__ void roll_flush_tally(uint32_t &tally, uint32_t &n_st
 // (block 0 before P, block b + 1 during block b, into the slot block b - 1 was read from before B_b — free from the start
 // for block 1) and read after it.  The helper draws nothing for a block that will not be played: a launch of one block
 // draws block 0 alone, and the last block's starts stop at what its steps can consume.
+// TAPE (k_obs_roll_tape, tron_rollout_actions): the action bytes are the caller's.  tape is int8[k_steps][N][2], the launch's
+// own first step at row 0, and pass b copies block b + 1's rows of it instead of drawing them: one 2-byte load per env and
+// step — the 64 lanes' 128 bytes are contiguous within a step's row —, all of a block's loads in flight at once, each
+// player's byte & 3 (what the per-step kernels take from that byte) into bits 0-1 / 2-3 of the ring's byte, where
+// draw_action_byte finds x & 3 of a drawn step.  Same slots, same double-buffering, same hand-off at P and B_b; a lane
+// without an env of its own (mine false) and a step past k_steps load nothing.  A finished env that restarts in step s
+// makes no move in it, as in the per-step kernels: row s is then not used, and nothing is shifted.  The starts ring is
+// drawn as ever: a restart's position is keyed by (env, episode), whoever chose the actions.
+template <bool TAPE>
 __device__ __forceinline__ void roll_helper(const Params &P, int env, bool autoreset, const uint4 &st, const uint4 &rs, int k_steps,
                                             int lane, uint2 *aring, uint32_t *sring, const uint32_t *cring, const StepOut &out,
-                                            int wave, int gw)
+                                            int wave, int gw, bool mine, const int8_t *tape)
 {
     ROLL_HSTAMP(0);
     const uint32_t seed = P.seed, stream = P.stream;
@@ -1111,17 +1122,29 @@ __device__ __forceinline__ void roll_helper(const Params &P, int env, bool autor
         if (b + 1 >= nb) break;
         if (b >= 0) base = (b ? cring[(b & 1) * WAVE + lane] : 0u) + (uint32_t)ROLL_R;
         const uint32_t to = base + (uint32_t)min(ROLL_R, k_steps - (b + 1) * ROLL_R);
+        if constexpr (!TAPE) {
 #pragma nounroll
-        for (int d = 0; d < ROLL_R / 4; ++d) {                      // four steps' bytes, one dword
-            const uint32_t s0 = (uint32_t)((b + 1) * ROLL_R + d * 4);
-            uint32_t v = 0u;
+            for (int d = 0; d < ROLL_R / 4; ++d) {                  // four steps' bytes, one dword
+                const uint32_t s0 = (uint32_t)((b + 1) * ROLL_R + d * 4);
+                uint32_t v = 0u;
 #pragma unroll
-            for (uint32_t i = 0; i < 4u; ++i) {
-                uint32_t x[4];
-                philox4x32_10((uint32_t)env, tick0 + s0 + i, RNG_STEP, 0u, seed, stream, x);
-                v |= action_byte(x[0], x[1]) << (8u * i);
+                for (uint32_t i = 0; i < 4u; ++i) {
+                    uint32_t x[4];
+                    philox4x32_10((uint32_t)env, tick0 + s0 + i, RNG_STEP, 0u, seed, stream, x);
+                    v |= action_byte(x[0], x[1]) << (8u * i);
+                }
+                abytes[(((s0 / ROLL_R) & 1u) * WAVE + (uint32_t)lane) * (ROLL_R / 4) + ((s0 / 4u) & (ROLL_R / 4 - 1))] = v;
             }
-            abytes[(((s0 / ROLL_R) & 1u) * WAVE + (uint32_t)lane) * (ROLL_R / 4) + ((s0 / 4u) & (ROLL_R / 4 - 1))] = v;
+        } else {
+            const int s0 = (b + 1) * ROLL_R;                        // the block's eight rows: loads first, then the bytes
+            const uint16_t *row = reinterpret_cast<const uint16_t *>(tape) + (size_t)s0 * (size_t)P.N + (size_t)env;
+            uint32_t t[ROLL_R];
+#pragma unroll
+            for (int i = 0; i < ROLL_R; ++i) t[i] = (mine && s0 + i < k_steps) ? row[(size_t)i * (size_t)P.N] : 0u;
+            uint32_t v[2] = {0u, 0u};
+#pragma unroll
+            for (int i = 0; i < ROLL_R; ++i) v[i >> 2] |= ((t[i] & 3u) | ((t[i] >> 6) & 0xCu)) << (8 * (i & 3));
+            aring[((b + 1) & 1) * WAVE + lane] = make_uint2(v[0], v[1]);
         }
         if (autoreset) {
 #pragma nounroll
@@ -1138,8 +1161,9 @@ __device__ __forceinline__ void roll_helper(const Params &P, int env, bool autor
     }
 }
 
+template <bool TAPE>
 __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uint32_t cpe, uint32_t flags, const StepOut &out,
-                                              int k_steps, unsigned char *smem)
+                                              int k_steps, unsigned char *smem, const int8_t *tape)
 {
     const uint32_t sd = 2u * cpe + 1u;                              // dwords per board
     uint32_t *boards = reinterpret_cast<uint32_t *>(smem);          // [E][sd]
@@ -1160,7 +1184,8 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
     uint2 *aring = reinterpret_cast<uint2 *>(rings);                // [2][64]: a block's ROLL_R action bytes per env
     uint32_t *sring = rings + 4 * WAVE;                             // [2 ROLL_R][64]: pack_pos of restart ordinal j in slot j % (2 ROLL_R)
     uint32_t *cring = sring + 2 * ROLL_R * WAVE;                    // [2][64]: the env's restarts in the launch before block b, in slot b & 1
-    const bool autoreset = (flags & TRON_STEP_AUTORESET) != 0u, nonrev = (flags & TRON_STEP_NONREVERSING) != 0u;
+    // (a tape has no policy: its instantiation holds nothing of TRON_STEP_NONREVERSING)
+    const bool autoreset = (flags & TRON_STEP_AUTORESET) != 0u, nonrev = !TAPE && (flags & TRON_STEP_NONREVERSING) != 0u;
     const int we0 = wave * epw;                                     // this wave's first env within the workgroup
     const int e0 = (int)blockIdx.x * E + we0;
     const int env = e0 + lane;
@@ -1206,7 +1231,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         }
         __syncthreads();
         if (helper) {
-            roll_helper(P, env, autoreset, st, rs, k_steps, lane, aring, sring, cring, out, wave, gw);
+            roll_helper<TAPE>(P, env, autoreset, st, rs, k_steps, lane, aring, sring, cring, out, wave, gw, mine, tape);
             return;
         }
         // The wave reads its envs' player-1 planes one env at a time, lane = chunk (coalesced), packs them into the env's
@@ -1525,7 +1550,18 @@ __global__ __launch_bounds__(2 * BLOCK) void k_obs_roll(Params P, int E, int epw
     // compiler cannot see through) instead of kept live across the loop: 26 words of Params in SGPRs for the whole launch
     // spill, and every spilled word is a v_readlane per use.
     kernarg_t *kp = (kernarg_t *)__builtin_amdgcn_kernarg_segment_ptr();       // (Params is the first argument)
-    roll_resident(kp, E, epw, cpe, flags & ~TRON_ROLLOUT_RESIDENT, out, k_steps, smem);
+    roll_resident<false>(kp, E, epw, cpe, flags & ~TRON_ROLLOUT_RESIDENT, out, k_steps, smem, nullptr);
+}
+
+// The same launch with the caller's actions (tron_rollout_actions): the second instantiation of roll_resident.  Its game
+// waves run k_obs_roll's loop on bytes of the same ring; only its helper differs (roll_helper<true>), and tape points at the
+// launch's own first step.
+__global__ __launch_bounds__(2 * BLOCK) void k_obs_roll_tape(Params P, int E, int epw, uint32_t cpe, uint32_t flags, StepOut out, int k_steps,
+                                                             const int8_t *__restrict__ tape)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    kernarg_t *kp = (kernarg_t *)__builtin_amdgcn_kernarg_segment_ptr();       // (Params is the first argument: see k_obs_roll)
+    roll_resident<true>(kp, E, epw, cpe, flags, out, k_steps, smem, tape);
 }
 
 // Fewer workgroups than tiles (the TRON_ROLL_GRID override): workgroup w owns tiles w, w + gridDim.x, ... and
@@ -1563,6 +1599,7 @@ template <class R, class A0, class... A> struct first_kernel_arg<R (*)(A0, A...)
 static_assert(std::is_same<first_kernel_arg<decltype(&k_obs_roll)>::type, Params>::value,
               "k_obs_roll re-reads Params from kernarg offset 0: Params must stay its first parameter");
 static_assert(std::is_same<first_kernel_arg<decltype(&k_obs_roll_walk)>::type, Params>::value, "k_obs_roll_walk re-reads Params from kernarg offset 0");
+static_assert(std::is_same<first_kernel_arg<decltype(&k_obs_roll_tape)>::type, Params>::value, "k_obs_roll_tape re-reads Params from kernarg offset 0");
 static_assert(std::is_trivially_copyable<Params>::value && alignof(Params) <= 8 && sizeof(Params) % 4 == 0,
               "Params is block-copied from the kernel-argument segment with scalar loads");
 
@@ -2447,7 +2484,10 @@ size_t roll_smem(const tron_env *h, int E, int waves)
     return ((size_t)E * (2u * h->cpe + 1u) + 2u * h->cpe + (size_t)waves * (32u * h->cpe) + 1u + (size_t)waves * ROLL_RING_DWORDS) * 4u;
 }
 
-int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipStream_t st, int E, int waves, int chunk)
+// tape: null for k_obs_roll's own draws; else the caller's int8[k_steps][N][2], and every launch gets it advanced to its
+// own first step (k_obs_roll_tape: same grid, same workgroup, same LDS).
+int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipStream_t st, int E, int waves, int chunk,
+                 const int8_t *tape = nullptr)
 {
     if (waves < 1) waves = 1;
     if (E > waves * WAVE) waves = (E + WAVE - 1) / WAVE;            // at most 64 envs per wave
@@ -2458,6 +2498,8 @@ int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipS
     if (smem > 160u * 1024u) return TRON_ERR_BAD_ARG;
     static uint64_t prepared = 0;
     allow_big_lds(reinterpret_cast<const void *>(k_obs_roll), h->device, prepared);
+    static uint64_t prepared_t = 0;
+    if (tape) allow_big_lds(reinterpret_cast<const void *>(k_obs_roll_tape), h->device, prepared_t);
     static bool report = getenv("TRON_ROLL_REPORT") != nullptr;         // the launch shape and its occupancy on stderr, once per process
     if (report) {
         report = false;
@@ -2470,13 +2512,19 @@ int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipS
         (void)hipGetLastError();
     }
     for (int left = k_steps; left > 0; left -= chunk) {
-        hipLaunchKernelGGL(k_obs_roll, dim3(grid), dim3(2 * waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, out, left < chunk ? left : chunk);
+        if (tape)
+            hipLaunchKernelGGL(k_obs_roll_tape, dim3(grid), dim3(2 * waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, out,
+                               left < chunk ? left : chunk, tape + (size_t)(k_steps - left) * 2u * (size_t)h->P.N);
+        else
+            hipLaunchKernelGGL(k_obs_roll, dim3(grid), dim3(2 * waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, out, left < chunk ? left : chunk);
         if (launch_status() != TRON_OK) return TRON_ERR_LAUNCH;
     }
     return TRON_OK;
 }
 
-int rollout_persistent(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipStream_t st)
+// tape != null (tron_rollout_actions): TRON_ERR_UNSUPPORTED wherever the launch would not be k_obs_roll's shape — the
+// caller then steps per launch.
+int rollout_persistent(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipStream_t st, const int8_t *tape = nullptr)
 {
     static int env_e = 0, env_grid = 0, env_waves = 0, chunk = TRON_ROLLOUT_CHUNK;
     static bool probed = false;
@@ -2497,8 +2545,9 @@ int rollout_persistent(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out
         // the same way; a TRON_ROLL_E that needs more waves than fit (256 envs at 30x30) is TRON_ERR_BAD_ARG in rollout_wave.
         while (env_e <= 0 && waves > 1 && roll_smem(h, waves * ROLL_EPW, waves) > 160u * 1024u) --waves;
         const int E = env_e > 0 ? env_e : waves * ROLL_EPW;
-        if (!(env_grid > 0 && env_grid < (h->P.N + E - 1) / E)) return rollout_wave(h, k_steps, flags, out, st, E, waves, chunk);
+        if (!(env_grid > 0 && env_grid < (h->P.N + E - 1) / E)) return rollout_wave(h, k_steps, flags, out, st, E, waves, chunk, tape);
     }
+    if (tape) return TRON_ERR_UNSUPPORTED;
     static uint64_t prepared_w = 0;
     allow_big_lds(reinterpret_cast<const void *>(k_obs_roll_walk), h->device, prepared_w);
     if (!h->roll_E) h->roll_E = roll_tile_envs(h);
@@ -2605,6 +2654,33 @@ int tron_rollout_random(tron_handle h, int32_t k_steps, uint32_t flags, int32_t 
     StepOut out{nullptr, nullptr, nullptr, totals};
     if (h->P.obs_state && obs_fmt == TRON_OBS_CODES_I8 && obs != h->P.obs_state) return TRON_ERR_BAD_ARG;
     return rollout_launches(h, k_steps, flags | TRON_STEP_AUTORESET, obs_fmt, obs, out, S_(stream));
+}
+
+int tron_rollout_actions(tron_handle h, int32_t k_steps, const int8_t *actions, uint32_t flags, int32_t obs_fmt, void *obs,
+                         unsigned long long *totals, void *stream)
+{
+    if (bad_handle(h)) return h ? TRON_ERR_NO_DEVICE : TRON_ERR_BAD_ARG;
+    if (!actions || k_steps < 0 || (obs_fmt != TRON_OBS_NONE) != (obs != nullptr)) return TRON_ERR_BAD_ARG;
+    if (flags & ~TRON_ROLLOUT_PER_STEP) return TRON_ERR_BAD_ARG;    // autoreset is implied; a tape has no policy to flag
+    if (obs_fmt < TRON_OBS_NONE || obs_fmt > TRON_OBS_PLANES4_F32) return TRON_ERR_BAD_ARG;
+    if (h->P.obs_state && obs_fmt == TRON_OBS_CODES_I8 && obs != h->P.obs_state) return TRON_ERR_BAD_ARG;
+    StepOut out{nullptr, nullptr, nullptr, totals};
+    hipStream_t st = S_(stream);
+    const bool f32 = obs_fmt == TRON_OBS_PLANES3_F32 || obs_fmt == TRON_OBS_PLANES4_F32;
+    // the persistent launches: mode None on the attached codes (k_obs_roll_tape); a single step is one per-step launch
+    if (h->P.obs_state && h->P.mode == TRON_MODE_NONE && !f32 && !(flags & TRON_ROLLOUT_PER_STEP) && k_steps > 1) {
+        const int rc = rollout_persistent(h, k_steps, TRON_STEP_AUTORESET, out, st, actions);
+        if (rc != TRON_ERR_UNSUPPORTED) return rc;                   // (boards past 64 chunks, a TRON_ROLL_GRID override: below)
+    }
+    // everywhere else: tron_step_encode's launch with row k, and the totals tron_rollout_random's per-step form keeps
+    const size_t row = 2u * (size_t)h->P.N;
+    for (int k = 0; k < k_steps; ++k) {
+        const int rc = h->P.obs_state ? launch_obs<true>(h, actions + k * row, TRON_STEP_AUTORESET, out, st)
+                                      : launch_fmt<true>(h, obs_fmt, actions + k * row, nullptr, TRON_STEP_AUTORESET, obs, out, st);
+        if (rc != TRON_OK) return rc;
+    }
+    if (h->P.obs_state && f32 && k_steps > 0) return obs_planes(h, obs_fmt, obs, st);
+    return TRON_OK;
 }
 
 int tron_minimax_actions(tron_handle h, int32_t player, int32_t depth, int32_t mode, int8_t *out_actions,

@@ -196,6 +196,32 @@ class VecTron:
                                                     self._fmt, nat.ptr(self.obs),
                                                     nat.ptr(totals), nat.stream_ptr()), "tron_rollout_random")
 
+    def rollout_actions(self, actions, totals=None, per_step_launches=False):
+        """K steps with autoreset whose actions come from a tape: `actions` is a contiguous int8 tensor [K, N, 2] in 0..3 on
+        this env's device, row k what step(actions[k]) would take (recorded games, scripted openings, a planner's candidate
+        sequences, action repeat).  Same boards, state, observations and totals, bit for bit, as K calls of
+        step(actions[k], autoreset=True).  Mode None on the attached int8 codes runs as persistent launches of up to 64
+        steps (the launch of rollout_random, its action bytes copied from the tape); every other mode, side and format —
+        and per_step_launches=True — is one launch per step.  self.obs holds the observations of the last step once the
+        call's work completes on the stream; the tape must not be overwritten before that."""
+        if not torch.is_tensor(actions):
+            raise TypeError("rollout_actions takes an int8 tensor [K, N, 2]")
+        if actions.dtype != torch.int8:
+            raise TypeError(f"rollout_actions takes int8 actions, got {actions.dtype}")
+        if actions.dim() != 3 or tuple(actions.shape[1:]) != (self.N, 2):
+            raise ValueError(f"expected shape (K, {self.N}, 2), got {tuple(actions.shape)}")
+        if actions.device != self.device:
+            raise ValueError(f"the tape must be on {self.device}, got {actions.device}")
+        if not actions.is_contiguous():
+            raise ValueError("the tape must be contiguous")
+        if actions.shape[0] == 0:
+            return
+        flags = nat.ROLLOUT_PER_STEP if per_step_launches else 0
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.tron_rollout_actions(self._h, int(actions.shape[0]), nat.ptr(actions), flags,
+                                                     self._fmt, nat.ptr(self.obs),
+                                                     nat.ptr(totals), nat.stream_ptr()), "tron_rollout_actions")
+
     def minimax_actions(self, player, mode="voronoi", out=None, want_values=False):
         """MinimaxPlayer(2, mode).action(game.map(), player) for every env (minimax.py:284-297):
         int8 [N] actions 0..3 = UP, RIGHT, DOWN, LEFT (-1 for finished games).  With want_values

@@ -177,6 +177,25 @@ int tron_encode(tron_handle h, int32_t obs_fmt, void *obs, void *stream);
 int tron_rollout_random(tron_handle h, int32_t k_steps, uint32_t flags, int32_t obs_fmt, void *obs,
                         unsigned long long *totals, void *stream);
 
+/* K steps with autoreset, the actions taken from a tape: actions int8[k_steps][N][2] in 0..3 (device), step-major —
+ * row k is exactly the `actions` argument the k-th tron_step_encode call would take.  When the call's work completes
+ * on `stream`, everything the handle owns (boards, state words, weight / degree, counters), the attached buffer or
+ * `obs`, and `totals` (accumulated as tron_rollout_random accumulates it) are bit for bit what k_steps calls of
+ * tron_step_encode(h, actions + k * 2N, NULL, TRON_STEP_AUTORESET, ...) leave: restart positions, the weight / degree
+ * draws and the sliding modes' uniforms are keyed by (env, episode) and (env, tick), not by who chose the actions.  A
+ * byte outside 0..3 is the caller's error and is read as tron_step_encode reads it: its low two bits.  An env that is
+ * finished when a step begins (stepped without autoreset before) restarts in that step and makes no move: the step's
+ * row is not used for it.
+ * Mode None with an attached observation buffer and TRON_OBS_CODES_I8 (or TRON_OBS_NONE): persistent launches of at
+ * most TRON_ROLLOUT_CHUNK steps, the launch of tron_rollout_random with the action bytes copied from the tape (2 bytes
+ * read per env-step) — and, as there, the planes and the state words are written when a launch ends.  Everywhere else
+ * — the sliding modes, odd W, f32 planes, no attached buffer, boards of more than 64 chunks — and with
+ * TRON_ROLLOUT_PER_STEP the call is a loop over tron_step_encode's launch with row k: the same results, no new kernel.
+ * flags: 0 or TRON_ROLLOUT_PER_STEP, anything else is TRON_ERR_BAD_ARG; so are actions == NULL and k_steps < 0.
+ * k_steps == 0 launches nothing.  The tape must stay valid until the call's work has completed on `stream`.      */
+int tron_rollout_actions(tron_handle h, int32_t k_steps, const int8_t *actions, uint32_t flags,
+                         int32_t obs_fmt, void *obs, unsigned long long *totals, void *stream);
+
 /* --- state read-back (parity dumps, the scalar Game facade) --------------------
  * Replaces: Game.history[-1].map / Map.array() (map.py:60-61), PositionPlayer
  * .position/.alive (game.py:36-41), Game.winner/.done/.weight/.degree/.slide.
