@@ -42,6 +42,8 @@
 //                           (tile_step / obs_tile), each workgroup stepping its own tiles
 //   k_obs_roll_tape         tron_rollout_actions: k_obs_roll's launch (roll_resident<true>) whose helper wave copies the
 //                           action bytes from the caller's tape into the ring instead of drawing them
+//   k_obs_roll_tape_rec     tron_rollout_actions_records: k_obs_roll_tape (roll_resident<true, true>) whose game waves also
+//                           store every step's done / winner / reward into the caller's step-major record tapes
 //   k_inc                   TRON_STEP_INCREMENTAL: writes only the touched cells + restarted boards
 //   k_reset, k_obs_reset, k_obs_to_grid, k_obs_planes, k_get_state, k_encode_codes, k_pop_up, ...
 //                           resets, read-back and stateless encodes
@@ -54,7 +56,7 @@
 //   k_obs_slide, k_obs_roll_slide             lane_move<CodeCells>   the same body on player-1 code bytes, slide marks
 //   k_obs, k_obs_roll_walk                    lane_move_codes        mode None: two reads, four writes of code bytes in LDS
 //   k_inc                                     inline in the kernel   lane_move_codes' steps on code bytes in global memory
-//   k_obs_roll, k_obs_roll_tape               inline in roll_resident  the same steps on 4-bit codes in LDS, with the chunk masks
+//   k_obs_roll, k_obs_roll_tape(_rec)         inline in roll_resident  the same steps on 4-bit codes in LDS, with the chunk masks
 #include "tron_device.hpp"
 #include "tron_minimax.hpp"
 #include "../../include/tron_hip.h"
@@ -1028,9 +1030,18 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 // An env that restarts in the step it finishes in skips the move's four cell writes and its refreshes: its trail goes stale
 // by the mask as it was before the move.  st4 / rs4 are written by the epilogue as well (same bytes as one store per step
 // leaves behind).
-// Not reachable through the API today: tron_rollout_random always sets TRON_STEP_AUTORESET and passes out.totals only, so
-// the !autoreset branches and the out.done / out.winner / out.reward stores below (kept as the per-step kernels have them,
-// uniform branches) are run by no caller and no test.
+// The records.  REC (k_obs_roll_tape_rec, tron_rollout_actions_records) stores what every step computes anyway — done,
+// winner and, when out.reward is asked for, the two rewards — into the caller's step-major tapes: out.done / out.winner are
+// int8[k_steps][N], out.reward float2[k_steps][N], the launch's own first step at row 0, any of them null.  The row
+// pointers are wave-uniform and are carried forward by N per step (no multiply in the loop); a lane adds its env: per wave
+// and step 64 contiguous bytes of done, 64 of winner, 512 of reward.  The stores are fire-and-forget: the loop still loads
+// nothing from memory and waits for nothing, a null tape costs a uniform branch, a lane without an env stores nothing and the
+// helper waves store no records.  Row s is what the s-th tron_step_encode with autoreset records, an env that is finished
+// when the step begins included: done 1, its old winner, rewards 0.
+// Without REC (k_obs_roll, k_obs_roll_tape) the three stores are indexed by env alone, as the per-step kernels have them,
+// and no caller reaches them: tron_rollout_random and tron_rollout_actions pass out.totals only, and a call that asks for
+// records runs the REC instantiation.  tron_rollout_random always sets TRON_STEP_AUTORESET, and so do the tape calls: the
+// !autoreset branches below are run by no caller and no test.
 // ---- the helper wave of k_obs_roll -------------------------------------------------------------------------------------------
 // A launch's steps come in blocks of ROLL_R.  Per game wave the helper keeps two rings in LDS:
 //   actions  [2][64] x ROLL_R bytes: action_byte of step s of env `lane` is byte s % ROLL_R of slot (s / ROLL_R) & 1
@@ -1161,7 +1172,7 @@ __device__ __forceinline__ void roll_helper(const Params &P, int env, bool autor
     }
 }
 
-template <bool TAPE>
+template <bool TAPE, bool REC = false>
 __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uint32_t cpe, uint32_t flags, const StepOut &out,
                                               int k_steps, unsigned char *smem, const int8_t *tape)
 {
@@ -1272,6 +1283,9 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         __syncthreads();                                           // the boards and the helpers' block 0 are in LDS before anyone reads them
     }
     const unsigned long long mask0 = mask;                          // chunks that differ from the template IN MEMORY until the epilogue
+    // REC: the record tapes' rows of the step being played (wave-uniform; the launch's own first step is row 0)
+    int8_t *row_done = REC ? out.done : nullptr, *row_winner = REC ? out.winner : nullptr;
+    float2 *row_reward = REC ? reinterpret_cast<float2 *>(out.reward) : nullptr;
 
     for (int s = 0; s < k_steps; ++s) {
         if ((s & (ROLL_R - 1)) == 0) {
@@ -1418,7 +1432,21 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         ROLL_STAMP(2);
 
         // ---- the records and the totals
-        if (mine) {
+        if constexpr (REC) {
+            const uint32_t n = (uint32_t)P.N;                           // a row: N envs
+            if (row_done) {
+                if (mine) row_done[(uint32_t)env] = (int8_t)done;
+                row_done += n;
+            }
+            if (row_winner) {
+                if (mine) row_winner[(uint32_t)env] = (int8_t)winner;
+                row_winner += n;
+            }
+            if (row_reward) {
+                if (mine) row_reward[(uint32_t)env] = make_float2(rw0, rw1);
+                row_reward += n;
+            }
+        } else if (mine) {
             if (out.done) out.done[env] = (int8_t)done;
             if (out.winner) out.winner[env] = (int8_t)winner;
             if (out.reward) reinterpret_cast<float2 *>(out.reward)[env] = make_float2(rw0, rw1);
@@ -1564,6 +1592,17 @@ __global__ __launch_bounds__(2 * BLOCK) void k_obs_roll_tape(Params P, int E, in
     roll_resident<true>(kp, E, epw, cpe, flags, out, k_steps, smem, tape);
 }
 
+// k_obs_roll_tape with the per-step records (tron_rollout_actions_records): the third instantiation of roll_resident.  Same
+// step loop, same helper; out.done / out.winner / out.reward are step-major tapes here and point, like tape, at the launch's
+// own first step.
+__global__ __launch_bounds__(2 * BLOCK) void k_obs_roll_tape_rec(Params P, int E, int epw, uint32_t cpe, uint32_t flags, StepOut out, int k_steps,
+                                                                 const int8_t *__restrict__ tape)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    kernarg_t *kp = (kernarg_t *)__builtin_amdgcn_kernarg_segment_ptr();       // (Params is the first argument: see k_obs_roll)
+    roll_resident<true, true>(kp, E, epw, cpe, flags, out, k_steps, smem, tape);
+}
+
 // Fewer workgroups than tiles (the TRON_ROLL_GRID override): workgroup w owns tiles w, w + gridDim.x, ... and
 // every step reads its tile's state from memory and rewrites both planes (obs_tile, as k_obs).  Every
 // workgroup runs a fixed trip count, so the grid always drains.
@@ -1600,6 +1639,7 @@ static_assert(std::is_same<first_kernel_arg<decltype(&k_obs_roll)>::type, Params
               "k_obs_roll re-reads Params from kernarg offset 0: Params must stay its first parameter");
 static_assert(std::is_same<first_kernel_arg<decltype(&k_obs_roll_walk)>::type, Params>::value, "k_obs_roll_walk re-reads Params from kernarg offset 0");
 static_assert(std::is_same<first_kernel_arg<decltype(&k_obs_roll_tape)>::type, Params>::value, "k_obs_roll_tape re-reads Params from kernarg offset 0");
+static_assert(std::is_same<first_kernel_arg<decltype(&k_obs_roll_tape_rec)>::type, Params>::value, "k_obs_roll_tape_rec re-reads Params from kernarg offset 0");
 static_assert(std::is_trivially_copyable<Params>::value && alignof(Params) <= 8 && sizeof(Params) % 4 == 0,
               "Params is block-copied from the kernel-argument segment with scalar loads");
 
@@ -2485,7 +2525,8 @@ size_t roll_smem(const tron_env *h, int E, int waves)
 }
 
 // tape: null for k_obs_roll's own draws; else the caller's int8[k_steps][N][2], and every launch gets it advanced to its
-// own first step (k_obs_roll_tape: same grid, same workgroup, same LDS).
+// own first step (k_obs_roll_tape: same grid, same workgroup, same LDS).  A tape call that asks for records (any of
+// out.done / out.winner / out.reward) runs k_obs_roll_tape_rec, and its launches get the record tapes advanced by the same rows.
 int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipStream_t st, int E, int waves, int chunk,
                  const int8_t *tape = nullptr)
 {
@@ -2499,7 +2540,10 @@ int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipS
     static uint64_t prepared = 0;
     allow_big_lds(reinterpret_cast<const void *>(k_obs_roll), h->device, prepared);
     static uint64_t prepared_t = 0;
-    if (tape) allow_big_lds(reinterpret_cast<const void *>(k_obs_roll_tape), h->device, prepared_t);
+    const bool rec = tape && (out.done || out.winner || out.reward);
+    if (tape && !rec) allow_big_lds(reinterpret_cast<const void *>(k_obs_roll_tape), h->device, prepared_t);
+    static uint64_t prepared_r = 0;
+    if (rec) allow_big_lds(reinterpret_cast<const void *>(k_obs_roll_tape_rec), h->device, prepared_r);
     static bool report = getenv("TRON_ROLL_REPORT") != nullptr;         // the launch shape and its occupancy on stderr, once per process
     if (report) {
         report = false;
@@ -2512,7 +2556,13 @@ int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipS
         (void)hipGetLastError();
     }
     for (int left = k_steps; left > 0; left -= chunk) {
-        if (tape)
+        if (rec) {
+            const size_t at = (size_t)(k_steps - left) * (size_t)h->P.N;   // the launch's first row, in envs
+            const StepOut rows{out.done ? out.done + at : nullptr, out.winner ? out.winner + at : nullptr,
+                               out.reward ? out.reward + 2u * at : nullptr, out.totals};
+            hipLaunchKernelGGL(k_obs_roll_tape_rec, dim3(grid), dim3(2 * waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, rows,
+                               left < chunk ? left : chunk, tape + 2u * at);
+        } else if (tape)
             hipLaunchKernelGGL(k_obs_roll_tape, dim3(grid), dim3(2 * waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, out,
                                left < chunk ? left : chunk, tape + (size_t)(k_steps - left) * 2u * (size_t)h->P.N);
         else
@@ -2659,12 +2709,20 @@ int tron_rollout_random(tron_handle h, int32_t k_steps, uint32_t flags, int32_t 
 int tron_rollout_actions(tron_handle h, int32_t k_steps, const int8_t *actions, uint32_t flags, int32_t obs_fmt, void *obs,
                          unsigned long long *totals, void *stream)
 {
+    return tron_rollout_actions_records(h, k_steps, actions, flags, obs_fmt, obs, nullptr, nullptr, nullptr, totals, stream);
+}
+
+int tron_rollout_actions_records(tron_handle h, int32_t k_steps, const int8_t *actions, uint32_t flags, int32_t obs_fmt, void *obs,
+                                 int8_t *out_done, int8_t *out_winner, float *out_reward, unsigned long long *totals, void *stream)
+{
     if (bad_handle(h)) return h ? TRON_ERR_NO_DEVICE : TRON_ERR_BAD_ARG;
     if (!actions || k_steps < 0 || (obs_fmt != TRON_OBS_NONE) != (obs != nullptr)) return TRON_ERR_BAD_ARG;
     if (flags & ~TRON_ROLLOUT_PER_STEP) return TRON_ERR_BAD_ARG;    // autoreset is implied; a tape has no policy to flag
     if (obs_fmt < TRON_OBS_NONE || obs_fmt > TRON_OBS_PLANES4_F32) return TRON_ERR_BAD_ARG;
     if (h->P.obs_state && obs_fmt == TRON_OBS_CODES_I8 && obs != h->P.obs_state) return TRON_ERR_BAD_ARG;
-    StepOut out{nullptr, nullptr, nullptr, totals};
+    if (reinterpret_cast<uintptr_t>(out_reward) & 7u) return TRON_ERR_BAD_ARG;   // a row is float2 stores
+    // the record tapes (any of them null): k_obs_roll_tape_rec in the persistent launches, row k to step k below
+    StepOut out{out_done, out_winner, out_reward, totals};
     hipStream_t st = S_(stream);
     const bool f32 = obs_fmt == TRON_OBS_PLANES3_F32 || obs_fmt == TRON_OBS_PLANES4_F32;
     // the persistent launches: mode None on the attached codes (k_obs_roll_tape); a single step is one per-step launch
@@ -2673,11 +2731,14 @@ int tron_rollout_actions(tron_handle h, int32_t k_steps, const int8_t *actions, 
         if (rc != TRON_ERR_UNSUPPORTED) return rc;                   // (boards past 64 chunks, a TRON_ROLL_GRID override: below)
     }
     // everywhere else: tron_step_encode's launch with row k, and the totals tron_rollout_random's per-step form keeps
-    const size_t row = 2u * (size_t)h->P.N;
+    const size_t row = 2u * (size_t)h->P.N, n = (size_t)h->P.N;
     for (int k = 0; k < k_steps; ++k) {
         const int rc = h->P.obs_state ? launch_obs<true>(h, actions + k * row, TRON_STEP_AUTORESET, out, st)
                                       : launch_fmt<true>(h, obs_fmt, actions + k * row, nullptr, TRON_STEP_AUTORESET, obs, out, st);
         if (rc != TRON_OK) return rc;
+        if (out.done) out.done += n;
+        if (out.winner) out.winner += n;
+        if (out.reward) out.reward += 2u * n;
     }
     if (h->P.obs_state && f32 && k_steps > 0) return obs_planes(h, obs_fmt, obs, st);
     return TRON_OK;

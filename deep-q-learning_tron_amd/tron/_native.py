@@ -45,6 +45,7 @@ SIGNATURES = {
     "tron_encode": (C.c_int, [_vp, _i32, _vp, _vp]),
     "tron_rollout_random": (C.c_int, [_vp, _i32, _u32, _i32, _vp, _vp, _vp]),
     "tron_rollout_actions": (C.c_int, [_vp, _i32, _vp, _u32, _i32, _vp, _vp, _vp]),
+    "tron_rollout_actions_records": (C.c_int, [_vp, _i32, _vp, _u32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tron_get_grid": (C.c_int, [_vp, _vp, _vp]),
     "tron_get_state": (C.c_int, [_vp] + [_vp] * 10),
     "tron_encode_codes": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp]),

@@ -196,14 +196,21 @@ class VecTron:
                                                     self._fmt, nat.ptr(self.obs),
                                                     nat.ptr(totals), nat.stream_ptr()), "tron_rollout_random")
 
-    def rollout_actions(self, actions, totals=None, per_step_launches=False):
+    def rollout_actions(self, actions, totals=None, per_step_launches=False, records=None):
         """K steps with autoreset whose actions come from a tape: `actions` is a contiguous int8 tensor [K, N, 2] in 0..3 on
         this env's device, row k what step(actions[k]) would take (recorded games, scripted openings, a planner's candidate
         sequences, action repeat).  Same boards, state, observations and totals, bit for bit, as K calls of
         step(actions[k], autoreset=True).  Mode None on the attached int8 codes runs as persistent launches of up to 64
         steps (the launch of rollout_random, its action bytes copied from the tape); every other mode, side and format —
         and per_step_launches=True — is one launch per step.  self.obs holds the observations of the last step once the
-        call's work completes on the stream; the tape must not be overwritten before that."""
+        call's work completes on the stream; the tape must not be overwritten before that.
+        records: None (nothing is recorded and None is returned), True, or a tuple (reward, done, winner) in the order of
+        step()'s tuple.  True allocates and returns the step-major record tapes reward f32 [K, N, 2], done int8 [K, N],
+        winner int8 [K, N]: row k is what step(actions[k]) returns as (reward, done, winner), for every env — when it
+        finished, who won, what the step paid.  A tuple takes the caller's contiguous tensors of those dtypes and shapes
+        on this device, any of them None (not recorded), and is returned as it is.  The persistent launches store the
+        records as they step (tron_rollout_actions_records); the tensors hold them once the call's work completes on the
+        stream."""
         if not torch.is_tensor(actions):
             raise TypeError("rollout_actions takes an int8 tensor [K, N, 2]")
         if actions.dtype != torch.int8:
@@ -214,13 +221,48 @@ class VecTron:
             raise ValueError(f"the tape must be on {self.device}, got {actions.device}")
         if not actions.is_contiguous():
             raise ValueError("the tape must be contiguous")
-        if actions.shape[0] == 0:
-            return
+        K = int(actions.shape[0])
+        if records is not None:
+            records = self._record_tapes(records, K)
+        if K == 0:
+            return records
         flags = nat.ROLLOUT_PER_STEP if per_step_launches else 0
         with torch.cuda.device(self.device):
-            nat.check(self._lib.tron_rollout_actions(self._h, int(actions.shape[0]), nat.ptr(actions), flags,
-                                                     self._fmt, nat.ptr(self.obs),
-                                                     nat.ptr(totals), nat.stream_ptr()), "tron_rollout_actions")
+            if records is None:
+                nat.check(self._lib.tron_rollout_actions(self._h, K, nat.ptr(actions), flags,
+                                                         self._fmt, nat.ptr(self.obs),
+                                                         nat.ptr(totals), nat.stream_ptr()), "tron_rollout_actions")
+            else:
+                reward, done, winner = records
+                nat.check(self._lib.tron_rollout_actions_records(self._h, K, nat.ptr(actions), flags,
+                                                                 self._fmt, nat.ptr(self.obs), nat.ptr(done),
+                                                                 nat.ptr(winner), nat.ptr(reward),
+                                                                 nat.ptr(totals), nat.stream_ptr()),
+                          "tron_rollout_actions_records")
+        return records
+
+    def _record_tapes(self, records, K):
+        """rollout_actions' records argument as a checked tuple (reward, done, winner)."""
+        spec = (("reward", torch.float32, (K, self.N, 2)), ("done", torch.int8, (K, self.N)),
+                ("winner", torch.int8, (K, self.N)))
+        if records is True:
+            return tuple(torch.empty(shape, dtype=dtype, device=self.device) for _, dtype, shape in spec)
+        if not isinstance(records, (tuple, list)) or len(records) != 3:
+            raise TypeError("records is None, True or a tuple (reward, done, winner)")
+        for t, (name, dtype, shape) in zip(records, spec):
+            if t is None:
+                continue
+            if not torch.is_tensor(t):
+                raise TypeError(f"the {name} records take a {dtype} tensor {shape} or None")
+            if t.dtype != dtype:
+                raise TypeError(f"the {name} records are {dtype}, got {t.dtype}")
+            if tuple(t.shape) != shape:
+                raise ValueError(f"expected {name} records of shape {shape}, got {tuple(t.shape)}")
+            if t.device != self.device:
+                raise ValueError(f"the {name} records must be on {self.device}, got {t.device}")
+            if not t.is_contiguous():
+                raise ValueError(f"the {name} records must be contiguous")
+        return records
 
     def minimax_actions(self, player, mode="voronoi", out=None, want_values=False):
         """MinimaxPlayer(2, mode).action(game.map(), player) for every env (minimax.py:284-297):

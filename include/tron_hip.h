@@ -196,6 +196,29 @@ int tron_rollout_random(tron_handle h, int32_t k_steps, uint32_t flags, int32_t 
 int tron_rollout_actions(tron_handle h, int32_t k_steps, const int8_t *actions, uint32_t flags,
                          int32_t obs_fmt, void *obs, unsigned long long *totals, void *stream);
 
+/* tron_rollout_actions that also records every step: when each env finished, who won, what the step paid.  The three
+ * record tapes are step-major device buffers — out_done int8[k_steps][N], out_winner int8[k_steps][N], out_reward
+ * float[k_steps][N][2] — and row k of each holds, bit for bit, what the k-th call of
+ * tron_step_encode(h, actions + k * 2N, NULL, TRON_STEP_AUTORESET, ..., out_done, out_winner, out_reward, ...) writes
+ * to its three outputs: done 1 in the step an env finishes in (autoreset restarts it in that same step), the winner
+ * (0 draw, 1, 2) and the two players' rewards under tron_set_reward's table.  That includes an env that is already
+ * finished when a step begins: it restarts without a move, and its row holds what the per-step kernel records for it
+ * (done 1, the finished game's winner, rewards 0).
+ * Everything else is exactly tron_rollout_actions: the handle's state, the attached buffer or `obs`, `totals`, flags
+ * 0 or TRON_ROLLOUT_PER_STEP, the errors.  Any subset of the three record pointers may be NULL; with all three NULL
+ * the call IS tron_rollout_actions.  Nothing outside rows [0, k_steps) and columns [0, N) of a record tape is written,
+ * and k_steps == 0 writes nothing.  An out_reward that is not 8-byte aligned is TRON_ERR_BAD_ARG.
+ * Where tron_rollout_actions runs persistent launches, this call runs them too (k_obs_roll_tape_rec: the same launch,
+ * whose steps also store 10 bytes per env-step of records, each launch's rows behind the launch before it); where it
+ * loops over tron_step_encode's launch, so does this one, with the three pointers advanced by a row per step.
+ * The record tapes, like the action tape, must stay valid until the call's work has completed on `stream`.        */
+int tron_rollout_actions_records(tron_handle h, int32_t k_steps, const int8_t *actions, uint32_t flags,
+                                 int32_t obs_fmt, void *obs,
+                                 int8_t *out_done,    /* int8[k_steps][N]   or NULL */
+                                 int8_t *out_winner,  /* int8[k_steps][N]   or NULL */
+                                 float *out_reward,   /* f32[k_steps][N][2] or NULL, 8-byte aligned */
+                                 unsigned long long *totals, void *stream);
+
 /* --- state read-back (parity dumps, the scalar Game facade) --------------------
  * Replaces: Game.history[-1].map / Map.array() (map.py:60-61), PositionPlayer
  * .position/.alive (game.py:36-41), Game.winner/.done/.weight/.degree/.slide.

@@ -4,13 +4,19 @@ the variants alternated so that they share the clocks:
 
   tape      VecTron.rollout_actions, 64-step launches walking a random tape that lives in HBM (2 bytes per env-step)
   per_step  the same rows through tron_step_encode, one launch per step: what a caller with its own actions had before
+  tape_rec  the tape launches with all three records (reward, done, winner: 10 bytes stored per env-step) into a resident
+            record buffer of --tape-steps rows
+  tape_dw   tape_rec without the reward tape (done and winner only: 2 bytes stored per env-step)
+  per_step_rec  the same record rows through tron_step_encode with its three outputs pointed at them, one launch per step:
+            what a caller who wanted the records had before
   rand64    tron_rollout_random, 64 steps per launch
   rand20    tron_rollout_random, 20 steps per launch
 
 A train is --steps env-steps per env, timed by the host clock between two device synchronisations; every variant is warmed
 up, then --repeats rounds run the variants one after the other.  Prints one line per variant (median, min, max over the
 rounds, G env-steps/s) and one JSON line.  TRON_HIP_LIB selects the library: with one that has no tron_rollout_actions (a
-build of an older commit, for the comparison of rand64 / rand20) the tape variant is left out and said so.
+build of an older commit, for the comparison of rand64 / rand20) the tape variant is left out and said so; with one that has
+no tron_rollout_actions_records, tape_rec, tape_dw and per_step_rec are.
 """
 import argparse
 import ctypes as C
@@ -43,8 +49,11 @@ def main():
         sys.exit("roll_actions_bench.py measures on the GPU; none here")
 
     have_tape = hasattr(C.CDLL(nat.LIB_PATH), "tron_rollout_actions")
+    have_rec = hasattr(C.CDLL(nat.LIB_PATH), "tron_rollout_actions_records")
     if not have_tape:
         nat.SIGNATURES.pop("tron_rollout_actions")               # an older library: bind what it has
+    if not have_rec:
+        nat.SIGNATURES.pop("tron_rollout_actions_records")
     N = a.envs
     env = tv.VecTron(N, a.width, seed=0x5EED, rank=0, obs_format="codes")
     assert env.obs_is_state
@@ -55,6 +64,31 @@ def main():
     base = tape.data_ptr()
     step_args = [(h, C.c_void_p(base + k * row_bytes), None, nat.STEP_AUTORESET, env._fmt, nat.ptr(env.obs), nat.ptr(env.done),
                   nat.ptr(env.winner), nat.ptr(env.reward), stream) for k in range(a.tape_steps)]
+
+    if have_rec:                                                 # the resident record tapes, row k beside the tape's row k
+        rec = (torch.empty(a.tape_steps, N, 2, dtype=torch.float32, device="cuda"),
+               torch.empty(a.tape_steps, N, dtype=torch.int8, device="cuda"),
+               torch.empty(a.tape_steps, N, dtype=torch.int8, device="cuda"))
+        step_rec_args = [(h, C.c_void_p(base + k * row_bytes), None, nat.STEP_AUTORESET, env._fmt, nat.ptr(env.obs),
+                          C.c_void_p(rec[1].data_ptr() + k * N), C.c_void_p(rec[2].data_ptr() + k * N),
+                          C.c_void_p(rec[0].data_ptr() + k * 8 * N), stream) for k in range(a.tape_steps)]
+
+    def run_tape_rec(steps):
+        for j in range(steps // 64):
+            r = (j * 64) % a.tape_steps
+            env.rollout_actions(tape[r:r + 64], records=(rec[0][r:r + 64], rec[1][r:r + 64], rec[2][r:r + 64]))
+
+    def run_tape_dw(steps):
+        for j in range(steps // 64):
+            r = (j * 64) % a.tape_steps
+            env.rollout_actions(tape[r:r + 64], records=(None, rec[1][r:r + 64], rec[2][r:r + 64]))
+
+    def run_per_step_rec(steps):
+        fn = lib.tron_step_encode
+        for k in range(steps):
+            rc = fn(*step_rec_args[k % a.tape_steps])
+            if rc:
+                nat.check(rc, "tron_step_encode")
 
     def run_tape(steps):
         for j in range(steps // 64):
@@ -75,7 +109,10 @@ def main():
         return run
 
     variants = [("tape", run_tape)] if have_tape else []
-    variants += [("per_step", run_per_step), ("rand64", run_random(64)), ("rand20", run_random(20))]
+    variants += [("per_step", run_per_step)]
+    if have_rec:
+        variants += [("tape_rec", run_tape_rec), ("tape_dw", run_tape_dw), ("per_step_rec", run_per_step_rec)]
+    variants += [("rand64", run_random(64)), ("rand20", run_random(20))]
     for _, fn in variants:
         fn(320 * a.warmup)
     torch.cuda.synchronize()
@@ -91,9 +128,11 @@ def main():
           f"trains of {a.steps} steps, {a.repeats} rounds, G env-steps/s: median [min max]")
     if not have_tape:
         print("  tape      not in this library")
+    if not have_rec:
+        print("  tape_rec, tape_dw, per_step_rec  not in this library (no tron_rollout_actions_records)")
     for name, _ in variants:
         r = [x / 1e9 for x in rates[name]]
-        print(f"  {name:9s} {statistics.median(r):7.3f} [{min(r):7.3f} {max(r):7.3f}]", flush=True)
+        print(f"  {name:12s} {statistics.median(r):7.3f} [{min(r):7.3f} {max(r):7.3f}]", flush=True)
     print(json.dumps({"lib": nat.LIB_PATH, "envs": N, "width": a.width, "steps": a.steps, "rates": rates}))
     env.close()
 
