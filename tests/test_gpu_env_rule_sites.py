@@ -11,6 +11,8 @@ on nothing."""
 import numpy as np
 import pytest
 
+from rollout_support import Ref, check_against_oracle, gpu_modules, new_totals, np_, pull
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
@@ -58,15 +60,8 @@ def oracle_run(oracle, mode):
 
 @pytest.fixture(scope="module")
 def T():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import tron.vec as tv
-    import oracle
+    tv, oracle = gpu_modules()
     return tv, oracle, {mode: oracle_run(oracle, mode) for mode in (None, "ice", "temper")}
-
-
-def np_(t):
-    return t.detach().cpu().numpy()
 
 
 def read_back(env, r, d, w):
@@ -126,22 +121,10 @@ def test_rollout_in_one_launch(T, mode, resident):
     env = tv.VecTron(N, W, mode=mode, seed=SEED, rank=RANK, obs_format="codes", reward=REWARD, slide=SLIDE)
     assert env.obs_is_state
     env.reset()
-    v = oracle.VecOracle(N, W, mode=mode, seed=SEED, stream=RANK, reward=REWARD, slide=SLIDE)
-    v.reset_all()
-    want = np.zeros(4, np.int64)                  # {env_steps, p1_wins, p2_wins, draws}
+    ref = Ref(oracle, N, W, SEED, RANK, mode=mode, reward=REWARD, slide=SLIDE)
     for _ in range(STEPS):
-        _, d, w, _ = v.step(autoreset=True, want_obs=False)
-        fin = d == 1
-        want += [N, int((fin & (w == 1)).sum()), int((fin & (w == 2)).sum()), int((fin & (w == 0)).sum())]
-    assert want[1:].sum() >= 1                    # somebody restarted inside the launch
-    totals = torch.zeros(4, dtype=torch.int64, device="cuda")
+        ref.step()
+    assert ref.totals[1:].sum() >= 1              # somebody restarted inside the launch
+    totals = new_totals()                         # {env_steps, p1_wins, p2_wins, draws}
     env.rollout_random(STEPS, totals, resident=resident)
-    torch.cuda.synchronize()
-    assert np.array_equal(np_(totals), want)
-    st = env.state()
-    for k in STATE_KEYS:
-        assert np.array_equal(np_(st[k]), getattr(v, k)), k
-    assert np.array_equal(np_(st["counters"]).astype(np.uint32), np.stack([v.tick, v.episode, v.eplen], 1))
-    assert np.array_equal(np_(env.grid()).reshape(N, -1), v.grid)
-    codes = np.stack([oracle.state_for_player(v.grid, 1), oracle.state_for_player(v.grid, 2)], 1)
-    assert np.array_equal(np_(env.obs).reshape(N, 2, -1), codes)
+    check_against_oracle(pull(env, totals), ref, (mode, resident))

@@ -16,8 +16,9 @@ slots (34 to 49 times in 64 steps under these tapes; 21 to 34 times at W = 10, w
 The twin is stepped once per (mode, W, N) through the longest tape and its state kept at every K of interest: a tape of K
 steps is the first K rows of that one.  Tapes are uniform over 0..3 from a seeded torch.Generator.
 """
-import numpy as np
 import pytest
+
+from rollout_support import Ref, check_against_oracle, check_against_twin, gpu_modules, make_tape, new_totals, pull, step_counted
 
 pytestmark = pytest.mark.gpu
 
@@ -31,43 +32,18 @@ FOUR_WAVES = 16384 + 200                                         # more 64-env w
 
 @pytest.fixture(scope="module")
 def tv():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import tron.vec as tv
-    return tv
-
-
-def make_tape(N, K, salt=0, lo=0, hi=4):
-    g = torch.Generator().manual_seed(1_000_003 * N + 131 * K + salt)
-    return torch.randint(lo, hi, (K, N, 2), generator=g, dtype=torch.int64).to(torch.int8).cuda()
+    return gpu_modules()[0]
 
 
 def make(tv, N, W, mode=None, obs_format="codes"):
     env = tv.VecTron(N, W, mode=mode, seed=SEED, rank=RANK, obs_format=obs_format)
     env.reset()
-    return env, torch.zeros(4, dtype=torch.int64, device="cuda")
-
-
-def step_counted(env, totals, actions):
-    """One per-step launch with autoreset, and the totals a rollout keeps of it (every env is live when a step begins:
-    autoreset restarts a finished one in the step it finishes in)."""
-    _, _, d, w = env.step(actions, autoreset=True)
-    fin = d == 1
-    totals += torch.stack([torch.tensor(env.N, device="cuda"), (fin & (w == 1)).sum(), (fin & (w == 2)).sum(),
-                           (fin & (w == 0)).sum()])
-
-
-def pull(env, totals):
-    torch.cuda.synchronize()
-    got = dict(obs=env.obs.clone().cpu(), grid=env.grid().cpu(), totals=totals.clone().cpu())
-    got.update({k: v.cpu() for k, v in env.state().items()})
-    return got
+    return env, new_totals()
 
 
 def assert_same(got, want, tag):
-    assert set(got) == set(want) == {"obs", "grid", "totals"} | set(STATE_KEYS)
-    for k in want:
-        assert got[k].shape == want[k].shape and torch.equal(got[k], want[k]), (tag, k)
+    assert set(want) == {"obs", "grid", "totals"} | set(STATE_KEYS)
+    check_against_twin(got, want, tag)
 
 
 _TWINS = {}
@@ -123,27 +99,16 @@ def test_tape_equals_oracle(tv):
     import oracle
     N, W, K = 70, 10, 130
     tape = make_tape(N, max(KS))[:K].contiguous()
-    ref = oracle.VecOracle(N, W, seed=SEED, stream=RANK)
-    ref.reset_all()
-    want_totals = np.zeros(4, np.int64)
+    ref = Ref(oracle, N, W, SEED, RANK)
     host = tape.cpu().numpy()
     for k in range(K):
-        _, d, w, _ = ref.step(actions=host[k], autoreset=True, want_obs=False)
-        want_totals += [N, int(((d == 1) & (w == 1)).sum()), int(((d == 1) & (w == 2)).sum()), int(((d == 1) & (w == 0)).sum())]
+        ref.step(host[k])
     env, totals = make(tv, N, W)
     env.rollout_actions(tape, totals)
-    got = {k: v.numpy() for k, v in pull(env, totals).items()}
+    got = pull(env, totals)
     env.close()
-    assert np.array_equal(got["grid"].reshape(N, -1), ref.grid)
-    for k in ("pos", "alive", "dir", "done", "winner", "weight", "degree"):
-        assert np.array_equal(got[k], getattr(ref, k)), k
-    c = got["counters"].astype(np.uint32)
-    assert np.array_equal(c[:, 0], ref.tick) and np.array_equal(c[:, 1], ref.episode) and np.array_equal(c[:, 2], ref.eplen)
-    obs = got["obs"].reshape(N, 2, -1)
-    assert np.array_equal(obs[:, 0], oracle.state_for_player(ref.grid, 1))
-    assert np.array_equal(obs[:, 1], oracle.state_for_player(ref.grid, 2))
-    assert np.array_equal(got["totals"], want_totals)
-    assert int(ref.episode.min()) > 0                            # (the oracle alone) every env restarted under this tape
+    check_against_oracle(got, ref, "the oracle")
+    assert int(ref.v.episode.min()) > 0                          # (the oracle alone) every env restarted under this tape
 
 
 # ---- 3: a tape split over two calls

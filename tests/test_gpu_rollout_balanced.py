@@ -11,10 +11,10 @@ totals only).
 A wave with an empty list whose envs are all finished cannot be made through the API: tron_rollout_random always sets autoreset,
 so a finished env restarts (and stores) in the launch's first step.  The empty list that can occur is that of a wave without
 envs, in a ragged last workgroup of four waves: test_four_wave_workgroups."""
-import os
-
 import numpy as np
 import pytest
+
+from rollout_support import Ref, check_against_oracle, gpu_modules, new_totals, np_, pull, restore_threads
 
 pytestmark = pytest.mark.gpu
 
@@ -23,71 +23,27 @@ torch = pytest.importorskip("torch")
 
 @pytest.fixture(scope="module")
 def T():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import tron.vec as tv
-    import oracle
-    return tv, oracle
-
-
-def np_(t):
-    return t.detach().cpu().numpy()
-
-
-class Ref:
-    """The oracle with autoreset done by hand: per-step records as a step with autoreset reports them, and the totals."""
-
-    def __init__(self, oracle, N, W, seed, rank):
-        self.oracle = oracle
-        self.v = oracle.VecOracle(N, W, seed=seed, stream=rank)
-        self.v.reset_all()
-        self.totals = np.zeros(4, np.int64)
-        self.restarts = []                    # per step: how many envs restarted
-
-    def step(self, nonrev=False):
-        v = self.v
-        stepped = v.done == 0                 # an env that was finished before the step is not stepped, only restarted
-        _, d, w, r = v.step(None, autoreset=False, want_obs=False, nonreversing=nonrev)
-        d, w, r = d.copy(), w.copy(), r.copy()
-        fin = (d == 1) & stepped
-        self.totals += np.array([stepped.sum(), (fin & (w == 1)).sum(), (fin & (w == 2)).sum(), (fin & (w == 0)).sum()], np.int64)
-        self.restarts.append(int((d == 1).sum()))
-        if (d == 1).any():
-            v.reset_masked(d == 1)
-        return d, w, r
-
-    def obs(self):
-        g = self.v.grid
-        return np.stack([self.oracle.state_for_player(g, 1), self.oracle.state_for_player(g, 2)], 1)
+    return gpu_modules()
 
 
 def check(env, ref, tag):
-    v, N = ref.v, ref.v.N
-    torch.cuda.synchronize()
-    st = env.state()
-    assert np.array_equal(np_(env.obs).reshape(N, 2, -1), ref.obs()), tag
-    assert np.array_equal(np_(env.grid()).reshape(N, -1), v.grid), tag
-    assert np.array_equal(np_(st["pos"]), v.pos) and np.array_equal(np_(st["alive"]), v.alive), tag
-    assert np.array_equal(np_(st["dir"]), v.dir), tag
-    assert np.array_equal(np_(st["done"]), v.done) and np.array_equal(np_(st["winner"]), v.winner), tag
-    assert np.array_equal(np_(st["weight"]), v.weight) and np.array_equal(np_(st["degree"]), v.degree), tag
-    c = np_(st["counters"]).astype(np.uint32)
-    assert np.array_equal(c[:, 0], v.tick) and np.array_equal(c[:, 1], v.episode) and np.array_equal(c[:, 2], v.eplen), tag
+    """Every byte a caller can read back against the oracle."""
+    check_against_oracle(pull(env), ref, tag, totals=False)
 
 
 def rollout(env, ref, K, nonrev, tag=""):
-    totals = torch.zeros(4, dtype=torch.int64, device="cuda")
+    totals = new_totals()
     env.rollout_random(K, totals, nonreversing=nonrev)
     before = ref.totals.copy()
     for _ in range(K):
-        ref.step(nonrev)
+        ref.step(nonrev=nonrev)
     check(env, ref, f"rollout of {K} {tag}")
     assert np.array_equal(np_(totals), ref.totals - before), f"totals of the rollout of {K} {tag}"
 
 
 def single_step(env, ref, nonrev, tag=""):
     _, reward, done, winner = env.step(nonreversing=nonrev)
-    d, w, r = ref.step(nonrev)
+    d, w, r = ref.step(nonrev=nonrev)
     assert np.array_equal(np_(done), d) and np.array_equal(np_(winner), w) and np.array_equal(np_(reward), r), f"step {tag}"
 
 
@@ -114,7 +70,7 @@ def test_rollouts_and_steps(T, N, W, nonrev):
         single_step(env, ref, nonrev, tag=f"after the rollout of {K}")
     check(env, ref, "after the last step")
     if N >= 63:
-        assert max(ref.restarts) > 0, "at least one restart must have gone through the list"
+        assert max(ref.restarts_per_step) > 0, "at least one restart must have gone through the list"
 
 
 @pytest.mark.parametrize("W,N", [(4, 64), (4, 200), (6, 64), (24, 64)])
@@ -132,9 +88,9 @@ def test_every_env_of_a_wave_restarts_at_once(T, W, N):
         assert np.array_equal(np_(done), d) and np.array_equal(np_(winner), w) and np.array_equal(np_(reward), r)
     assert (ref.v.done == 1).all(), "every env must have finished before the rollout"
     check(env, ref, "all envs finished")
-    ref.restarts.clear()
+    ref.restarts_per_step.clear()
     rollout(env, ref, 2, False, tag="restarting every env")      # (two steps: one alone would be a per-step launch)
-    assert ref.restarts[0] == N
+    assert ref.restarts_per_step[0] == N
     single_step(env, ref, False)
     rollout(env, ref, 64, False, tag="after the full restart")
     single_step(env, ref, False)
@@ -144,12 +100,11 @@ def test_every_env_of_a_wave_restarts_at_once(T, W, N):
 # fit the LDS).  + 1: one lane of wave 0 and three waves without envs (empty lists); + 200: three full waves and 8 lanes.
 @pytest.mark.parametrize("N,W,Ks", [(16384 + 1, 6, (7, 2)), (16384 + 200, 6, (3,)), (16384 + 65, 30, (2,))])
 def test_four_wave_workgroups(T, N, W, Ks):
-    _, oracle = T
-    oracle.set_threads(min(16, len(os.sched_getaffinity(0))))
+    _, oracle = gpu_modules(threads=True)
     try:
         env, ref = make(T, N, W, seed=N % 1000, rank=2)
         for K in Ks:
             rollout(env, ref, K, False, tag=f"N {N} W {W}")
             single_step(env, ref, False)
     finally:
-        oracle.set_threads(1)
+        restore_threads(oracle)

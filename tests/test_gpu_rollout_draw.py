@@ -9,6 +9,8 @@ drawn one restart ahead and are not in state(): they are compared when the resta
 import numpy as np
 import pytest
 
+from rollout_support import Ref, check_against_oracle, gpu_modules, new_totals, np_, pull
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
@@ -20,21 +22,7 @@ RESET_BLOCKS = 12              # Philox blocks a start can use: 2 + 4 + 2 * 16 +
 
 @pytest.fixture(scope="module")
 def T():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import tron.vec as tv
-    import oracle
-    return tv, oracle
-
-
-def np_(t):
-    return t.detach().cpu().numpy()
-
-
-def tally(d, w, stepped):
-    fin = (d == 1) & stepped
-    return np.array([int(stepped.sum()), int((fin & (w == 1)).sum()), int((fin & (w == 2)).sum()), int((fin & (w == 0)).sum())],
-                    np.int64)
+    return gpu_modules()
 
 
 def redraws_of_start(oracle, W, fair, seed, rank, env, episode):
@@ -52,58 +40,23 @@ def redraws_of_start(oracle, W, fair, seed, rank, env, episode):
     return (n - base) // 2
 
 
-class Ref:
-    """The oracle with autoreset done by hand, counting the restarts whose start was redrawn."""
-
-    def __init__(self, oracle, N, W, seed, rank, fair=False, count=False):
-        self.oracle, self.W, self.fair, self.seed, self.rank, self.count = oracle, W, fair, seed & 0xFFFFFFFF, rank, count
-        self.v = oracle.VecOracle(N, W, seed=seed, stream=rank, fair=fair)
-        self.v.reset_all()
-        self.totals = np.zeros(4, np.int64)
-        self.restarts = self.redrew_once = self.redrew_twice = 0
-
-    def step(self, actions=None):
-        """One step with autoreset; returns done / winner / reward as a step with autoreset reports them."""
-        v = self.v
-        was_done = v.done == 1               # finished before the step: not stepped, restarted by the autoreset
-        _, d, w, r = v.step(actions, autoreset=False, want_obs=False)
-        d, w, r = d.copy(), w.copy(), r.copy()
-        self.totals += tally(d, w, ~was_done)
-        fin = d == 1
-        if fin.any():
-            if self.count:
-                for i in np.flatnonzero(fin):
-                    n = redraws_of_start(self.oracle, self.W, self.fair, self.seed, self.rank, int(i), int(v.episode[i]))
-                    self.restarts += 1
-                    self.redrew_once += n >= 1
-                    self.redrew_twice += n >= 2
-            v.reset_masked(fin)
-        return d, w, r
-
-    def obs(self):
-        g = self.v.grid
-        return np.stack([self.oracle.state_for_player(g, 1), self.oracle.state_for_player(g, 2)], 1)
+def count_redraws(ref, fin):
+    """Ref's look at the finished envs before they restart: counts the restarts whose start was redrawn."""
+    for i in np.flatnonzero(fin):
+        n = redraws_of_start(ref.oracle, ref.W, ref.fair, ref.seed, ref.rank, int(i), int(ref.v.episode[i]))
+        ref.restarts += 1
+        ref.redrew_once += n >= 1
+        ref.redrew_twice += n >= 2
 
 
 def check(env, ref, tag):
     """Every byte a caller can read back against the oracle."""
-    v, N = ref.v, ref.v.N
-    torch.cuda.synchronize()
-    st = env.state()
-    assert np.array_equal(np_(env.obs).reshape(N, 2, -1), ref.obs()), tag
-    assert np.array_equal(np_(env.grid()).reshape(N, -1), v.grid), tag
-    assert np.array_equal(np_(st["pos"]), v.pos) and np.array_equal(np_(st["alive"]), v.alive), tag
-    assert np.array_equal(np_(st["dir"]), v.dir), tag
-    assert np.array_equal(np_(st["done"]), v.done) and np.array_equal(np_(st["winner"]), v.winner), tag
-    assert np.array_equal(np_(st["weight"]), v.weight) and np.array_equal(np_(st["degree"]), v.degree), tag
-    c = np_(st["counters"]).astype(np.uint32)
-    assert np.array_equal(c[:, 0], v.tick) and np.array_equal(c[:, 1], v.episode), tag
-    assert np.array_equal(c[:, 2], v.eplen), tag
+    check_against_oracle(pull(env), ref, tag, totals=False)
 
 
 def rollout(env, ref, K, tag=""):
     """K steps both ways; the rollout's totals against the oracle's."""
-    totals = torch.zeros(4, dtype=torch.int64, device="cuda")
+    totals = new_totals()
     env.rollout_random(K, totals)
     before = ref.totals.copy()
     for _ in range(K):
@@ -117,7 +70,9 @@ def make(T, N, W, seed, rank, fair=False, count=False):
     env = tv.VecTron(N, W, fair=fair, seed=seed, rank=rank, obs_format="codes")
     assert env.obs_is_state
     env.reset()
-    return env, Ref(oracle, N, W, seed, rank, fair, count)
+    ref = Ref(oracle, N, W, seed, rank, fair=fair, before_restart=count_redraws if count else None)
+    ref.restarts = ref.redrew_once = ref.redrew_twice = 0
+    return env, ref
 
 
 # Seeds for W = 4, fair=False, checked on the CPU with the oracle alone (the 133 steps of the test, this file's Ref): restarts

@@ -21,17 +21,17 @@ consumed in step 0), and one begins its launches with trails in memory (per-step
 
 test_inputs_reach_the_cases asserts, from the oracle alone, that these inputs reach the cases they are there for.
 """
-import os
-
 import numpy as np
 import pytest
+
+from rollout_support import Ref, apply, check_against_oracle, check_against_twin, gpu_modules, new_totals, pull, \
+    restore_threads
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 R = 8                                                            # steps per block of the helper (ROLL_R)
-LAUNCH = 64                                                      # steps per persistent launch (TRON_ROLLOUT_CHUNK)
 SPLIT = 40                                                       # see the docstring
 STEPS = (1, 7, 8, 9, 15, 16, 17, 24, 25, 63, 64, 65, 130)
 SMALL = (1, SPLIT - 1, SPLIT, SPLIT + 1, 63, 64, 65, 130, 257)
@@ -40,7 +40,6 @@ CASES = [(4, False), (10, False), (24, False), (30, False), (4, True), (10, True
 LARGE_CASES = [(24, False), (30, False), (4, True)]
 SEED, RANK = 0x70B0, 2
 FOLLOW_MAX = 64                                                  # per-step launches after a sequence, at the most
-STATE_KEYS = ("pos", "alive", "dir", "done", "winner", "weight", "degree", "counters")
 ROLLS = [("roll", k) for k in STEPS]
 FINISHED = [("steps_noreset", 5), ("roll", 2 * R + 1), ("steps_noreset", 3), ("roll", 65), ("steps_noreset", 2), ("roll", 1),
             ("roll", R + 1)]
@@ -49,86 +48,20 @@ TRAILS = [("steps", 6), ("roll", 9), ("steps", 3), ("roll", 17), ("roll", 65)]
 
 @pytest.fixture(scope="module")
 def T():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import tron.vec as tv
-    import oracle
-    oracle.set_threads(min(16, len(os.sched_getaffinity(0))))
+    tv, oracle = gpu_modules(threads=True)
     yield tv, oracle
-    oracle.set_threads(1)
+    restore_threads(oracle)
 
 
-def np_(t):
-    return t.detach().cpu().numpy()
-
-
-class Ref:
-    """The oracle stepped through a sequence, with what the conditions on the inputs need: per launch the episode
-    counters around it, which envs restarted in which step, and the chunks of the player-1 plane that differ from the
-    fresh board when the launch begins."""
-
-    def __init__(self, oracle, N, W, fair):
-        self.oracle, self.N, self.W, self.fair = oracle, N, W, fair
-        self.v = oracle.VecOracle(N, W, seed=SEED, stream=RANK, fair=fair)
-        self.v.reset_all()
-        self.totals = np.zeros(4, np.int64)
-        self.launches = []                                       # per launch: ([N] episode before, [k, N] restarted in step s, [N] chunks)
-        self.entered_done = 0                                    # envs that were finished when a launch began
-
-    def step(self, nonrev, autoreset=True, count=True):
-        v = self.v
-        was_done = v.done == 1
-        _, d, w, _ = v.step(autoreset=autoreset, want_obs=False, nonreversing=nonrev)
-        if count:                                                # (a finished env restarts without stepping: not counted)
-            stepped = ~was_done
-            self.totals += [int(stepped.sum()), int((stepped & (d == 1) & (w == 1)).sum()),
-                            int((stepped & (d == 1) & (w == 2)).sum()), int((stepped & (d == 1) & (w == 0)).sum())]
-
-    def mask_chunks(self):
-        """Per env the 16-cell chunks of the player-1 plane that are not the fresh board's (border -1, inside 1)."""
-        p1 = self.oracle.state_for_player(self.v.grid, 1).reshape(self.N, -1)
-        fresh = np.where(p1 == -1, -1, 1)
-        diff = p1 != fresh
-        pad = (-diff.shape[1]) % 16
-        diff = np.pad(diff, ((0, 0), (0, pad)))
-        return diff.reshape(self.N, -1, 16).any(2).sum(1)
-
-    def roll(self, K, nonrev):
-        left = K
-        while left:
-            k = min(left, LAUNCH)
-            before = self.v.episode.copy()
-            chunks = self.mask_chunks()
-            self.entered_done += int((self.v.done == 1).sum())
-            hit = np.zeros((k, self.N), bool)
-            for s in range(k):
-                ep = self.v.episode.copy()
-                self.step(nonrev)
-                hit[s] = self.v.episode != ep
-            self.launches.append((before, hit, chunks))
-            left -= k
-
-    def apply(self, op, nonrev):
-        if op[0] == "roll":
-            self.roll(op[1], nonrev)
-        else:
-            for _ in range(op[1]):
-                self.step(nonrev, autoreset=op[0] == "steps", count=False)
-
-    def obs(self):
-        g = self.v.grid
-        return np.stack([self.oracle.state_for_player(g, 1), self.oracle.state_for_player(g, 2)], 1)
-
-    def clashes(self, envs=16):
-        """Restarts inside the launches, among the first `envs` envs, whose make_game clashes."""
-        nd = 9 if self.fair else 7                               # draws of a game without a clash
-        n = 0
-        for before, hit, _ in self.launches:
-            for e in range(min(envs, self.N)):
-                for ep in range(int(before[e]) + 1, int(before[e]) + int(hit[:, e].sum()) + 1):
-                    words = np.concatenate([self.oracle.philox([e, ep, 2, b], [SEED, RANK]) for b in range(12)])
-                    n += self.oracle.make_game(self.W, self.fair, words)[3] > nd
-        return n
+def mask_chunks(ref):
+    """Per env the 16-cell chunks of the player-1 plane that are not the fresh board's (border -1, inside 1): logged at
+    every launch's entry (Ref.launch_notes)."""
+    p1 = ref.oracle.state_for_player(ref.v.grid, 1).reshape(ref.N, -1)
+    fresh = np.where(p1 == -1, -1, 1)
+    diff = p1 != fresh
+    pad = (-diff.shape[1]) % 16
+    diff = np.pad(diff, ((0, 0), (0, pad)))
+    return diff.reshape(ref.N, -1, 16).any(2).sum(1)
 
 
 def consumed(hit):
@@ -153,50 +86,16 @@ def topups(hit):
     return np.stack(out, 0) if out else np.zeros((0, hit.shape[1]), np.int64)
 
 
-def apply(env, totals, op, nonrev, per_step):
-    if op[0] == "roll":
-        env.rollout_random(op[1], totals, nonreversing=nonrev, per_step_launches=per_step)
-    else:
-        for _ in range(op[1]):
-            env.step(autoreset=op[0] == "steps", nonreversing=nonrev)
-
-
-def pull(env, totals):
-    torch.cuda.synchronize()
-    got = dict(obs=np_(env.obs).reshape(env.N, 2, -1).copy(), grid=np_(env.grid()).reshape(env.N, -1),
-               totals=np_(totals).copy())
-    got.update({k: np_(v) for k, v in env.state().items()})
-    return got
-
-
-def check_against_oracle(got, ref, tag):
-    v = ref.v
-    assert np.array_equal(got["obs"], ref.obs()), (tag, "obs")
-    assert np.array_equal(got["grid"], v.grid), (tag, "grid")
-    for k in ("pos", "alive", "dir", "done", "winner", "weight", "degree"):
-        assert np.array_equal(got[k], getattr(v, k)), (tag, k)
-    assert np.array_equal(got["totals"], ref.totals), (tag, "totals")
-    c = got["counters"].astype(np.uint32)
-    assert np.array_equal(c[:, 0], v.tick), (tag, "tick")
-    assert np.array_equal(c[:, 1], v.episode), (tag, "episode")
-    assert np.array_equal(c[:, 2], v.eplen), (tag, "eplen")
-
-
-def check_against_twin(got, twin, tag):
-    for k in ("obs", "grid", "totals") + STATE_KEYS:
-        assert np.array_equal(got[k], twin[k]), (tag, k)
-
-
 def make(tv, N, W, fair):
     env = tv.VecTron(N, W, seed=SEED, rank=RANK, obs_format="codes", fair=fair)
     assert env.obs_is_state
     env.reset()
-    return env, torch.zeros(4, dtype=torch.int64, device="cuda")
+    return env, new_totals()
 
 
 def run_sequence(T, N, W, fair, nonrev, ops):
     tv, oracle = T
-    ref = Ref(oracle, N, W, fair)
+    ref = Ref(oracle, N, W, SEED, RANK, fair=fair, at_launch=mask_chunks)
     env, totals = make(tv, N, W, fair)
     twin, ttot = make(tv, N, W, fair)
     for i, op in enumerate(ops):
@@ -212,7 +111,7 @@ def run_sequence(T, N, W, fair, nonrev, ops):
     for j in range(FOLLOW_MAX):
         if (ref.v.episode != seen).all():
             break
-        ref.step(False, count=False)
+        ref.step(count=False)
         env.step()
         twin.step()
         check_against_oracle(pull(env, totals), ref, (N, W, fair, nonrev, "follow", j))
@@ -228,7 +127,7 @@ def run_sequence(T, N, W, fair, nonrev, ops):
 @pytest.mark.parametrize("W,fair", CASES)
 def test_one_game_wave_per_workgroup(T, W, fair, N, nonrev):
     ref = run_sequence(T, N, W, fair, nonrev, ROLLS)
-    assert sum(int(hit.sum()) for _, hit, _ in ref.launches) > N  # games ended and restarted inside the launches
+    assert sum(int(hit.sum()) for _, hit in ref.launches) > N  # games ended and restarted inside the launches
 
 
 @pytest.mark.parametrize("nonrev", [False, True])
@@ -251,11 +150,11 @@ def test_launches_entered_with_finished_envs(T, W, fair, nonrev):
 def test_launches_begin_with_trails_in_memory(T, W, fair, nonrev):
     ref = run_sequence(T, 130, W, fair, nonrev, TRAILS)
     # (the oracle alone) masks of more than two chunks at a launch's entry; a 4x4 game's board is three chunks in all
-    assert max(int(chunks.max()) for _, _, chunks in ref.launches) > (2 if W > 4 else 1)
+    assert max(int(chunks.max()) for chunks in ref.launch_notes) > (2 if W > 4 else 1)
 
 
 def oracle_only(oracle, N, W, fair, nonrev, ops):
-    ref = Ref(oracle, N, W, fair)
+    ref = Ref(oracle, N, W, SEED, RANK, fair=fair, at_launch=mask_chunks)
     for op in ops:
         ref.apply(op, nonrev)
     return ref
@@ -272,14 +171,14 @@ def reached(oracle):
     # 16 384 envs x 64 steps at 24x24).  Rare even so: the 16 384 + 1 envs of the four-wave shape (side 4, `fair`) reach it.
     ref4l = oracle_only(oracle, LARGE[0], 4, True, False, ROLLS)
     n = 0
-    for _, hit, _ in ref4l.launches:
+    for _, hit in ref4l.launches:
         cons = consumed(hit)
         n += int(((cons[:-1] == R) & (cons[1:] == 0)).sum())
     out["R restarts in a block, then a block with none (side 4, fair, 16 385 envs)"] = n
     # two lanes of one wave whose consumption in one block differs by at least 4
     for name, ref in (("side 4", ref4), ("side 24", ref24)):
         n = 0
-        for _, hit, _ in ref.launches:
+        for _, hit in ref.launches:
             cons = consumed(hit)
             for w0 in range(0, 130, 64):
                 cw = cons[:, w0:w0 + 64]
@@ -287,19 +186,19 @@ def reached(oracle):
         out[f"wave-blocks whose lanes' consumption differs by >= 4 ({name})"] = n
     # top-ups past block 0 (drawn during block b >= 1) of 0 and of R
     for name, ref in (("side 4", ref4), ("side 24", ref24)):
-        t = [topups(hit)[1:] for _, hit, _ in ref.launches if len(hit) > 2 * R]
+        t = [topups(hit)[1:] for _, hit in ref.launches if len(hit) > 2 * R]
         out[f"top-ups of 0 past block 0 ({name})"] = sum(int((x == 0).sum()) for x in t)
         if ref is ref4:                                          # (at 24x24 no env restarts R times in one block)
             out[f"top-ups of R past block 0 ({name})"] = sum(int((x == R).sum()) for x in t)
         out[f"partial top-ups past block 0, 1..R-1 ({name})"] = sum(int(((x > 0) & (x < R)).sum()) for x in t)
     for fair in (False, True):
         ref = ref4 if not fair else oracle_only(oracle, 130, 4, True, False, ROLLS)
-        out[f"clashing starts among the first 16 envs (side 4, fair={fair})"] = ref.clashes()
+        out[f"clashing starts among the first 16 envs (side 4, fair={fair})"] = ref.clashes()[0]
     # an env of the upper lanes of a wave (SPLIT and above) whose mask at launch entry has more than two chunks
     for name, ref in (("side 24, rollouts only", ref24), ("side 24, per-step launches first", oracle_only(oracle, 130, 24, False, False, TRAILS))):
         upper = (np.arange(130) % 64) >= SPLIT
         out[f"env-launches of the upper lanes entered with more than two chunks in the mask ({name})"] = \
-            sum(int((chunks[upper] > 2).sum()) for _, _, chunks in ref.launches)
+            sum(int((chunks[upper] > 2).sum()) for chunks in ref.launch_notes)
     out["env-launches entered finished (side 24)"] = oracle_only(oracle, 130, 24, False, False, FINISHED).entered_done
     return out
 

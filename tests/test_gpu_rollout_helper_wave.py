@@ -19,17 +19,17 @@ behind the others from then on.
 
 test_inputs_reach_the_cases asserts, from the oracle alone, that these inputs reach the cases they are there for.
 """
-import os
-
 import numpy as np
 import pytest
+
+from rollout_support import Ref, apply, check_against_oracle, check_against_twin, gpu_modules, new_totals, pull, \
+    restore_threads
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 R = 8                                                            # steps per block of the helper (ROLL_R)
-LAUNCH = 64                                                      # steps per persistent launch (TRON_ROLLOUT_CHUNK)
 STEPS = (1, R - 1, R, R + 1, 2 * R, 2 * R + 1, 63, 64, 65, 130)
 SMALL = (1, 63, 64, 65, 130, 257)
 LARGE = (16384 + 1, 16384 + 200)
@@ -37,7 +37,6 @@ CASES = [(4, False), (10, False), (24, False), (30, False), (4, True), (10, True
 LARGE_CASES = [(24, False), (30, False), (4, True)]
 SEED, RANK = 0xB10C, 1
 FOLLOW_MAX = 64                                                  # per-step launches after a sequence, at the most
-STATE_KEYS = ("pos", "alive", "dir", "done", "winner", "weight", "degree", "counters")
 ROLLS = [("roll", k) for k in STEPS]
 FINISHED = [("steps_noreset", 5), ("roll", 2 * R + 1), ("steps_noreset", 3), ("roll", 65), ("steps_noreset", 2), ("roll", 1),
             ("roll", R)]
@@ -45,122 +44,21 @@ FINISHED = [("steps_noreset", 5), ("roll", 2 * R + 1), ("steps_noreset", 3), ("r
 
 @pytest.fixture(scope="module")
 def T():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import tron.vec as tv
-    import oracle
-    oracle.set_threads(min(16, len(os.sched_getaffinity(0))))
+    tv, oracle = gpu_modules(threads=True)
     yield tv, oracle
-    oracle.set_threads(1)
-
-
-def np_(t):
-    return t.detach().cpu().numpy()
-
-
-class Ref:
-    """The oracle stepped through a sequence, with what the conditions on the inputs need: per launch the episode
-    counters around it, and per launch and step which envs restarted."""
-
-    def __init__(self, oracle, N, W, fair):
-        self.oracle, self.N, self.W, self.fair = oracle, N, W, fair
-        self.v = oracle.VecOracle(N, W, seed=SEED, stream=RANK, fair=fair)
-        self.v.reset_all()
-        self.totals = np.zeros(4, np.int64)
-        self.launches = []                                       # per launch: ([N] episode before, [k, N] restarted in step s)
-        self.entered_done = 0                                    # envs that were finished when a launch began
-
-    def step(self, nonrev, autoreset=True, count=True):
-        v = self.v
-        was_done = v.done == 1
-        _, d, w, _ = v.step(autoreset=autoreset, want_obs=False, nonreversing=nonrev)
-        if count:                                                # (a finished env restarts without stepping: not counted)
-            stepped = ~was_done
-            self.totals += [int(stepped.sum()), int((stepped & (d == 1) & (w == 1)).sum()),
-                            int((stepped & (d == 1) & (w == 2)).sum()), int((stepped & (d == 1) & (w == 0)).sum())]
-
-    def roll(self, K, nonrev):
-        left = K
-        while left:
-            k = min(left, LAUNCH)
-            before = self.v.episode.copy()
-            self.entered_done += int((self.v.done == 1).sum())
-            hit = np.zeros((k, self.N), bool)
-            for s in range(k):
-                ep = self.v.episode.copy()
-                self.step(nonrev)
-                hit[s] = self.v.episode != ep
-            self.launches.append((before, hit))
-            left -= k
-
-    def apply(self, op, nonrev):
-        if op[0] == "roll":
-            self.roll(op[1], nonrev)
-        else:
-            for _ in range(op[1]):
-                self.step(nonrev, autoreset=False, count=False)
-
-    def obs(self):
-        g = self.v.grid
-        return np.stack([self.oracle.state_for_player(g, 1), self.oracle.state_for_player(g, 2)], 1)
-
-    def clashes(self, envs=16):
-        """Restarts inside the launches, among the first `envs` envs, whose make_game clashes."""
-        nd = 9 if self.fair else 7                               # draws of a game without a clash
-        n = 0
-        for before, hit in self.launches:
-            for e in range(min(envs, self.N)):
-                for ep in range(int(before[e]) + 1, int(before[e]) + int(hit[:, e].sum()) + 1):
-                    words = np.concatenate([self.oracle.philox([e, ep, 2, b], [SEED, RANK]) for b in range(12)])
-                    n += self.oracle.make_game(self.W, self.fair, words)[3] > nd
-        return n
-
-
-def apply(env, totals, op, nonrev, per_step):
-    if op[0] == "roll":
-        env.rollout_random(op[1], totals, nonreversing=nonrev, per_step_launches=per_step)
-    else:
-        for _ in range(op[1]):
-            env.step(autoreset=False, nonreversing=nonrev)
-
-
-def pull(env, totals):
-    torch.cuda.synchronize()
-    got = dict(obs=np_(env.obs).reshape(env.N, 2, -1).copy(), grid=np_(env.grid()).reshape(env.N, -1),
-               totals=np_(totals).copy())
-    got.update({k: np_(v) for k, v in env.state().items()})
-    return got
-
-
-def check_against_oracle(got, ref, tag, totals=True):
-    v = ref.v
-    assert np.array_equal(got["obs"], ref.obs()), (tag, "obs")
-    assert np.array_equal(got["grid"], v.grid), (tag, "grid")
-    for k in ("pos", "alive", "dir", "done", "winner", "weight", "degree"):
-        assert np.array_equal(got[k], getattr(v, k)), (tag, k)
-    if totals:
-        assert np.array_equal(got["totals"], ref.totals), (tag, "totals")
-    c = got["counters"].astype(np.uint32)
-    assert np.array_equal(c[:, 0], v.tick), (tag, "tick")
-    assert np.array_equal(c[:, 1], v.episode), (tag, "episode")
-    assert np.array_equal(c[:, 2], v.eplen), (tag, "eplen")
-
-
-def check_against_twin(got, twin, tag):
-    for k in ("obs", "grid", "totals") + STATE_KEYS:
-        assert np.array_equal(got[k], twin[k]), (tag, k)
+    restore_threads(oracle)
 
 
 def make(tv, N, W, fair):
     env = tv.VecTron(N, W, seed=SEED, rank=RANK, obs_format="codes", fair=fair)
     assert env.obs_is_state
     env.reset()
-    return env, torch.zeros(4, dtype=torch.int64, device="cuda")
+    return env, new_totals()
 
 
 def run_sequence(T, N, W, fair, nonrev, ops):
     tv, oracle = T
-    ref = Ref(oracle, N, W, fair)
+    ref = Ref(oracle, N, W, SEED, RANK, fair=fair)
     env, totals = make(tv, N, W, fair)
     twin, ttot = make(tv, N, W, fair)
     for i, op in enumerate(ops):
@@ -176,7 +74,7 @@ def run_sequence(T, N, W, fair, nonrev, ops):
     for j in range(FOLLOW_MAX):
         if (ref.v.episode != seen).all():
             break
-        ref.step(False, count=False)
+        ref.step(count=False)
         env.step()
         twin.step()
         check_against_oracle(pull(env, totals), ref, (N, W, fair, nonrev, "follow", j))
@@ -221,7 +119,7 @@ def longest_run(hit):
 
 
 def oracle_only(oracle, N, W, fair, nonrev, ops):
-    ref = Ref(oracle, N, W, fair)
+    ref = Ref(oracle, N, W, SEED, RANK, fair=fair)
     for op in ops:
         ref.apply(op, nonrev)
     return ref
@@ -247,6 +145,6 @@ def test_inputs_reach_the_cases(T):
     ref = oracle_only(oracle, 130, 24, False, True, ROLLS)
     assert any((hit.sum(0) == 0).any() for _, hit in ref.launches if len(hit) > 2 * R)
     for fair in (False, True):                                   # clashing starts at side 4: the helper's general routine
-        assert oracle_only(oracle, 130, 4, fair, False, ROLLS).clashes() > 0
+        assert oracle_only(oracle, 130, 4, fair, False, ROLLS).clashes()[0] > 0
     ref = oracle_only(oracle, 130, 24, False, False, FINISHED)
     assert ref.entered_done > 0                                  # envs that are finished when a launch begins

@@ -15,10 +15,10 @@ The whole observation buffer [N, 2, G] is compared, so a store past G of a short
 player-2 plane, or of the next env's player-1 plane — shows as a difference there: no separate check of the bytes between
 planes is needed.
 """
-import os
-
 import numpy as np
 import pytest
+
+from rollout_support import Ref, check_against_oracle, check_against_twin, gpu_modules, new_totals, np_, pull, restore_threads
 
 pytestmark = pytest.mark.gpu
 
@@ -28,34 +28,13 @@ WIDTHS = (4, 10, 24, 30)
 ENVS = (1, 63, 130, 257)
 STEPS = (1, 2, 63, 64, 65, 130)
 SEED, RANK = 0xC0FFEE, 2
-STATE_KEYS = ("pos", "alive", "dir", "done", "winner", "weight", "degree", "counters")
 
 
 @pytest.fixture(scope="module")
 def T():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import tron.vec as tv
-    import oracle
-    oracle.set_threads(min(16, len(os.sched_getaffinity(0))))
+    tv, oracle = gpu_modules(threads=True)
     yield tv, oracle
-    oracle.set_threads(1)
-
-
-def np_(t):
-    return t.detach().cpu().numpy()
-
-
-def snapshot(ref, obs, totals):
-    return dict(obs=obs.copy(), grid=ref.grid.copy(), pos=ref.pos.copy(), alive=ref.alive.copy(), dir=ref.dir.copy(),
-                done=ref.done.copy(), winner=ref.winner.copy(), weight=ref.weight.copy(), degree=ref.degree.copy(),
-                tick=ref.tick.copy(), episode=ref.episode.copy(), eplen=ref.eplen.copy(), totals=totals.copy())
-
-
-def oracle_step(ref, totals, want_obs, nonrev, actions=None):
-    o, d, w, _ = ref.step(actions=actions, autoreset=True, want_obs=want_obs, nonreversing=nonrev)
-    totals += [ref.N, int(((d == 1) & (w == 1)).sum()), int(((d == 1) & (w == 2)).sum()), int(((d == 1) & (w == 0)).sum())]
-    return o
+    restore_threads(oracle)
 
 
 _REFS = {}
@@ -65,14 +44,12 @@ def reference(oracle, N, W, nonrev):
     """The oracle's snapshots after each step count of STEPS: computed once per (N, W, distribution), never modified."""
     key = (N, W, nonrev)
     if key not in _REFS:
-        ref = oracle.VecOracle(N, W, seed=SEED, stream=RANK)
-        ref.reset_all()
-        totals = np.zeros(4, np.int64)
+        ref = Ref(oracle, N, W, SEED, RANK)
         snaps = {}
         for k in range(1, max(STEPS) + 1):
-            o = oracle_step(ref, totals, k in STEPS, nonrev)
+            ref.step(nonrev=nonrev)
             if k in STEPS:
-                snaps[k] = snapshot(ref, o, totals)
+                snaps[k] = ref.snapshot()
         _REFS[key] = snaps
     return _REFS[key]
 
@@ -85,33 +62,16 @@ def swap_codes(plane):
     return table[plane.view(np.uint8)]
 
 
-def pull(env, totals):
-    got = dict(obs=np_(env.obs).reshape(env.N, 2, -1).copy(), grid=np_(env.grid()).reshape(env.N, -1),
-               totals=np_(totals).copy())
-    got.update({k: np_(v) for k, v in env.state().items()})
-    return got
-
-
-def check_against_oracle(got, exp, tag):
-    for k in ("obs", "grid", "pos", "alive", "dir", "done", "winner", "weight", "degree", "totals"):
-        assert np.array_equal(got[k], exp[k]), (tag, k)
-    c = got["counters"].astype(np.uint32)
-    assert np.array_equal(c[:, 0], exp["tick"]), (tag, "tick")
-    assert np.array_equal(c[:, 1], exp["episode"]), (tag, "episode")
-    assert np.array_equal(c[:, 2], exp["eplen"]), (tag, "eplen")
+def check(got, exp, tag):
+    check_against_oracle(got, exp, tag)
     assert np.array_equal(got["obs"][:, 1], swap_codes(got["obs"][:, 0])), (tag, "player-2 plane")
-
-
-def check_against_twin(got, twin, tag):
-    for k in ("obs", "grid", "totals") + STATE_KEYS:
-        assert np.array_equal(got[k], twin[k]), (tag, k)
 
 
 def make(tv, N, W):
     env = tv.VecTron(N, W, seed=SEED, rank=RANK, obs_format="codes")
     assert env.obs_is_state
     env.reset()
-    return env, torch.zeros(4, dtype=torch.int64, device="cuda")
+    return env, new_totals()
 
 
 @pytest.mark.parametrize("nonrev", [False, True])
@@ -125,7 +85,7 @@ def test_launch_stores_equal_oracle_and_per_step_twin(T, W, N, nonrev):
         env, totals = make(tv, N, W)
         env.rollout_random(K, totals, nonreversing=nonrev)
         got = pull(env, totals)
-        check_against_oracle(got, snaps[K], (W, N, nonrev, K))
+        check(got, snaps[K], (W, N, nonrev, K))
         twin, ttot = make(tv, N, W)
         twin.rollout_random(K, ttot, nonreversing=nonrev, per_step_launches=True)
         check_against_twin(got, pull(twin, ttot), (W, N, nonrev, K, "twin"))
@@ -147,25 +107,23 @@ def test_launch_stores_between_other_writers(T, W, nonrev, masked_reset):
     tv, oracle = T
     N = 130
     rng = np.random.RandomState(1000 + W)
-    ref = oracle.VecOracle(N, W, seed=SEED, stream=RANK)
-    ref.reset_all()
-    exp_tot = np.zeros(4, np.int64)
+    ref = Ref(oracle, N, W, SEED, RANK)
     env, totals = make(tv, N, W)
     twin, ttot = make(tv, N, W)
 
     def rollout(K, tag):
         env.rollout_random(K, totals, nonreversing=nonrev)
         twin.rollout_random(K, ttot, nonreversing=nonrev, per_step_launches=True)
-        o = None
         for k in range(K):
-            o = oracle_step(ref, exp_tot, k == K - 1, nonrev)
+            ref.step(nonrev=nonrev)
         got = pull(env, totals)
-        check_against_oracle(got, snapshot(ref, o, exp_tot), (W, nonrev, masked_reset, tag))
+        check(got, ref, (W, nonrev, masked_reset, tag))
         check_against_twin(got, pull(twin, ttot), (W, nonrev, masked_reset, tag, "twin"))
 
     rollout(5, "first rollout")
     a = rng.randint(0, 4, size=(N, 2)).astype(np.int8)
-    o, dd, ww, _ = ref.step(actions=a, autoreset=True)
+    dd, ww, _ = ref.step(a, count=False)
+    o = ref.obs()
     for name, e in (("env", env), ("twin", twin)):
         obs, _, d, w = e.step(torch.from_numpy(a), autoreset=True)
         assert np.array_equal(np_(obs).reshape(N, 2, -1), o), (W, nonrev, masked_reset, name, "step obs")
@@ -175,7 +133,7 @@ def test_launch_stores_between_other_writers(T, W, nonrev, masked_reset):
         mask[0] = 1
         for e in (env, twin):
             e.reset(mask=torch.from_numpy(mask))
-        ref.reset_masked(mask)
+        ref.v.reset_masked(mask)
     rollout(70, "second rollout")
     env.close()
     twin.close()

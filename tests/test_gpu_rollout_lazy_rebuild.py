@@ -14,10 +14,10 @@ placement (three Philox blocks per restart, clashing starts common) at widths 4 
 
 test_inputs_reach_the_rare_paths asserts, on the oracle alone, that these inputs do reach the paths they are there for.
 """
-import os
-
 import numpy as np
 import pytest
+
+from rollout_support import LAUNCH, Ref, check_against_oracle, check_against_twin, gpu_modules, new_totals, pull, restore_threads
 
 pytestmark = pytest.mark.gpu
 
@@ -27,37 +27,15 @@ WIDTHS = (4, 10, 24, 30)
 FAIR_WIDTHS = (4, 10)
 ENVS = (1, 63, 130, 257)
 STEPS = (1, 2, 63, 64, 65, 130)
-LAUNCH = 64                                                      # steps per persistent launch (TRON_ROLLOUT_CHUNK)
 SEED, RANK = 0xC0FFEE, 2
-STATE_KEYS = ("pos", "alive", "dir", "done", "winner", "weight", "degree", "counters")
 CASES = [(W, False) for W in WIDTHS] + [(W, True) for W in FAIR_WIDTHS]
 
 
 @pytest.fixture(scope="module")
 def T():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import tron.vec as tv
-    import oracle
-    oracle.set_threads(min(16, len(os.sched_getaffinity(0))))
+    tv, oracle = gpu_modules(threads=True)
     yield tv, oracle
-    oracle.set_threads(1)
-
-
-def np_(t):
-    return t.detach().cpu().numpy()
-
-
-def snapshot(ref, obs, totals):
-    return dict(obs=obs.copy(), grid=ref.grid.copy(), pos=ref.pos.copy(), alive=ref.alive.copy(), dir=ref.dir.copy(),
-                done=ref.done.copy(), winner=ref.winner.copy(), weight=ref.weight.copy(), degree=ref.degree.copy(),
-                tick=ref.tick.copy(), episode=ref.episode.copy(), eplen=ref.eplen.copy(), totals=totals.copy())
-
-
-def oracle_step(ref, totals, want_obs, nonrev):
-    o, d, w, _ = ref.step(autoreset=True, want_obs=want_obs, nonreversing=nonrev)
-    totals += [ref.N, int(((d == 1) & (w == 1)).sum()), int(((d == 1) & (w == 2)).sum()), int(((d == 1) & (w == 0)).sum())]
-    return o
+    restore_threads(oracle)
 
 
 _REFS = {}
@@ -67,44 +45,21 @@ def reference(oracle, N, W, nonrev, fair):
     """The oracle's snapshots after each step count of STEPS: computed once per case, never modified."""
     key = (N, W, nonrev, fair)
     if key not in _REFS:
-        ref = oracle.VecOracle(N, W, seed=SEED, stream=RANK, fair=fair)
-        ref.reset_all()
-        totals = np.zeros(4, np.int64)
+        ref = Ref(oracle, N, W, SEED, RANK, fair=fair)
         snaps = {}
         for k in range(1, max(STEPS) + 1):
-            o = oracle_step(ref, totals, k in STEPS, nonrev)
+            ref.step(nonrev=nonrev)
             if k in STEPS:
-                snaps[k] = snapshot(ref, o, totals)
+                snaps[k] = ref.snapshot()
         _REFS[key] = snaps
     return _REFS[key]
-
-
-def pull(env, totals):
-    got = dict(obs=np_(env.obs).reshape(env.N, 2, -1).copy(), grid=np_(env.grid()).reshape(env.N, -1),
-               totals=np_(totals).copy())
-    got.update({k: np_(v) for k, v in env.state().items()})
-    return got
-
-
-def check_against_oracle(got, exp, tag):
-    for k in ("obs", "grid", "pos", "alive", "dir", "done", "winner", "weight", "degree", "totals"):
-        assert np.array_equal(got[k], exp[k]), (tag, k)
-    c = got["counters"].astype(np.uint32)
-    assert np.array_equal(c[:, 0], exp["tick"]), (tag, "tick")
-    assert np.array_equal(c[:, 1], exp["episode"]), (tag, "episode")
-    assert np.array_equal(c[:, 2], exp["eplen"]), (tag, "eplen")
-
-
-def check_against_twin(got, twin, tag):
-    for k in ("obs", "grid", "totals") + STATE_KEYS:
-        assert np.array_equal(got[k], twin[k]), (tag, k)
 
 
 def make(tv, N, W, fair):
     env = tv.VecTron(N, W, seed=SEED, rank=RANK, obs_format="codes", fair=fair)
     assert env.obs_is_state
     env.reset()
-    return env, torch.zeros(4, dtype=torch.int64, device="cuda")
+    return env, new_totals()
 
 
 @pytest.mark.parametrize("nonrev", [False, True])

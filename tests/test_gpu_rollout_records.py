@@ -23,6 +23,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from rollout_support import check_against_twin, gpu_modules, make_tape, new_totals, pull, step_counted
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
@@ -38,15 +40,7 @@ PRE_STEPS = 2                                                    # a 4x4 game la
 
 @pytest.fixture(scope="module")
 def tv():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import tron.vec as tv
-    return tv
-
-
-def make_tape(N, K, salt=0):
-    g = torch.Generator().manual_seed(1_000_003 * N + 131 * K + salt)
-    return torch.randint(0, 4, (K, N, 2), generator=g, dtype=torch.int64).to(torch.int8).cuda()
+    return gpu_modules()[0]
 
 
 def make(tv, N, W, mode=None, reward="default"):
@@ -54,31 +48,12 @@ def make(tv, N, W, mode=None, reward="default"):
     if REWARDS[reward] is not None:
         env.set_reward(**REWARDS[reward])
     env.reset()
-    return env, torch.zeros(4, dtype=torch.int64, device="cuda")
-
-
-def step_counted(env, totals, actions, live=None):
-    """One per-step launch with autoreset, the totals a rollout keeps of it (it counts the envs that move: every env,
-    unless the caller says which were live when the step began), and clones of the (reward, done, winner) it returned."""
-    _, r, d, w = env.step(actions, autoreset=True)
-    if live is None:
-        live = torch.ones_like(d, dtype=torch.bool)
-    fin = (d == 1) & live
-    totals += torch.stack([live.sum(), (fin & (w == 1)).sum(), (fin & (w == 2)).sum(), (fin & (w == 0)).sum()])
-    return r.clone(), d.clone(), w.clone()
-
-
-def pull(env, totals):
-    torch.cuda.synchronize()
-    got = dict(obs=env.obs.clone().cpu(), grid=env.grid().cpu(), totals=totals.clone().cpu())
-    got.update({k: v.cpu() for k, v in env.state().items()})
-    return got
+    return env, new_totals()
 
 
 def assert_same(got, want, tag):
-    assert set(got) == set(want) == {"obs", "grid", "totals"} | set(STATE_KEYS)
-    for k in want:
-        assert got[k].shape == want[k].shape and torch.equal(got[k], want[k]), (tag, k)
+    assert set(want) == {"obs", "grid", "totals"} | set(STATE_KEYS)
+    check_against_twin(got, want, tag)
 
 
 def assert_records(got, want, K, tag, which=(0, 1, 2)):
@@ -121,7 +96,7 @@ def run_records(tv, N, W, K, mode=None, reward="default", records=True, **kw):
     return rec, got
 
 
-def check_against_twin(tv, N, W, K, tag, mode=None, reward="default", **kw):
+def check_records_against_twin(tv, N, W, K, tag, mode=None, reward="default", **kw):
     rec, got = run_records(tv, N, W, K, mode, reward, **kw)
     snaps, want = twin(tv, W, N, mode, reward)
     assert rec[0].shape == (K, N, 2) and rec[1].shape == (K, N) and rec[2].shape == (K, N)
@@ -135,7 +110,7 @@ def check_against_twin(tv, N, W, K, tag, mode=None, reward="default", **kw):
 @pytest.mark.parametrize("N", [1, 70, 200])
 @pytest.mark.parametrize("W", [4, 10])
 def test_records_equal_per_step(tv, W, N, K, reward):
-    check_against_twin(tv, N, W, K, (W, N, K, reward), reward=reward)
+    check_records_against_twin(tv, N, W, K, (W, N, K, reward), reward=reward)
 
 
 def test_the_twin_pays_by_step_index_under_the_dqn_table(tv):
@@ -146,7 +121,7 @@ def test_the_twin_pays_by_step_index_under_the_dqn_table(tv):
 
 # ---- 2: four game waves per workgroup
 def test_records_four_game_waves(tv):
-    check_against_twin(tv, FOUR_WAVES, 4, 130, "four game waves")
+    check_records_against_twin(tv, FOUR_WAVES, 4, 130, "four game waves")
 
 
 # ---- 3: the C oracle
@@ -248,15 +223,15 @@ def test_split_tape(tv):
 
 # ---- 8: the paths that loop over the per-step launch
 def test_fallback_temper(tv):
-    check_against_twin(tv, 70, 10, 20, "temper", mode="temper")
+    check_records_against_twin(tv, 70, 10, 20, "temper", mode="temper")
 
 
 def test_fallback_odd_side(tv):
-    check_against_twin(tv, 70, 5, 20, "W = 5")
+    check_records_against_twin(tv, 70, 5, 20, "W = 5")
 
 
 def test_per_step_launches_flag(tv):
-    check_against_twin(tv, 70, 10, 65, "per_step_launches", per_step_launches=True)
+    check_records_against_twin(tv, 70, 10, 65, "per_step_launches", per_step_launches=True)
 
 
 def test_fallback_f32_planes_on_attached_codes(tv):

@@ -4,93 +4,29 @@ what such a store could get wrong: a buffer changed between rollouts by every wr
 on the border (a head overwrites a WALL cell) or head-on on one cell and the restarts that follow them, sizes around the
 residency limits and ragged last tiles.  Every byte of env.obs, grid() and state() is compared with the CPU oracle
 driven the same way.  No tolerances anywhere."""
-import os
-
 import numpy as np
 import pytest
+
+from rollout_support import Ref, check_against_oracle, gpu_modules, np_, pull, restore_threads, start_positions
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-STATE_KEYS = ("pos", "alive", "dir", "done", "winner", "weight", "degree", "counters")
-WALL, P1_HEAD = -1, 2          # raw tile values (map.py:9-17)
-
-
 @pytest.fixture(scope="module")
 def T():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import tron.vec as tv
-    import oracle
-    return tv, oracle
-
-
-def np_(t):
-    return t.detach().cpu().numpy()
-
-
-class Ref:
-    """The oracle with autoreset done by hand (a step without autoreset, then a reset of the envs that finished: what
-    orc_vec_step does with autoreset), so that the boards that finished can be looked at before they restart."""
-
-    def __init__(self, oracle, N, W, seed, rank):
-        self.oracle = oracle
-        self.v = oracle.VecOracle(N, W, seed=seed, stream=rank)
-        self.v.reset_all()
-        S = W + 2
-        b = np.zeros((S, S), bool)
-        b[0, :] = b[-1, :] = b[:, 0] = b[:, -1] = True
-        self.border = b.reshape(-1)
-        self.border_deaths = 0          # episodes that ended with a head on a border cell
-        self.same_cell = 0              # episodes that ended with both heads on one cell (P2's head over P1's)
-
-    def step(self, actions=None, nonrev=False, count=False):
-        v = self.v
-        if not count:
-            _, d, w, r = v.step(actions, autoreset=True, want_obs=False, nonreversing=nonrev)
-            return d, w, r
-        _, d, w, r = v.step(actions, autoreset=False, want_obs=False, nonreversing=nonrev)
-        fin = d == 1                     # (every env was live before the step: autoreset)
-        if fin.any():
-            g = v.grid[fin]
-            self.border_deaths += int((g[:, self.border] != WALL).any(1).sum())
-            self.same_cell += int((~(g == P1_HEAD).any(1)).sum())
-            v.reset_masked(fin)
-        return d, w, r
-
-    def obs(self):
-        g = self.v.grid
-        return np.stack([self.oracle.state_for_player(g, 1), self.oracle.state_for_player(g, 2)], 1)
+    return gpu_modules()
 
 
 def check(env, ref, tag):
     """Every byte a caller can read back against the oracle."""
-    v, N = ref.v, ref.v.N
-    torch.cuda.synchronize()
-    st = env.state()
-    assert np.array_equal(np_(env.obs).reshape(N, 2, -1), ref.obs()), tag
-    assert np.array_equal(np_(env.grid()).reshape(N, -1), v.grid), tag
-    assert np.array_equal(np_(st["pos"]), v.pos) and np.array_equal(np_(st["alive"]), v.alive), tag
-    assert np.array_equal(np_(st["dir"]), v.dir), tag
-    assert np.array_equal(np_(st["done"]), v.done) and np.array_equal(np_(st["winner"]), v.winner), tag
-    assert np.array_equal(np_(st["weight"]), v.weight) and np.array_equal(np_(st["degree"]), v.degree), tag
-    c = np_(st["counters"]).astype(np.uint32)
-    assert np.array_equal(c[:, 0], v.tick) and np.array_equal(c[:, 1], v.episode), tag
-    assert np.array_equal(c[:, 2], v.eplen), tag
+    check_against_oracle(pull(env), ref, tag, totals=False)
 
 
-def rollout(env, ref, K, nonrev, count=False):
+def rollout(env, ref, K, nonrev):
     env.rollout_random(K, nonreversing=nonrev)
     for _ in range(K):
-        ref.step(nonrev=nonrev, count=count)
-
-
-def start_positions(rs, N, W):
-    sp = rs.randint(0, W, (N, 4)).astype(np.int8)
-    clash = (sp[:, 0] == sp[:, 2]) & (sp[:, 1] == sp[:, 3])
-    sp[clash, 3] = (sp[clash, 1] + 1) % W
-    return sp
+        ref.step(nonrev=nonrev)
 
 
 @pytest.mark.parametrize("nonrev", [False, True])
@@ -154,17 +90,17 @@ def test_border_deaths_and_same_cell_draws(T, N, W, seed, nonrev):
     next restarts (per-step launches)."""
     tv, oracle = T
     env = tv.VecTron(N, W, seed=seed, rank=1, obs_format="codes")
-    ref = Ref(oracle, N, W, seed=seed, rank=1)
+    ref = Ref(oracle, N, W, seed=seed, rank=1, events=True)    # (looks at the finished boards before they restart)
     env.reset()
     for K in (20, 65, 64):
         b0, s0 = ref.border_deaths, ref.same_cell
-        rollout(env, ref, K, nonrev, count=True)
+        rollout(env, ref, K, nonrev)
         print(f"rollout of {K}: {ref.border_deaths - b0} border deaths, {ref.same_cell - s0} same-cell draws")
         assert ref.border_deaths > b0 and ref.same_cell > s0, "the seed must show both kinds of ending"
         check(env, ref, f"rollout of {K}")
     for k in range(6):
         env.step(nonreversing=nonrev)
-        ref.step(nonrev=nonrev, count=True)
+        ref.step(nonrev=nonrev)
         check(env, ref, f"per-step launch {k} after the rollouts")
 
 
@@ -180,7 +116,7 @@ def test_sizes_around_residency_limits(T, N, W, nonrev):
     tv, oracle = T
     big = N >= 65536
     if big:
-        oracle.set_threads(min(16, len(os.sched_getaffinity(0))))
+        gpu_modules(threads=True)
     try:
         env = tv.VecTron(N, W, seed=29, rank=2, obs_format="codes")
         ref = Ref(oracle, N, W, seed=29, rank=2)
@@ -192,4 +128,4 @@ def test_sizes_around_residency_limits(T, N, W, nonrev):
             ref.step(nonrev=nonrev)
         check(env, ref, "per-step launches after the rollout")
     finally:
-        oracle.set_threads(1)
+        restore_threads(oracle)

@@ -8,92 +8,30 @@ Every byte of env.obs, grid() and state() and the totals are compared with the C
 tolerances.  tron_rollout_random implies autoreset and returns totals only, so done / winner / reward are compared
 as the totals of every rollout and as the per-step arrays of the step() calls between rollouts; envs that finished
 under autoreset=False reach the rollout as finished envs (nothing is redrawn for them before it)."""
-import os
-
 import numpy as np
 import pytest
+
+from rollout_support import Ref, check_against_oracle, check_against_twin, gpu_modules, new_totals, np_, pull, restore_threads, \
+    start_positions
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-STATE_KEYS = ("pos", "alive", "dir", "done", "winner", "weight", "degree", "counters")
-WALL, P1_HEAD = -1, 2          # raw tile values (map.py:9-17)
-
 
 @pytest.fixture(scope="module")
 def T():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import tron.vec as tv
-    import oracle
-    return tv, oracle
-
-
-def np_(t):
-    return t.detach().cpu().numpy()
-
-
-def tally(d, w, stepped):
-    fin = (d == 1) & stepped
-    return np.array([int(stepped.sum()), int((fin & (w == 1)).sum()), int((fin & (w == 2)).sum()), int((fin & (w == 0)).sum())],
-                    np.int64)
-
-
-class Ref:
-    """The oracle with autoreset done by hand, so that finished boards can be looked at before they restart."""
-
-    def __init__(self, oracle, N, W, seed, rank):
-        self.oracle = oracle
-        self.v = oracle.VecOracle(N, W, seed=seed, stream=rank)
-        self.v.reset_all()
-        S = W + 2
-        b = np.zeros((S, S), bool)
-        b[0, :] = b[-1, :] = b[:, 0] = b[:, -1] = True
-        self.border = b.reshape(-1)
-        self.border_deaths = self.same_cell = self.long_episodes = 0
-        self.totals = np.zeros(4, np.int64)
-
-    def step(self, actions=None, nonrev=False):
-        """One step with autoreset; returns done / winner / reward as a step with autoreset reports them."""
-        v = self.v
-        was_done = v.done == 1               # finished before the step: not stepped, restarted by the autoreset
-        _, d, w, r = v.step(actions, autoreset=False, want_obs=False, nonreversing=nonrev)
-        d, w, r = d.copy(), w.copy(), r.copy()
-        self.totals += tally(d, w, ~was_done)
-        fin = d == 1
-        if fin.any():
-            g = v.grid[fin & ~was_done]
-            self.border_deaths += int((g[:, self.border] != WALL).any(1).sum())
-            self.same_cell += int((~(g == P1_HEAD).any(1)).sum())
-            self.long_episodes += int((v.eplen[fin] >= 20).sum())
-            v.reset_masked(fin)
-        return d, w, r
-
-    def obs(self):
-        g = self.v.grid
-        return np.stack([self.oracle.state_for_player(g, 1), self.oracle.state_for_player(g, 2)], 1)
+    return gpu_modules()
 
 
 def check(env, ref, tag):
     """Every byte a caller can read back against the oracle."""
-    v, N = ref.v, ref.v.N
-    torch.cuda.synchronize()
-    st = env.state()
-    assert np.array_equal(np_(env.obs).reshape(N, 2, -1), ref.obs()), tag
-    assert np.array_equal(np_(env.grid()).reshape(N, -1), v.grid), tag
-    assert np.array_equal(np_(st["pos"]), v.pos) and np.array_equal(np_(st["alive"]), v.alive), tag
-    assert np.array_equal(np_(st["dir"]), v.dir), tag
-    assert np.array_equal(np_(st["done"]), v.done) and np.array_equal(np_(st["winner"]), v.winner), tag
-    assert np.array_equal(np_(st["weight"]), v.weight) and np.array_equal(np_(st["degree"]), v.degree), tag
-    c = np_(st["counters"]).astype(np.uint32)
-    assert np.array_equal(c[:, 0], v.tick) and np.array_equal(c[:, 1], v.episode), tag
-    assert np.array_equal(c[:, 2], v.eplen), tag
+    check_against_oracle(pull(env), ref, tag, totals=False)
 
 
 def rollout(env, ref, K, nonrev=False, tag=""):
     """K steps both ways; the rollout's totals against the oracle's."""
-    totals = torch.zeros(4, dtype=torch.int64, device="cuda")
+    totals = new_totals()
     env.rollout_random(K, totals, nonreversing=nonrev)
     before = ref.totals.copy()
     for _ in range(K):
@@ -107,7 +45,7 @@ def make(T, N, W, seed, rank):
     env = tv.VecTron(N, W, seed=seed, rank=rank, obs_format="codes")
     assert env.obs_is_state
     env.reset()
-    return env, Ref(oracle, N, W, seed, rank)
+    return env, Ref(oracle, N, W, seed, rank, events=True)
 
 
 # Up to 64 x (number of CUs) envs the host launches one 64-env wave per workgroup, so there wave and workgroup are the same:
@@ -128,14 +66,13 @@ def test_ragged_waves_and_launch_seams(T, N, W):
 @pytest.mark.parametrize("N", [16384 + 1, 16384 + 65, 16384 + 200, 16384 + 255])
 def test_ragged_four_wave_workgroups(T, N):
     """The benchmark's launch shape with a ragged tail, through the 64-step seam (65 = 64 + 1, then 3 from memory)."""
-    _, oracle = T
-    oracle.set_threads(min(16, len(os.sched_getaffinity(0))))
+    _, oracle = gpu_modules(threads=True)
     try:
         env, ref = make(T, N, 6, seed=N % 1000, rank=2)
         rollout(env, ref, 65)
         rollout(env, ref, 3)
     finally:
-        oracle.set_threads(1)
+        restore_threads(oracle)
 
 
 @pytest.mark.parametrize("W,K", [(30, 65), (32, 65), (9, 20)])
@@ -147,7 +84,7 @@ def test_mask_width_limits_and_routing(T, W, K):
     env = tv.VecTron(N, W, seed=5, rank=3, obs_format="codes")
     assert env.obs_is_state == (W % 2 == 0)
     env.reset()
-    ref = Ref(oracle, N, W, 5, 3)
+    ref = Ref(oracle, N, W, 5, 3, events=True)
     assert ((W + 2) ** 2 + 15) // 16 == {30: 64, 32: 73, 9: 8}[W]
     rollout(env, ref, K)
     rollout(env, ref, 3)
@@ -181,13 +118,6 @@ def test_long_episodes(T):
     assert ref.long_episodes > 0, "at least one episode must reach 20 steps before restarting"
     assert ref.border_deaths > 0, "at least one episode must end with a head on a border cell"
     assert ref.same_cell > 0, "at least one episode must end with both heads on one cell"
-
-
-def start_positions(rs, N, W):
-    sp = rs.randint(0, W, (N, 4)).astype(np.int8)
-    clash = (sp[:, 0] == sp[:, 2]) & (sp[:, 1] == sp[:, 3])
-    sp[clash, 3] = (sp[clash, 1] + 1) % W
-    return sp
 
 
 @pytest.mark.parametrize("N,W", [(65, 6), (200, 24)])
@@ -241,13 +171,7 @@ def test_twin_per_step_launches(T, N, W, K, nonrev):
     for per_step in (False, True):
         env = tv.VecTron(N, W, seed=11, rank=4, obs_format="codes")
         env.reset()
-        totals = torch.zeros(4, dtype=torch.int64, device="cuda")
+        totals = new_totals()
         env.rollout_random(K, totals, nonreversing=nonrev, per_step_launches=per_step)
-        torch.cuda.synchronize()
-        st = env.state()
-        snap = {"obs": np_(env.obs).copy(), "grid": np_(env.grid()).copy(), "totals": np_(totals).copy()}
-        for k in STATE_KEYS:
-            snap[k] = np_(st[k]).copy()
-        snaps.append(snap)
-    for k in snaps[0]:
-        assert np.array_equal(snaps[0][k], snaps[1][k]), k
+        snaps.append(pull(env, totals))
+    check_against_twin(snaps[0], snaps[1], "per_step_launches")
