@@ -1049,6 +1049,12 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 //            the launch draws, in slot j % (2 ROLL_R)
 // and reads one word per env and block, counts[64]: the env's restarts so far.
 constexpr int ROLL_R = 8;
+// A launch flag of the host's own (rollout_wave), beside the TRON_STEP_* bits: every env's entry mask describes its planes.
+constexpr uint32_t ROLL_ENTRY_MASKED = 0x80000000u;
+// Behind a masked entry the game wave is at P within 5 us and its helper, with 16 Philox blocks to draw, is not (stamps:
+// profiles/r18_rollout_ab.txt).  The game wave then draws the last ROLL_GAME_STARTS ordinals of block 0 itself, after its
+// gather; with 2 the two roles meet at P (0: the helper is 2.8 us late in every pair, 4: the game wave is 1.4 us late).
+constexpr int ROLL_GAME_STARTS = 2;
 constexpr size_t ROLL_RING_DWORDS = 4 * WAVE + 2 * ROLL_R * WAVE + 2 * WAVE;
 static_assert(ROLL_R == 8 && TRON_ROLLOUT_CHUNK % ROLL_R == 0, "a block's action bytes are one qword; blocks tile a launch");
 #ifdef TRON_STAMPS
@@ -1086,7 +1092,12 @@ __device__ __forceinline__ void roll_flush_tally(uint32_t &tally, uint32_t &n_st
 // lane hi, the highest ordinal it has drawn, and TOPS THE RING UP: during block b (behind B_b; behind P for block 0, where
 // c_0 = 0 needs no read) it draws (hi, c_b + ROLL_R + len_(b+1)] and sets hi — everything block b + 1 can read, and in
 // steady state c_b - c_(b-1) draws: what block b - 1 consumed (2.8 per env and block at 24x24, the slowest lane of a wave
-// 4.8, where drawing every block's ROLL_R anew was 8).  The prologue draws (0, len_0]: hi = len_0 at P.
+// 4.8, where drawing every block's ROLL_R anew was 8).  The prologue draws (0, len_0]: hi = len_0 at P.  Behind a masked
+// entry (roll_resident) the last game_starts = min(ROLL_GAME_STARTS, len_0) of these ordinals are the GAME wave's: the helper
+// draws (0, len_0 - game_starts], the game wave (len_0 - game_starts, len_0] with the same make_game_starts (a clash goes
+// through make_game_general there as here) into the same slots j % (2 ROLL_R), both before P; hi = len_0 at P as before.
+// The two sets of slots are disjoint (len_0 <= ROLL_R consecutive ordinals), nobody reads the ring before P, and the helper's
+// next write is behind P: the invariant below holds with "the ring holds (0, len_0] at P" whoever wrote which slot.
 // Invariant: at B_(b+1) the ring holds (c_b, hi] with hi >= c_b + ROLL_R + len_(b+1), which contains block b + 1's (c_(b+1),
 // c_(b+1) + len_(b+1)].  Induction: at B_b (P for b = 0) the ring holds (c_(b-1), hi] with hi >= c_(b-1) + ROLL_R + len_b >=
 // c_b + len_b (full blocks but the last: hi >= c_b + ROLL_R wherever a block b + 1 exists).  During block b the helper
@@ -1114,7 +1125,7 @@ __device__ __forceinline__ void roll_flush_tally(uint32_t &tally, uint32_t &n_st
 template <bool TAPE>
 __device__ __forceinline__ void roll_helper(const Params &P, int env, bool autoreset, const uint4 &st, const uint4 &rs, int k_steps,
                                             int lane, uint2 *aring, uint32_t *sring, const uint32_t *cring, const StepOut &out,
-                                            int wave, int gw, bool mine, const int8_t *tape)
+                                            int wave, int gw, bool mine, const int8_t *tape, uint32_t game_starts)
 {
     ROLL_HSTAMP(0);
     const uint32_t seed = P.seed, stream = P.stream;
@@ -1158,8 +1169,9 @@ __device__ __forceinline__ void roll_helper(const Params &P, int env, bool autor
             aring[((b + 1) & 1) * WAVE + lane] = make_uint2(v[0], v[1]);
         }
         if (autoreset) {
+            const uint32_t upto = b < 0 ? to - min(game_starts, to) : to;   // (block 0's last ordinals may be the game wave's)
 #pragma nounroll
-            for (uint32_t j = hi + 1u; j <= to; ++j)                // (per lane: nothing where hi >= to)
+            for (uint32_t j = hi + 1u; j <= upto; ++j)              // (per lane: nothing where hi >= upto)
                 sring[(j & (2u * ROLL_R - 1u)) * WAVE + (uint32_t)lane] = make_game_starts(seed, stream, W, fair, (uint32_t)env, ep0 + j);
             hi = max(hi, to);
         }
@@ -1174,7 +1186,7 @@ __device__ __forceinline__ void roll_helper(const Params &P, int env, bool autor
 
 template <bool TAPE, bool REC = false>
 __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uint32_t cpe, uint32_t flags, const StepOut &out,
-                                              int k_steps, unsigned char *smem, const int8_t *tape)
+                                              int k_steps, unsigned char *smem, const int8_t *tape, unsigned long long *emask)
 {
     const uint32_t sd = 2u * cpe + 1u;                              // dwords per board
     uint32_t *boards = reinterpret_cast<uint32_t *>(smem);          // [E][sd]
@@ -1224,9 +1236,13 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         const int ne = min(min(epw, E - we0), P.N - e0);            // this wave's envs (<= 0: none)
         mine = lane < ne;
         oenv = P.obs_state + (size_t)(mine ? env : 0) * 2u * G;
+        const bool masked = (flags & ROLL_ENTRY_MASKED) != 0u;      // (wave-uniform: a launch argument)
+        // the ordinals of block 0 that the game wave draws itself behind a masked entry (roll_helper: Starts)
+        const uint32_t game_starts = masked && autoreset ? (uint32_t)min(ROLL_GAME_STARTS, min(ROLL_R, k_steps)) : 0u;
         if (mine) {
             st = P.st4[env];
             if (autoreset) rs = P.rs4[env];
+            if (masked && !helper) mask = emask[env];
         }
         for (uint32_t d = (uint32_t)tid; d < 2u * cpe; d += blockDim.x) {
             // eight cells of the fresh board (G % 4 == 0: whole words; a word past G is read as the last one and not used)
@@ -1242,41 +1258,109 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         }
         __syncthreads();
         if (helper) {
-            roll_helper<TAPE>(P, env, autoreset, st, rs, k_steps, lane, aring, sring, cring, out, wave, gw, mine, tape);
+            roll_helper<TAPE>(P, env, autoreset, st, rs, k_steps, lane, aring, sring, cring, out, wave, gw, mine, tape, game_starts);
             return;
         }
-        // The wave reads its envs' player-1 planes one env at a time, lane = chunk (coalesced), packs them into the env's
-        // board and compares with the template: the ballot is the env's mask.  A plane byte outside the six codes cannot
-        // occur in mode None: the planes are written by k_obs_reset and the attach (code1 of a tile value: six codes, the
-        // slide tiles' among them), by the moves of obs_tile / k_inc / this kernel (the constants -2, -3, 10, -10) and from
-        // the fresh-board template (1 / -1), and the caller never writes the buffer — so the low nibble is the code.
-        const bool ck = (uint32_t)lane < cpe;
-        const int nb = G - lane * 16;                               // valid cells of this lane's chunk (G % 4 == 0)
-        const uint32_t t0 = ck ? tmpl[2 * lane] : 0u, t1 = ck ? tmpl[2 * lane + 1] : 0u;
-        // Loads in flight (unconditional, so that they are: a lane or an env past the end reads chunk 0 / the last env again).
-        // 16 in flight (95 VGPRs) measured no faster than 8 in either form of the benchmark (profiles/r10_rollout_ab.txt).
-        constexpr int PF = 8;
-        for (int e = 0; e < ne; e += PF) {
-            uint4 v[PF];
+        if (masked) {
+            // ---- the masked entry: the launch before this one left, per env, the mask its epilogue ended with (emask, below) —
+            // a superset of the chunks that differ from the template — and stored dirty & (mask | mask0), so memory outside
+            // that mask IS the template (a chunk of its mask0 that left its mask went through a restart: dirty, and stored
+            // from the template).  Nobody wrote the planes or st4 since (the host's flag behind ROLL_ENTRY_MASKED).  So a
+            // chunk outside the mask is entered as stale — the template, whatever its bytes in LDS say: no load, no pack,
+            // no LDS write — and only the mask's chunks are read.  mask0 = mask is then a superset of what differs in
+            // memory, which is all the epilogue's filter needs; "stale is a subset of dirty" does not hold for the
+            // chunks entered stale, and need not: they are the template in memory too, and whoever makes one dirty (a
+            // move's refresh, a restart) stores it by the same rules.  A lane without an env has an empty mask.
+            // The gather is the epilogue's list run backwards: the same seven-ballot prefix sum, the same wlist region
+            // (free until the epilogue), entries (owner lane, chunk); lane l of trip t loads entry 64 t + l, whoever owns
+            // it, packs it and writes the two dwords into the owner's board.  The loads of up to GF trips are all issued
+            // before the first is waited for: one exposed round trip per GF trips (T is 3.5 per env at 24x24 under random
+            // play: four trips).  Lanes write boards they do not own: fence and wave barrier as in the epilogue.
+            stale = ~mask & (cpe >= 64u ? ~0ull : (1ull << cpe) - 1ull);
+            unsigned long long m = mask;
+            const uint32_t cnt = (uint32_t)__popcll(m);
+            uint32_t pos = 0u, T = 0u;
 #pragma unroll
-            for (int j = 0; j < PF; ++j)
-                v[j] = load_chunk<true>(P.obs_state + (size_t)(e0 + min(e + j, ne - 1)) * 2u * G + (ck ? lane * 16 : 0));
-#pragma unroll
-            for (int j = 0; j < PF; ++j) {
-                if (e + j >= ne) break;
-                uint32_t p0 = 0u, p1 = 0u;
-                if (ck) {
-                    if (nb <= 4) v[j].y = 0u;                       // the over-read past G (the player-2 plane) is no board
-                    if (nb <= 8) v[j].z = 0u;
-                    if (nb <= 12) v[j].w = 0u;
-                    p0 = pack_codes8(v[j].x, v[j].y);
-                    p1 = pack_codes8(v[j].z, v[j].w);
-                    uint32_t *b = wboards + (size_t)(e + j) * sd + 2 * lane;
-                    b[0] = p0;
-                    b[1] = p1;
+            for (uint32_t b = 0; b < 7u; ++b) {
+                const unsigned long long bm = __ballot(((cnt >> b) & 1u) != 0u);
+                pos += __builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u)) << b;
+                T += (uint32_t)__popcll(bm) << b;
+            }
+            if (T) {
+                for (uint32_t p = pos; m; ++p) {
+                    wlist[p] = (uint16_t)(((uint32_t)lane << 6) | ((uint32_t)__ffsll((long long)m) - 1u));
+                    m &= m - 1ull;
                 }
-                const unsigned long long diff = __ballot(ck && (p0 != t0 || p1 != t1));
-                if (lane == e + j) mask = diff;
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                const int8_t *const obase = P.obs_state + (size_t)e0 * 2u * G;     // this wave's first env
+                constexpr uint32_t GF = 8u;
+                for (uint32_t t0 = 0u; t0 < T; t0 += 64u * GF) {                    // (t0 and T are wave-uniform)
+                    uint32_t ent[GF];
+                    uint4 v[GF];
+#pragma unroll
+                    for (uint32_t j = 0; j < GF; ++j) ent[j] = wlist[min(t0 + 64u * j + (uint32_t)lane, T - 1u)];
+#pragma unroll
+                    for (uint32_t j = 0; j < GF; ++j)                               // (a lane past T reads the last entry's chunk again)
+                        if (t0 + 64u * j < T)
+                            v[j] = load_chunk<true>(obase + (__umul24(ent[j] >> 6, 2u * (uint32_t)G) + (ent[j] & 63u) * 16u));
+#pragma unroll
+                    for (uint32_t j = 0; j < GF; ++j)
+                        if (t0 + 64u * j < T && t0 + 64u * j + (uint32_t)lane < T) {
+                            const uint32_t own = ent[j] >> 6, k = ent[j] & 63u;
+                            const int nb = G - (int)k * 16;                         // valid cells of the chunk (G % 4 == 0)
+                            if (nb <= 4) v[j].y = 0u;                               // the over-read past G (the player-2 plane) is no board
+                            if (nb <= 8) v[j].z = 0u;
+                            if (nb <= 12) v[j].w = 0u;
+                            uint32_t *b = wboards + __umul24(own, sd) + 2u * k;
+                            b[0] = pack_codes8(v[j].x, v[j].y);
+                            b[1] = pack_codes8(v[j].z, v[j].w);
+                        }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            }
+            // the last game_starts ordinals of block 0's (0, len_0], into the slots the helper leaves alone before P
+            if (game_starts) {
+                const uint32_t to = (uint32_t)min(ROLL_R, k_steps);
+#pragma nounroll
+                for (uint32_t j = to - game_starts + 1u; j <= to; ++j)
+                    sring[(j & (2u * ROLL_R - 1u)) * WAVE + (uint32_t)lane] = make_game_starts(P.seed, P.stream, P.W, P.fair, (uint32_t)env, rs.y + j);
+            }
+        } else {
+            // The wave reads its envs' player-1 planes one env at a time, lane = chunk (coalesced), packs them into the env's
+            // board and compares with the template: the ballot is the env's mask.  A plane byte outside the six codes cannot
+            // occur in mode None: the planes are written by k_obs_reset and the attach (code1 of a tile value: six codes, the
+            // slide tiles' among them), by the moves of obs_tile / k_inc / this kernel (the constants -2, -3, 10, -10) and from
+            // the fresh-board template (1 / -1), and the caller never writes the buffer — so the low nibble is the code.
+            const bool ck = (uint32_t)lane < cpe;
+            const int nb = G - lane * 16;                               // valid cells of this lane's chunk (G % 4 == 0)
+            const uint32_t t0 = ck ? tmpl[2 * lane] : 0u, t1 = ck ? tmpl[2 * lane + 1] : 0u;
+            // Loads in flight (unconditional, so that they are: a lane or an env past the end reads chunk 0 / the last env again).
+            // 16 in flight (95 VGPRs) measured no faster than 8 in either form of the benchmark (profiles/r10_rollout_ab.txt).
+            constexpr int PF = 8;
+            for (int e = 0; e < ne; e += PF) {
+                uint4 v[PF];
+#pragma unroll
+                for (int j = 0; j < PF; ++j)
+                    v[j] = load_chunk<true>(P.obs_state + (size_t)(e0 + min(e + j, ne - 1)) * 2u * G + (ck ? lane * 16 : 0));
+#pragma unroll
+                for (int j = 0; j < PF; ++j) {
+                    if (e + j >= ne) break;
+                    uint32_t p0 = 0u, p1 = 0u;
+                    if (ck) {
+                        if (nb <= 4) v[j].y = 0u;                       // the over-read past G (the player-2 plane) is no board
+                        if (nb <= 8) v[j].z = 0u;
+                        if (nb <= 12) v[j].w = 0u;
+                        p0 = pack_codes8(v[j].x, v[j].y);
+                        p1 = pack_codes8(v[j].z, v[j].w);
+                        uint32_t *b = wboards + (size_t)(e + j) * sd + 2 * lane;
+                        b[0] = p0;
+                        b[1] = p1;
+                    }
+                    const unsigned long long diff = __ballot(ck && (p0 != t0 || p1 != t1));
+                    if (lane == e + j) mask = diff;
+                }
             }
         }
         ROLL_HSTAMP(ROLL_HSTAMPS - 1);                              // (the game wave's arrival at P, in its helper's region)
@@ -1536,6 +1620,10 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         }
         ROLL_STAMP_LAUNCH(2);
         if (mine && st_dirty) P.st4[env] = st;
+        // The next launch's entry mask (the masked entry above): what differs from the template now lies inside mask, and the
+        // stores above left memory outside it the template.  Every env of the launch, a lane that did not step (the mask it
+        // entered with) included.
+        if (mine) emask[env] = mask;
         // rs4.envp / rs4.nenvp of an env that restarted, drawn here once instead of at every restart: nenvp belongs to the
         // game at the final `episode`; envp is what nenvp was before the env's last restart — the word the prologue read
         // after one restart (so what tron_set_weight_degree put into envp leaves with the first restart, as it always
@@ -1571,36 +1659,37 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
 // E envs per workgroup, epw (<= 64) per wave, blockDim.x / 64 waves; gridDim.x == ceil(N / E).  Mode None, int8 codes,
 // even side, cpe <= 64 (roll_resident).  TRON_ROLLOUT_RESIDENT asks for what this kernel does by itself; the flag is
 // accepted for its callers' sake.
-__global__ __launch_bounds__(2 * BLOCK) void k_obs_roll(Params P, int E, int epw, uint32_t cpe, uint32_t flags, StepOut out, int k_steps)
+__global__ __launch_bounds__(2 * BLOCK) void k_obs_roll(Params P, int E, int epw, uint32_t cpe, uint32_t flags, StepOut out, int k_steps,
+                                                        unsigned long long *__restrict__ emask)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // The step's parameters are re-read from the kernel-argument segment at every step (scalar loads through a pointer the
     // compiler cannot see through) instead of kept live across the loop: 26 words of Params in SGPRs for the whole launch
     // spill, and every spilled word is a v_readlane per use.
     kernarg_t *kp = (kernarg_t *)__builtin_amdgcn_kernarg_segment_ptr();       // (Params is the first argument)
-    roll_resident<false>(kp, E, epw, cpe, flags & ~TRON_ROLLOUT_RESIDENT, out, k_steps, smem, nullptr);
+    roll_resident<false>(kp, E, epw, cpe, flags & ~TRON_ROLLOUT_RESIDENT, out, k_steps, smem, nullptr, emask);
 }
 
 // The same launch with the caller's actions (tron_rollout_actions): the second instantiation of roll_resident.  Its game
 // waves run k_obs_roll's loop on bytes of the same ring; only its helper differs (roll_helper<true>), and tape points at the
 // launch's own first step.
 __global__ __launch_bounds__(2 * BLOCK) void k_obs_roll_tape(Params P, int E, int epw, uint32_t cpe, uint32_t flags, StepOut out, int k_steps,
-                                                             const int8_t *__restrict__ tape)
+                                                             const int8_t *__restrict__ tape, unsigned long long *__restrict__ emask)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     kernarg_t *kp = (kernarg_t *)__builtin_amdgcn_kernarg_segment_ptr();       // (Params is the first argument: see k_obs_roll)
-    roll_resident<true>(kp, E, epw, cpe, flags, out, k_steps, smem, tape);
+    roll_resident<true>(kp, E, epw, cpe, flags, out, k_steps, smem, tape, emask);
 }
 
 // k_obs_roll_tape with the per-step records (tron_rollout_actions_records): the third instantiation of roll_resident.  Same
 // step loop, same helper; out.done / out.winner / out.reward are step-major tapes here and point, like tape, at the launch's
 // own first step.
 __global__ __launch_bounds__(2 * BLOCK) void k_obs_roll_tape_rec(Params P, int E, int epw, uint32_t cpe, uint32_t flags, StepOut out, int k_steps,
-                                                                 const int8_t *__restrict__ tape)
+                                                                 const int8_t *__restrict__ tape, unsigned long long *__restrict__ emask)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     kernarg_t *kp = (kernarg_t *)__builtin_amdgcn_kernarg_segment_ptr();       // (Params is the first argument: see k_obs_roll)
-    roll_resident<true, true>(kp, E, epw, cpe, flags, out, k_steps, smem, tape);
+    roll_resident<true, true>(kp, E, epw, cpe, flags, out, k_steps, smem, tape, emask);
 }
 
 // Fewer workgroups than tiles (the TRON_ROLL_GRID override): workgroup w owns tiles w, w + gridDim.x, ... and
@@ -2044,11 +2133,19 @@ struct tron_env {
     int part0, nparts;        // slice of the tiles the next launch covers (0, 1 = all of them)
     int roll_E;               // envs per tile of the persistent rollout (0: not chosen yet), see roll_tile_envs
     int roll_waves;           // waves per workgroup of k_obs_roll (0: not chosen yet), see roll_waves
+    unsigned long long *emask; // [N] in the blob: k_obs_roll's entry masks, written by every launch of the roll_resident family
+    bool entry_masks;         // the entry masks describe the attached planes: the last call that could write the planes or the
+                              // state words enqueued was such a launch over all envs (set in rollout_wave, cleared by
+                              // planes_written; it follows the order of the calls, as the planes follow the order of the stream)
 };
 
 namespace {
 
 inline hipStream_t S_(void *s) { return reinterpret_cast<hipStream_t>(s); }
+
+// Every entry point that can write the planes or the state words other than through the roll_resident family: k_obs_roll's
+// next launch reads whole planes again.
+inline void planes_written(tron_env *h) { h->entry_masks = false; }
 
 inline int launch_status()
 {
@@ -2237,6 +2334,7 @@ int tron_create(int32_t n_envs, int32_t W, int32_t mode, int32_t fair, uint32_t 
     P.r_step = -1.0f; P.r_win = 100.0f; P.r_lose = -100.0f; P.r_draw = 0.0f; P.r_index = 0;   // DDQN.py:289-305
     h->device = dev;
     h->side = nullptr; h->fork = nullptr; h->join = nullptr; h->part0 = 0; h->nparts = 1;
+    h->entry_masks = false;
     h->aligned = (P.G % 4) == 0;
     h->cpe = ((uint32_t)P.G + 15u) / 16u;
     h->cpe_magic = (uint32_t)((0x100000000ull + h->cpe - 1) / h->cpe);   // exact i / cpe for i < 2^32 / cpe
@@ -2258,7 +2356,7 @@ int tron_create(int32_t n_envs, int32_t W, int32_t mode, int32_t fair, uint32_t 
     const size_t log_bytes = P.mode != TRON_MODE_NONE ? N * (size_t)slide_log_len(P.W) * sizeof(uint16_t) : 0;
     const size_t o_grid = 0, o_st4 = align(o_grid + N * P.G + 64), o_rs4 = align(o_st4 + 16 * N),
                  o_slide = align(o_rs4 + 16 * N), o_log = align(o_slide + 8 * N), o_fresh = align(o_log + log_bytes),
-                 total = align(o_fresh + (size_t)P.G + 16);
+                 o_emask = align(o_fresh + (size_t)P.G + 16), total = align(o_emask + 8 * N);
     char *blob = nullptr;
     if (hipMalloc(reinterpret_cast<void **>(&blob), total) != hipSuccess) {
         (void)hipGetLastError();
@@ -2272,6 +2370,7 @@ int tron_create(int32_t n_envs, int32_t W, int32_t mode, int32_t fair, uint32_t 
     P.slide = reinterpret_cast<double *>(blob + o_slide);
     P.obs_state = nullptr;
     P.fresh = reinterpret_cast<const int8_t *>(blob + o_fresh);
+    h->emask = reinterpret_cast<unsigned long long *>(blob + o_emask);
     if (hipMemsetAsync(blob, 0, total, nullptr) != hipSuccess) { (void)hipGetLastError(); }
     hipLaunchKernelGGL(k_fresh, dim3((P.G + 255) / 256), dim3(256), 0, nullptr, const_cast<int8_t *>(P.fresh), P.S);
     hipLaunchKernelGGL(k_fill_f64, dim3((n_envs + 255) / 256), dim3(256), 0, nullptr, P.slide, 0.15,
@@ -2325,6 +2424,7 @@ int tron_set_slide(tron_handle h, double slide, const double *slide_dev, void *s
 int tron_set_weight_degree(tron_handle h, const int16_t *weight, const int16_t *degree, void *stream)
 {
     if (bad_handle(h)) return h ? TRON_ERR_NO_DEVICE : TRON_ERR_BAD_ARG;
+    planes_written(h);              // (rs4 only, which no entry mask describes: cleared all the same, the call is rare)
     hipLaunchKernelGGL(k_set_wd, dim3((h->P.N + 255) / 256), dim3(256), 0, S_(stream), h->P, weight, degree);
     return launch_status();
 }
@@ -2333,6 +2433,7 @@ int tron_reset(tron_handle h, const int8_t *env_mask, const int8_t *start_pos, c
                const int16_t *degree, void *stream)
 {
     if (bad_handle(h)) return h ? TRON_ERR_NO_DEVICE : TRON_ERR_BAD_ARG;
+    planes_written(h);
     const int per = BLOCK / 64;
     hipLaunchKernelGGL(k_reset, dim3((h->P.N + per - 1) / per), dim3(BLOCK), 0, S_(stream), h->P, env_mask, start_pos,
                        weight, degree);
@@ -2347,6 +2448,7 @@ int tron_attach_obs_state(tron_handle h, int8_t *obs_codes, void *stream)
     if (!obs_codes || (reinterpret_cast<uintptr_t>(obs_codes) & 15u)) return TRON_ERR_BAD_ARG;
     if (!h->aligned || h->P.G >= 0x3FFF) return TRON_ERR_UNSUPPORTED;                 // (cell + 1 travels in 14 bits: restart word, slide marks)
     if (h->P.obs_state) return TRON_ERR_BAD_ARG;                                      // already attached
+    planes_written(h);
     h->P.obs_state = obs_codes;
     const int per = BLOCK / 64;     // derive the planes from the boards as they are now
     hipLaunchKernelGGL(k_obs_reset, dim3((h->P.N + per - 1) / per), dim3(BLOCK), 0, S_(stream), h->P,
@@ -2363,6 +2465,7 @@ int tron_step_encode(tron_handle h, const int8_t *actions, const float *uniforms
     if ((obs_fmt != TRON_OBS_NONE) != (obs != nullptr)) return TRON_ERR_BAD_ARG;
     if (flags & ~(TRON_STEP_AUTORESET | TRON_STEP_INCREMENTAL | TRON_STEP_NONREVERSING)) return TRON_ERR_BAD_ARG;
     if ((flags & TRON_STEP_INCREMENTAL) && (!h->P.obs_state || h->P.mode != TRON_MODE_NONE)) return TRON_ERR_UNSUPPORTED;
+    planes_written(h);              // tron_step, the part steps and the incremental path (k_inc) all come through here
     StepOut out{out_done, out_winner, out_reward, nullptr};
     if (h->P.obs_state) {
         if (obs_fmt == TRON_OBS_CODES_I8 && obs != h->P.obs_state) return TRON_ERR_BAD_ARG;   // the attached buffer is the output
@@ -2527,7 +2630,7 @@ size_t roll_smem(const tron_env *h, int E, int waves)
 // tape: null for k_obs_roll's own draws; else the caller's int8[k_steps][N][2], and every launch gets it advanced to its
 // own first step (k_obs_roll_tape: same grid, same workgroup, same LDS).  A tape call that asks for records (any of
 // out.done / out.winner / out.reward) runs k_obs_roll_tape_rec, and its launches get the record tapes advanced by the same rows.
-int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipStream_t st, int E, int waves, int chunk,
+int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags_in, StepOut out, hipStream_t st, int E, int waves, int chunk,
                  const int8_t *tape = nullptr)
 {
     if (waves < 1) waves = 1;
@@ -2544,6 +2647,8 @@ int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipS
     if (tape && !rec) allow_big_lds(reinterpret_cast<const void *>(k_obs_roll_tape), h->device, prepared_t);
     static uint64_t prepared_r = 0;
     if (rec) allow_big_lds(reinterpret_cast<const void *>(k_obs_roll_tape_rec), h->device, prepared_r);
+    // TRON_ROLL_FULL_ENTRY: every launch reads whole planes, as if no entry mask were valid (A/B runs, the tests' twin)
+    static const bool full_entry = getenv("TRON_ROLL_FULL_ENTRY") != nullptr;
     static bool report = getenv("TRON_ROLL_REPORT") != nullptr;         // the launch shape and its occupancy on stderr, once per process
     if (report) {
         report = false;
@@ -2556,18 +2661,23 @@ int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipS
         (void)hipGetLastError();
     }
     for (int left = k_steps; left > 0; left -= chunk) {
+        // The launch covers all envs (grid x E >= N) and writes every env's entry mask; the one behind it on the stream may
+        // enter by them.  Nothing is assumed of a launch that failed.
+        const uint32_t flags = flags_in | (h->entry_masks && !full_entry ? ROLL_ENTRY_MASKED : 0u);
+        h->entry_masks = false;
         if (rec) {
             const size_t at = (size_t)(k_steps - left) * (size_t)h->P.N;   // the launch's first row, in envs
             const StepOut rows{out.done ? out.done + at : nullptr, out.winner ? out.winner + at : nullptr,
                                out.reward ? out.reward + 2u * at : nullptr, out.totals};
             hipLaunchKernelGGL(k_obs_roll_tape_rec, dim3(grid), dim3(2 * waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, rows,
-                               left < chunk ? left : chunk, tape + 2u * at);
+                               left < chunk ? left : chunk, tape + 2u * at, h->emask);
         } else if (tape)
             hipLaunchKernelGGL(k_obs_roll_tape, dim3(grid), dim3(2 * waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, out,
-                               left < chunk ? left : chunk, tape + (size_t)(k_steps - left) * 2u * (size_t)h->P.N);
+                               left < chunk ? left : chunk, tape + (size_t)(k_steps - left) * 2u * (size_t)h->P.N, h->emask);
         else
-            hipLaunchKernelGGL(k_obs_roll, dim3(grid), dim3(2 * waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, out, left < chunk ? left : chunk);
+            hipLaunchKernelGGL(k_obs_roll, dim3(grid), dim3(2 * waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, out, left < chunk ? left : chunk, h->emask);
         if (launch_status() != TRON_OK) return TRON_ERR_LAUNCH;
+        h->entry_masks = true;
     }
     return TRON_OK;
 }
@@ -2598,6 +2708,7 @@ int rollout_persistent(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out
         if (!(env_grid > 0 && env_grid < (h->P.N + E - 1) / E)) return rollout_wave(h, k_steps, flags, out, st, E, waves, chunk, tape);
     }
     if (tape) return TRON_ERR_UNSUPPORTED;
+    planes_written(h);              // k_obs_roll_walk, k_obs_roll_slide
     static uint64_t prepared_w = 0;
     allow_big_lds(reinterpret_cast<const void *>(k_obs_roll_walk), h->device, prepared_w);
     if (!h->roll_E) h->roll_E = roll_tile_envs(h);
@@ -2641,6 +2752,7 @@ int rollout_launches(tron_env *h, int32_t k_steps, uint32_t flags, int32_t obs_f
         return TRON_OK;
     }
     flags &= ~TRON_ROLLOUT_RESIDENT;                               // only k_obs_roll knows it
+    planes_written(h);              // k_tile_roll, two streams, one launch per step
     if (!h->P.obs_state && !per_step && k_steps > 1) {             // board-owning layout: same idea, k_tile_roll
         for (int left = k_steps; left > 0; left -= TRON_ROLLOUT_CHUNK) {
             const int rc = launch_roll_fmt(h, obs_fmt, left < TRON_ROLLOUT_CHUNK ? left : TRON_ROLLOUT_CHUNK, flags, obs, out, st);
@@ -2731,6 +2843,7 @@ int tron_rollout_actions_records(tron_handle h, int32_t k_steps, const int8_t *a
         if (rc != TRON_ERR_UNSUPPORTED) return rc;                   // (boards past 64 chunks, a TRON_ROLL_GRID override: below)
     }
     // everywhere else: tron_step_encode's launch with row k, and the totals tron_rollout_random's per-step form keeps
+    planes_written(h);
     const size_t row = 2u * (size_t)h->P.N, n = (size_t)h->P.N;
     for (int k = 0; k < k_steps; ++k) {
         const int rc = h->P.obs_state ? launch_obs<true>(h, actions + k * row, TRON_STEP_AUTORESET, out, st)

@@ -173,7 +173,24 @@ int tron_encode(tron_handle h, int32_t obs_fmt, void *obs, void *stream);
  * the chip and writes the planes (and the state words) at its end, so nothing that
  * runs beside it — another stream, the host through a mapped buffer — sees the steps
  * in between; work queued behind the call on `stream` sees the last step as before.
- * TRON_ROLLOUT_PER_STEP is the form whose every step is in memory.               */
+ * TRON_ROLLOUT_PER_STEP is the form whose every step is in memory.
+ * Entry masks.  Every such launch (this call's, tron_rollout_actions' and
+ * tron_rollout_actions_records') also leaves, in the handle, one 64-bit mask per env:
+ * the 16-byte chunks of its player-1 plane that may differ from a fresh board.  The
+ * next launch of that family reads only those chunks instead of every whole plane,
+ * provided no other call that can write the planes or the state words was made on the
+ * handle in between: tron_reset, tron_step / tron_step_encode(_part) (the incremental
+ * path included), tron_attach_obs_state, tron_set_weight_degree and every rollout that
+ * does not run as persistent mode-None launches (one step, TRON_ROLLOUT_PER_STEP,
+ * TRON_ROLLOUT_TWO_STREAMS, the sliding modes, boards of more than 64 chunks) make the
+ * next launch read whole planes again.  That holds between the launches of one call of
+ * more than TRON_ROLLOUT_CHUNK steps and between consecutive calls.  The host keeps
+ * this as one flag per handle that follows the ORDER OF THE CALLS, as the planes
+ * themselves follow the order of the work on the stream: calls on one handle are
+ * enqueued on streams that order them (one stream, or events), as they already must
+ * be for the planes to mean anything.  Results are the same bit for bit either way;
+ * the environment variable TRON_ROLL_FULL_ENTRY (read once per process) makes every
+ * launch read whole planes, for A/B measurements.                                  */
 int tron_rollout_random(tron_handle h, int32_t k_steps, uint32_t flags, int32_t obs_fmt, void *obs,
                         unsigned long long *totals, void *stream);
 
