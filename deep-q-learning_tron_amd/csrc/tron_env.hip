@@ -967,16 +967,23 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 
 // The steps of a persistent launch (k_obs_roll): ONE LANE = ONE ENV for the whole launch, and a wave owns its envs from the
 // prologue to the epilogue.  Nobody else touches an env's planes or state words during the launch, and nobody can read them
-// before it ends, so everything a step reads or writes is carried from the step before: st4, rs4 and the Philox words of the
-// block's actions in the lane's registers, the board in the lane's own region of LDS (4 bits per cell, above).  The game
+// before it ends, so everything a step reads or writes is carried from the step before: the env's state, rs4 and the
+// block's action bytes in the lane's registers, the board in the lane's own region of LDS (4 bits per cell, above).
+// The state is carried DECODED: the two heads' r and c (collide and settle take them), their cell indices, the LDS address
+// and nibble shift of each head's dword and its chunk's mask bit, alive, done, winner, the two last actions + 1 (the
+// non-reversing policy), eplen and tick.  The prologue unpacks st4 into them once; a step moves a head's cell by +-1 or
+// +-S and derives the rest of the new head from that, and the old heads' cells, addresses and bits are simply the ones the
+// step before computed; a restart sets them all from rs4.nstart; the epilogue packs st4 once, under st_dirty, into the bytes
+// stepped_st4 / restarted_st4 of the env's last event would have left.  The helper reads st and rs as loaded.  The game
 // wave does the move, a restarted env's board, the records and the lane's tally of the totals; what is random — the actions
 // of every step and the starts of every restarted env's next game — its helper wave draws ahead of it into rings in LDS
 // (roll_helper above: the rings, their invariants and the barriers).  The step loop has ONE workgroup barrier per block of
 // ROLL_R steps and none inside a block; no lane touches another lane's board, and the game waves of a workgroup share the
 // fresh-board template only, built in the prologue.  Memory is read in the prologue only and the planes are written in the epilogue only: the loop holds
 // no global load, no s_waitcnt vmcnt and no plane store (with every CU storing 8 scattered 16-byte chunks per env-step the
-// shared store path set the launch time: profiles/r10_rollout_ab.txt, r11_rollout_ab.txt).  The parameters are re-read per
-// step with scalar loads (load_params_scalar).
+// shared store path set the launch time: profiles/r10_rollout_ab.txt, r11_rollout_ab.txt).  Of the parameters the loop
+// needs S and W alone, two SGPRs for the whole launch; REC re-reads N and the reward table per step with scalar loads
+// (load_params_scalar).  A block's steps are an inner loop of their own: the block-start branch is outside it.
 // What the caller sees: when the launch completes on its stream the buffer holds the observations of its last step, exactly
 // the bytes one store per step would have left; until a wave's epilogue its envs' planes hold what the launch began with.
 // LDS: an env's board takes 2 cpe + 1 dwords — odd, so that the same dword of the boards of the 64 lanes falls on 64
@@ -995,10 +1002,12 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 // only the head chunks are written, straight-line — the template's two dwords each, the head nibbles XORed in in registers —
 // and leave stale.  Most of a trail's chunks are never looked at again before the next restart; the few that are, are known
 // at the moment they are looked at:
-// A move reads four cells, and only the two new heads can lie in a stale chunk (the old heads' chunks are in mask).  The
-// template's chunks of the two new heads are read in the same LDS round trip as the four bytes; where the chunk is stale the
-// cell's byte is taken from the template, and the chunk is refreshed (the template's two dwords) in front of the four cell
-// writes and leaves stale.  plain_targets and collide so see what the wiped board would have shown, an out-of-bounds head on
+// A move reads the two new heads' cells alone, one dword each (the old heads' cells are only overwritten), and only a new
+// head can lie in a stale chunk (the old heads' chunks are in mask).  The template's chunks of the two new heads are read in
+// the same LDS round trip as the two dwords; where the chunk is stale the cell's nibble is taken from the template, and the
+// chunk is refreshed (the template's two dwords) in front of the four cell writes and leaves stale.  The four writes are
+// four ds_mskor_b32 (lds_set_nibble: memory = (memory & ~mask) | data on the cell's dword) in the reference's order; a
+// lane's LDS operations execute in order, so cells that share a dword need no merging in registers.  plain_targets and collide so see what the wiped board would have shown, an out-of-bounds head on
 // the border wall and both heads in one stale chunk included.  A move marks the chunks of its four cells in mask and dirty.
 // A lane writes only its own board in the loop, so the loop needs no fence and no wave barrier.
 // The epilogue stores dirty & (mask | mask0), mask0 being the mask the prologue built: a chunk outside both is the template
@@ -1032,15 +1041,15 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 // leaves behind).
 // The records.  REC (k_obs_roll_tape_rec, tron_rollout_actions_records) stores what every step computes anyway — done,
 // winner and, when out.reward is asked for, the two rewards — into the caller's step-major tapes: out.done / out.winner are
-// int8[k_steps][N], out.reward float2[k_steps][N], the launch's own first step at row 0, any of them null.  The row
-// pointers are wave-uniform and are carried forward by N per step (no multiply in the loop); a lane adds its env: per wave
+// int8[k_steps][N], out.reward float2[k_steps][N], the launch's own first step at row 0, any of them null.  The row's
+// offset is wave-uniform and is carried forward by N per step (no multiply in the loop); a lane adds its env: per wave
 // and step 64 contiguous bytes of done, 64 of winner, 512 of reward.  The stores are fire-and-forget: the loop still loads
 // nothing from memory and waits for nothing, a null tape costs a uniform branch, a lane without an env stores nothing and the
 // helper waves store no records.  Row s is what the s-th tron_step_encode with autoreset records, an env that is finished
 // when the step begins included: done 1, its old winner, rewards 0.
-// Without REC (k_obs_roll, k_obs_roll_tape) the three stores are indexed by env alone, as the per-step kernels have them,
-// and no caller reaches them: tron_rollout_random and tron_rollout_actions pass out.totals only, and a call that asks for
-// records runs the REC instantiation.  tron_rollout_random always sets TRON_STEP_AUTORESET, and so do the tape calls: the
+// Without REC (k_obs_roll, k_obs_roll_tape) the loop holds no record store, no step_rewards and no load of the reward
+// table: tron_rollout_random and tron_rollout_actions pass out.totals only, and a call that asks for records runs the REC
+// instantiation.  tron_rollout_random always sets TRON_STEP_AUTORESET, and so do the tape calls: the
 // !autoreset branches below are run by no caller and no test.
 // ---- the helper wave of k_obs_roll -------------------------------------------------------------------------------------------
 // A launch's steps come in blocks of ROLL_R.  Per game wave the helper keeps two rings in LDS:
@@ -1184,6 +1193,19 @@ __device__ __forceinline__ void roll_helper(const Params &P, int env, bool autor
     }
 }
 
+// cell_index for the resident loop's prologue: r + 1 and S are small, one 24-bit multiply-add
+__device__ __forceinline__ int roll_cell(int S, int r, int c) { return __mul24(r + 1, S) + (c + 1); }
+// One cell of a packed board in LDS, given the board's LDS byte address: memory = (memory & ~mask) | data on the cell's
+// dword (lds_cell_dword, lds_cell_shift), the nibble's four bits.  One instruction, nothing read back; a lane's LDS operations execute in order, and the
+// memory clobber keeps the compiler's own LDS accesses on their side of it.
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
+__device__ __forceinline__ uint32_t lds_cell_dword(uint32_t board_lds, uint32_t cell) { return board_lds + (cell >> 3) * 4u; }
+__device__ __forceinline__ uint32_t lds_cell_shift(uint32_t cell) { return (cell & 7u) * 4u; }
+__device__ __forceinline__ void lds_set_nibble(uint32_t dword_lds, uint32_t shift, uint32_t nib)
+{
+    asm volatile("ds_mskor_b32 %0, %1, %2" : : "v"(dword_lds), "v"(0xFu << shift), "v"(nib << shift) : "memory");
+}
+
 template <bool TAPE, bool REC = false>
 __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uint32_t cpe, uint32_t flags, const StepOut &out,
                                               int k_steps, unsigned char *smem, const int8_t *tape, unsigned long long *emask)
@@ -1226,6 +1248,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
     uint32_t nres = 0u;                                             // this env's restarts in the launch
     uint32_t n_steps = 0u, n_w1 = 0u, n_w2 = 0u, n_draw = 0u;        // this wave's totals (uniform)
     uint32_t tally = 0u;                                            // this env's share of them, a byte each, since the last flush
+    int S = 0, W = 0;                                               // all the step loop needs of Params: two SGPRs for the whole launch
 
     ROLL_STAMP_LAUNCH(0);
     // ---- prologue: the only loads from memory of the launch
@@ -1233,6 +1256,8 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         Params P;
         load_params_scalar(P, kp);
         const int G = P.G;
+        S = P.S;
+        W = P.W;
         const int ne = min(min(epw, E - we0), P.N - e0);            // this wave's envs (<= 0: none)
         mine = lane < ne;
         oenv = P.obs_state + (size_t)(mine ? env : 0) * 2u * G;
@@ -1368,176 +1393,193 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
     }
     const unsigned long long mask0 = mask;                          // chunks that differ from the template IN MEMORY until the epilogue
     // REC: the record tapes' rows of the step being played (wave-uniform; the launch's own first step is row 0)
-    int8_t *row_done = REC ? out.done : nullptr, *row_winner = REC ? out.winner : nullptr;
-    float2 *row_reward = REC ? reinterpret_cast<float2 *>(out.reward) : nullptr;
+    size_t row = 0;                                                 // in envs: N per step (no multiply in the loop)
 
-    for (int s = 0; s < k_steps; ++s) {
-        if ((s & (ROLL_R - 1)) == 0) {
-            // ---- a block begins.  The one barrier per block: behind it the helper has this block's action bytes and the
-            // starts of the restart ordinals up to nres + ROLL_R in the rings, and may overwrite what the block before
-            // read; in front of it this lane publishes its restart count for the helper's next draws.
-            if (s) {
-                if (out.totals && (s & 127) == 0) roll_flush_tally(tally, n_steps, n_w1, n_w2, n_draw);
-                cring[((s / ROLL_R) & 1) * WAVE + lane] = nres;
-                __syncthreads();
-            }
-            ab = aring[((s / ROLL_R) & 1) * WAVE + lane];
+    // ---- the env's state, decoded once: the loop carries these in place of st and the epilogue packs them again
+    int r[2], c[2];                                                 // the heads (a dead player's may be off the board)
+    unpack_pos(st.x, r, c);
+    int cell[2] = {roll_cell(S, r[0], c[0]), roll_cell(S, r[1], c[1])};
+    unsigned long long hbit[2] = {1ull << (cell[0] >> 4), 1ull << (cell[1] >> 4)};   // the heads' chunks, as mask bits
+    uint32_t alive = st.y & 3u;
+    bool done = (st.y & META_DONE) != 0u;
+    int winner = (int)((st.y >> 4) & 3u);
+    uint32_t last[2] = {(st.y >> 8) & 0xFu, (st.y >> 12) & 0xFu};   // the players' last actions + 1, 0 before a game's first move
+    uint32_t eplen = st.z, tick = st.w;
+    const uint32_t board_lds = (uint32_t)(uintptr_t)(lds_u32 *)board;
+    uint32_t hdw[2] = {lds_cell_dword(board_lds, (uint32_t)cell[0]), lds_cell_dword(board_lds, (uint32_t)cell[1])};   // the heads' dwords in LDS
+    uint32_t hsh[2] = {lds_cell_shift((uint32_t)cell[0]), lds_cell_shift((uint32_t)cell[1])};                         // and their nibbles' shifts
+
+    for (int s0 = 0; s0 < k_steps; s0 += ROLL_R) {
+        // ---- a block begins.  The one barrier per block: behind it the helper has this block's action bytes and the
+        // starts of the restart ordinals up to nres + ROLL_R in the rings, and may overwrite what the block before
+        // read; in front of it this lane publishes its restart count for the helper's next draws.
+        if (s0) {
+            if (out.totals && (s0 & 127) == 0) roll_flush_tally(tally, n_steps, n_w1, n_w2, n_draw);
+            cring[((s0 / ROLL_R) & 1) * WAVE + lane] = nres;
+            __syncthreads();
         }
-        Params P;                                                   // re-read per step: see k_obs_roll
-        load_params_scalar(P, kp);
-        const int S = P.S, W = P.W, G = P.G;
-        ROLL_STAMP(0);
+        ab = aring[((s0 / ROLL_R) & 1) * WAVE + lane];
+        const int s1 = min(s0 + ROLL_R, k_steps);
+#pragma nounroll
+        for (int s = s0; s < s1; ++s) {                             // the block's steps: ab.x's low byte is this step's
+            Params P;                                                   // REC alone: N and the reward table, re-read per step (see k_obs_roll)
+            if constexpr (REC) load_params_scalar(P, kp);
+            ROLL_STAMP(0);
 
-        // ---- the move: lane_move_codes on the packed board (nibble reads, byte-sharing writes, the chunk masks)
-        bool stepped = false;
-        bool done = (st.y & META_DONE) != 0u;
-        int winner = (int)((st.y >> 4) & 3u);
-        float rw0 = 0.0f, rw1 = 0.0f;
-        if (mine && !done) {
-            stepped = true;
-            const uint32_t abyte = (uint32_t)(((((unsigned long long)ab.y) << 32) | ab.x) >> ((uint32_t)(s & (ROLL_R - 1)) * 8u)) & 0xFFu;
-            const int a[2] = {draw_action_byte(abyte, 0, (st.y >> 8) & 0xFu, nonrev), draw_action_byte(abyte, 1, (st.y >> 12) & 0xFu, nonrev)};
-            int r[2], c[2];
-            unpack_pos(st.x, r, c);
-            int cells[4];                                            // the old heads, the new ones
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                int dr, dc;
-                action_delta(a[p], dr, dc);
-                cells[p] = cell_index(S, r[p], c[p]);
-                r[p] += dr;
-                c[p] += dc;
-                cells[2 + p] = cell_index(S, r[p], c[p]);
-            }
-            // One LDS round trip: the bytes of the four cells and the template's chunks of the two new heads.  Only a new
-            // head can lie in a stale chunk (the old heads' chunks are in mask); its byte then comes from the template, which
-            // is what the chunk holds once it is refreshed below.
-            uint32_t b[4], tc[2][2];
-            bool sl[2];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) b[k] = cellb[cells[k] >> 1];
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const uint32_t k = (uint32_t)cells[2 + p] >> 4;
-                tc[p][0] = tmpl[2u * k];
-                tc[p][1] = tmpl[2u * k + 1u];
-                sl[p] = ((stale >> k) & 1ull) != 0ull;
-            }
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const uint32_t bi = ((uint32_t)cells[2 + p] >> 1) & 7u;          // the cell's byte within its chunk
-                const uint32_t tb = (uint32_t)((((unsigned long long)tc[p][1] << 32) | tc[p][0]) >> (bi * 8u)) & 0xFFu;
-                b[2 + p] = sl[p] ? tb : b[2 + p];
-            }
-            uint32_t tf[2];
-#pragma unroll
-            for (int p = 0; p < 2; ++p) tf[p] = (b[2 + p] >> ((cells[2 + p] & 1) * 4)) & 15u;
-            plain_targets(cells, cells + 2, tf, NIB_P1_BODY, NIB_P2_BODY, NIB_P1_HEAD);
-            uint32_t alive = st.y & 3u;
-#pragma unroll
-            for (int p = 0; p < 2; ++p) alive = collide(alive, p, W, r[p], c[p], tf[p] == NIB_EMPTY);
-            done = settle(alive, r, c, winner);
-            if (out.reward) step_rewards(P, done, winner, st.z, rw0, rw1);
-            st = stepped_st4(r, c, pack_meta(alive, done, winner, a[0], a[1]), st.z, st.w);
-            st_dirty = true;
-            if (!(done && autoreset)) {
-                // the writes in the reference's order: bodies, then P1's head, then P2's (an out-of-bounds head lands on
-                // the border WALL cell; a same-cell head-on leaves P2's head).  Cells that share a byte: a later write
-                // starts from the earlier one's byte, and same-lane LDS writes keep their order.
-                // A new head's stale chunk is refreshed first: the template's two dwords, then the cell writes on top (both
-                // heads in one stale chunk write the same dwords twice).
+            // ---- the move: lane_move_codes on the packed board (two dword reads, masked-OR writes, the chunk masks)
+            const bool stepped = mine && !done;
+            float rw0 = 0.0f, rw1 = 0.0f;
+            if (stepped) {
+                const uint32_t abyte = ab.x & 0xFFu;
+                const int a[2] = {draw_action_byte(abyte, 0, last[0], nonrev), draw_action_byte(abyte, 1, last[1], nonrev)};
+                int ncell[2];                                            // the new heads: the old ones' cells +-1 or +-S
+                unsigned long long nbit[2];
+                uint32_t nk[2], ndw[2], nsh[2];
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
-                    const uint32_t k = (uint32_t)cells[2 + p] >> 4;
-                    if (sl[p]) {
-                        board[2u * k] = tc[p][0];
-                        board[2u * k + 1u] = tc[p][1];
-                        stale &= ~(1ull << k);
+                    int dr, dc;
+                    action_delta(a[p], dr, dc);
+                    r[p] += dr;
+                    c[p] += dc;
+                    ncell[p] = cell[p] + __mul24(dr, S) + dc;
+                    nk[p] = (uint32_t)ncell[p] >> 4;
+                    asm("" : "+v"(nk[p]));                           // (the chunk index as one value: its two dwords are one ds_read2 / ds_write2)
+                    nbit[p] = 1ull << nk[p];
+                    ndw[p] = lds_cell_dword(board_lds, (uint32_t)ncell[p]);
+                    nsh[p] = lds_cell_shift((uint32_t)ncell[p]);
+                }
+                // One LDS round trip: the dwords of the two new heads and the template's chunks of theirs.  Only a new head can
+                // lie in a stale chunk (the old heads' chunks are in mask); its nibble then comes from the template, which is
+                // what the chunk holds once it is refreshed below.  The old heads' cells are not read: they are overwritten.
+                uint32_t bw[2], tc0[2], tc1[2];                  // (two arrays: each is indexed by the player alone)
+                bool sl[2];
+#pragma unroll
+                for (int p = 0; p < 2; ++p) {
+                    bw[p] = *(lds_u32 *)(uintptr_t)ndw[p];
+                    tc0[p] = tmpl[2u * nk[p]];
+                    tc1[p] = tmpl[2u * nk[p] + 1u];
+                    sl[p] = (stale & nbit[p]) != 0ull;
+                }
+                uint32_t tf[2];
+#pragma unroll
+                for (int p = 0; p < 2; ++p) {
+                    const uint32_t tw = (ncell[p] & 8) ? tc1[p] : tc0[p];
+                    tf[p] = ((sl[p] ? tw : bw[p]) >> nsh[p]) & 15u;
+                }
+                plain_targets(cell, ncell, tf, NIB_P1_BODY, NIB_P2_BODY, NIB_P1_HEAD);
+#pragma unroll
+                for (int p = 0; p < 2; ++p) alive = collide(alive, p, W, r[p], c[p], tf[p] == NIB_EMPTY);
+                done = settle(alive, r, c, winner);
+                if constexpr (REC)
+                    if (out.reward) step_rewards(P, done, winner, eplen, rw0, rw1);
+                last[0] = (uint32_t)a[0] + 1u;
+                last[1] = (uint32_t)a[1] + 1u;
+                eplen += 1u;
+                tick += 1u;
+                st_dirty = true;
+                if (!(done && autoreset)) {
+                    // the writes in the reference's order: bodies, then P1's head, then P2's (an out-of-bounds head lands on
+                    // the border WALL cell; a same-cell head-on leaves P2's head).  Each is one masked OR on the cell's dword;
+                    // same-lane LDS operations keep their order, so a later write starts from the earlier one's result.
+                    // A new head's stale chunk is refreshed first: the template's two dwords, then the cell writes on top (both
+                    // heads in one stale chunk write the same dwords twice).
+#pragma unroll
+                    for (int p = 0; p < 2; ++p) {
+                        if (sl[p]) {
+                            board[2u * nk[p]] = tc0[p];
+                            board[2u * nk[p] + 1u] = tc1[p];
+                            stale &= ~nbit[p];
+                        }
                     }
+                    lds_set_nibble(hdw[0], hsh[0], NIB_P1_BODY);
+                    lds_set_nibble(hdw[1], hsh[1], NIB_P2_BODY);
+                    lds_set_nibble(ndw[0], nsh[0], NIB_P1_HEAD);
+                    lds_set_nibble(ndw[1], nsh[1], NIB_P2_HEAD);
+                    const unsigned long long sm = hbit[0] | hbit[1] | nbit[0] | nbit[1];
+                    mask |= sm;
+                    dirty |= sm;
                 }
-                const uint32_t nib[4] = {NIB_P1_BODY, NIB_P2_BODY, NIB_P1_HEAD, NIB_P2_HEAD};
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const uint32_t sh = (uint32_t)(cells[k] & 1) * 4u;
-                    b[k] = (b[k] & ~(0xFu << sh)) | (nib[k] << sh);
-#pragma unroll
-                    for (int j = k + 1; j < 4; ++j)
-                        if ((cells[j] >> 1) == (cells[k] >> 1)) b[j] = b[k];
+                for (int p = 0; p < 2; ++p) {
+                    cell[p] = ncell[p];
+                    hbit[p] = nbit[p];
+                    hdw[p] = ndw[p];
+                    hsh[p] = nsh[p];
                 }
-                unsigned long long sm = 0ull;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    cellb[cells[k] >> 1] = (unsigned char)b[k];
-                    sm |= 1ull << (cells[k] >> 4);
-                }
-                mask |= sm;
-                dirty |= sm;
             }
-        }
-        ROLL_STAMP(1);
+            const bool fin = done;                                      // what the step records: the move's outcome, or that of a
+            const int win = winner;                                     // game finished before the step (the restart below resets both)
+            ROLL_STAMP(1);
 
-        // ---- a restart (ACKTR.py:307-310), one divergent region: the state words, the board, the next game's starts.
-        // The board: the two head chunks only, straight-line (everything else the old game drew goes stale).  One LDS
-        // round trip reads the template's two dwords of each head chunk; the heads go in in registers — a head cell is
-        // EMPTY in the template: XOR turns that nibble into the head's (game.py:90-91); the two heads are different
-        // cells, possibly of one chunk or one dword, and then both chunks' words take both XORs and the two writes store
-        // the same bytes — and the two chunks are written.  A head on the short last chunk is no special case: the
-        // chunk's padding nibbles are 0 in the template and stay 0.  A lane writes only its own board: no fence, no wave
-        // barrier.  The next game: rs4.episode moves on and rs4.nstart is drawn, one Philox block (make_game_starts);
-        // rs4.envp and rs4.nenvp stay as the prologue read them until the epilogue (no step of mode None reads them).
-        if (mine && done && autoreset) {
-            st = restarted_st4(rs.z, st.w);
-            st_dirty = true;
-            uint32_t h1, h2;                                         // the new heads' cells
-            start_cells(S, rs.z, h1, h2);
-            const uint32_t k1 = h1 >> 4, k2 = h2 >> 4;
-            const unsigned long long heads = (1ull << k1) | (1ull << k2);
-            dirty |= mask | heads;
-            stale = (stale | mask) & ~heads;                         // the old trail is not wiped: its chunks go stale
-            mask = heads;
-            uint32_t a[2] = {tmpl[2u * k1], tmpl[2u * k1 + 1u]}, c[2] = {tmpl[2u * k2], tmpl[2u * k2 + 1u]};
-            const uint32_t hx1 = (NIB_EMPTY ^ NIB_P1_HEAD) << ((h1 & 7u) * 4u), hx2 = (NIB_EMPTY ^ NIB_P2_HEAD) << ((h2 & 7u) * 4u);
-            const uint32_t d1 = (h1 >> 3) & 1u, d2 = (h2 >> 3) & 1u;
-            const bool same = k1 == k2;
+            // ---- a restart (ACKTR.py:307-310), one divergent region: the state words, the board, the next game's starts.
+            // The board: the two head chunks only, straight-line (everything else the old game drew goes stale).  One LDS
+            // round trip reads the template's two dwords of each head chunk; the heads go in in registers — a head cell is
+            // EMPTY in the template: XOR turns that nibble into the head's (game.py:90-91); the two heads are different
+            // cells, possibly of one chunk or one dword, and then both chunks' words take both XORs and the two writes store
+            // the same bytes — and the two chunks are written.  A head on the short last chunk is no special case: the
+            // chunk's padding nibbles are 0 in the template and stay 0.  A lane writes only its own board: no fence, no wave
+            // barrier.  The next game: rs4.episode moves on and rs4.nstart is drawn, one Philox block (make_game_starts);
+            // rs4.envp and rs4.nenvp stay as the prologue read them until the epilogue (no step of mode None reads them).
+            // The carried state becomes restarted_st4's: the heads at rs4.nstart, both alive, no last action, eplen 0.
+            if (mine && done && autoreset) {
+                unpack_pos(rs.z, r, c);
+                alive = META_ALIVE0 | META_ALIVE1;
+                done = false;
+                winner = 0;
+                last[0] = last[1] = 0u;
+                eplen = 0u;
+                st_dirty = true;
+                cell[0] = roll_cell(S, r[0], c[0]);                      // start_cells' values
+                cell[1] = roll_cell(S, r[1], c[1]);
+                const uint32_t h1 = (uint32_t)cell[0], h2 = (uint32_t)cell[1];
 #pragma unroll
-            for (uint32_t d = 0; d < 2u; ++d) {
-                const uint32_t y1 = d1 == d ? hx1 : 0u, y2 = d2 == d ? hx2 : 0u;
-                a[d] ^= y1 ^ (same ? y2 : 0u);
-                c[d] ^= y2 ^ (same ? y1 : 0u);
+                for (int p = 0; p < 2; ++p) {
+                    hdw[p] = lds_cell_dword(board_lds, (uint32_t)cell[p]);
+                    hsh[p] = lds_cell_shift((uint32_t)cell[p]);
+                }
+                const uint32_t k1 = h1 >> 4, k2 = h2 >> 4;
+                hbit[0] = 1ull << k1;
+                hbit[1] = 1ull << k2;
+                const unsigned long long heads = hbit[0] | hbit[1];
+                dirty |= mask | heads;
+                stale = (stale | mask) & ~heads;                         // the old trail is not wiped: its chunks go stale
+                mask = heads;
+                uint32_t ta[2] = {tmpl[2u * k1], tmpl[2u * k1 + 1u]}, tb[2] = {tmpl[2u * k2], tmpl[2u * k2 + 1u]};
+                const uint32_t hx1 = (NIB_EMPTY ^ NIB_P1_HEAD) << hsh[0], hx2 = (NIB_EMPTY ^ NIB_P2_HEAD) << hsh[1];
+                const uint32_t d1 = (h1 >> 3) & 1u, d2 = (h2 >> 3) & 1u;
+                const bool same = k1 == k2;
+#pragma unroll
+                for (uint32_t d = 0; d < 2u; ++d) {
+                    const uint32_t y1 = d1 == d ? hx1 : 0u, y2 = d2 == d ? hx2 : 0u;
+                    ta[d] ^= y1 ^ (same ? y2 : 0u);
+                    tb[d] ^= y2 ^ (same ? y1 : 0u);
+                }
+                board[2u * k1] = ta[0];
+                board[2u * k1 + 1u] = ta[1];
+                board[2u * k2] = tb[0];
+                board[2u * k2 + 1u] = tb[1];
+                rs.y += 1u;
+                nres += 1u;
+                rs.z = sring[(nres & (2u * ROLL_R - 1u)) * WAVE + lane];  // make_game_starts(env, rs.y), drawn by the helper
             }
-            board[2u * k1] = a[0];
-            board[2u * k1 + 1u] = a[1];
-            board[2u * k2] = c[0];
-            board[2u * k2 + 1u] = c[1];
-            rs.y += 1u;
-            nres += 1u;
-            rs.z = sring[(nres & (2u * ROLL_R - 1u)) * WAVE + lane];  // make_game_starts(env, rs.y), drawn by the helper
-        }
-        ROLL_STAMP(2);
+            ROLL_STAMP(2);
 
-        // ---- the records and the totals
-        if constexpr (REC) {
-            const uint32_t n = (uint32_t)P.N;                           // a row: N envs
-            if (row_done) {
-                if (mine) row_done[(uint32_t)env] = (int8_t)done;
-                row_done += n;
+            // ---- the records (REC alone: the other instantiations hold no record store and no reward) and the totals
+            if constexpr (REC) {
+                const uint32_t n = (uint32_t)P.N;                           // a row: N envs
+                if (mine) {
+                    if (out.done) (out.done + row)[(uint32_t)env] = (int8_t)fin;
+                    if (out.winner) (out.winner + row)[(uint32_t)env] = (int8_t)win;
+                    if (out.reward) (reinterpret_cast<float2 *>(out.reward) + row)[(uint32_t)env] = make_float2(rw0, rw1);
+                }
+                row += n;
             }
-            if (row_winner) {
-                if (mine) row_winner[(uint32_t)env] = (int8_t)winner;
-                row_winner += n;
-            }
-            if (row_reward) {
-                if (mine) row_reward[(uint32_t)env] = make_float2(rw0, rw1);
-                row_reward += n;
-            }
-        } else if (mine) {
-            if (out.done) out.done[env] = (int8_t)done;
-            if (out.winner) out.winner[env] = (int8_t)winner;
-            if (out.reward) reinterpret_cast<float2 *>(out.reward)[env] = make_float2(rw0, rw1);
+            // per lane, a byte each: steps, player 1 wins, player 2 wins, draws; summed over the wave at a flush
+            if (out.totals && stepped) tally += 1u + (fin ? 1u << ((0x00100818u >> (8 * win)) & 31u) : 0u);   // (draw: byte 3)
+            ab.x = (ab.x >> 8) | (ab.y << 24);                          // the next step's byte
+            ab.y >>= 8;
+            ROLL_STAMP(3);
         }
-        // per lane, a byte each: steps, player 1 wins, player 2 wins, draws; summed over the wave at a flush
-        if (out.totals && stepped) tally += 1u + (done ? 1u << (winner ? 8 * winner : 24) : 0u);
-        ROLL_STAMP(3);
     }
 
     ROLL_STAMP_LAUNCH(1);
@@ -1619,7 +1661,10 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
             }
         }
         ROLL_STAMP_LAUNCH(2);
-        if (mine && st_dirty) P.st4[env] = st;
+        // st4 is packed here alone, from the carried state: the bytes stepped_st4 or restarted_st4 of the env's last event
+        // would have left (last[] is the stored action + 1, and 0 behind a restart; a dead player's head may be off the board)
+        if (mine && st_dirty)
+            P.st4[env] = make_uint4(pack_pos(r[0], c[0], r[1], c[1]), pack_meta(alive, done, winner, (int)last[0] - 1, (int)last[1] - 1), eplen, tick);
         // The next launch's entry mask (the masked entry above): what differs from the template now lies inside mask, and the
         // stores above left memory outside it the template.  Every env of the launch, a lane that did not step (the mask it
         // entered with) included.
@@ -1663,9 +1708,9 @@ __global__ __launch_bounds__(2 * BLOCK) void k_obs_roll(Params P, int E, int epw
                                                         unsigned long long *__restrict__ emask)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // The step's parameters are re-read from the kernel-argument segment at every step (scalar loads through a pointer the
-    // compiler cannot see through) instead of kept live across the loop: 26 words of Params in SGPRs for the whole launch
-    // spill, and every spilled word is a v_readlane per use.
+    // Params is read from the kernel-argument segment where it is needed (scalar loads through a pointer the compiler
+    // cannot see through: the prologue, the epilogue, REC's steps) instead of kept live across the loop: 26 words of
+    // Params in SGPRs for the whole launch spill, and every spilled word is a v_readlane per use.  S and W do stay live.
     kernarg_t *kp = (kernarg_t *)__builtin_amdgcn_kernarg_segment_ptr();       // (Params is the first argument)
     roll_resident<false>(kp, E, epw, cpe, flags & ~TRON_ROLLOUT_RESIDENT, out, k_steps, smem, nullptr, emask);
 }
