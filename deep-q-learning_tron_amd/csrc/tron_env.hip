@@ -93,8 +93,9 @@ struct StepOut {
 // wave per workgroup (roll_waves), where only wave 0's half is written.
 // Behind that region, at ceil(N / 64) * 2 * (TRON_ROLLOUT_CHUNK + 1) * 4 whatever the grid, the helpers of the stamped game
 // waves have their own: [blocks][2][ROLL_HSTAMPS] (ROLL_HSTAMP: 0 kernel entry, 1 prologue draws done, 2 arrival at P, 3
-// departure from P, 2 + 2 b / 3 + 2 b arrival at / departure from B_b; the last slot is the GAME wave's arrival at P, which
-// its own layout has no place for).
+// departure from P, 2 + 2 b / 3 + 2 b arrival at / departure from B_b; the last slot but one is the end of the hand-off
+// pass, which begins at the departure from B_(nb-1), or from P in a launch of one block; behind a handed entry slot 1 is
+// "the handed words are in the rings"; the last slot is the GAME wave's arrival at P, which its own layout has no place for).
 #ifdef TRON_STAMPS
 constexpr int ROLL_HSTAMPS = 4 + 2 * (TRON_ROLLOUT_CHUNK / 8);
 #define ROLL_HSTAMP(slot)                                                                         \
@@ -1055,7 +1056,8 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 // A launch's steps come in blocks of ROLL_R.  Per game wave the helper keeps two rings in LDS:
 //   actions  [2][64] x ROLL_R bytes: action_byte of step s of env `lane` is byte s % ROLL_R of slot (s / ROLL_R) & 1
 //   starts   [2 ROLL_R][64] dwords: make_game_starts(env, episode0 + j), the start of the game the env's j-th restart of
-//            the launch draws, in slot j % (2 ROLL_R)
+//            the launch draws, in slot (episode0 + j) % (2 ROLL_R): the slot of an ABSOLUTE episode, so that a ring image
+//            still means something to the next launch, whose episode0 has moved on (Hand-off below)
 // and reads one word per env and block, counts[64]: the env's restarts so far.
 constexpr int ROLL_R = 8;
 // A launch flag of the host's own (rollout_wave), beside the TRON_STEP_* bits: every env's entry mask describes its planes.
@@ -1064,6 +1066,14 @@ constexpr uint32_t ROLL_ENTRY_MASKED = 0x80000000u;
 // profiles/r18_rollout_ab.txt).  The game wave then draws the last ROLL_GAME_STARTS ordinals of block 0 itself, after its
 // gather; with 2 the two roles meet at P (0: the helper is 2.8 us late in every pair, 4: the game wave is 1.4 us late).
 constexpr int ROLL_GAME_STARTS = 2;
+// The second flag of the host's own: the launch before this one on the handle handed over its helper's rings (roll_helper:
+// Hand-off).  hand is [ROLL_HAND_DWORDS][N] dwords in the handle's blob, word-major, so that a wave's 64 envs are 256
+// contiguous bytes per word: the 2 ROLL_R slots of the start ring, the two dwords of the next launch's block-0 action
+// bytes, and the highest absolute episode the ring holds.  No action byte is 0xFF (action_byte: bits 4-5 and 6-7 are
+// __umulhi(x, 3) <= 2), so a second action dword of ROLL_HAND_NO_ACTIONS says "starts only" (a tape launch's hand-off).
+constexpr uint32_t ROLL_ENTRY_HANDED = 0x40000000u;
+constexpr int ROLL_HAND_DWORDS = 2 * ROLL_R + 3;
+constexpr uint32_t ROLL_HAND_NO_ACTIONS = 0xFFFFFFFFu;
 constexpr size_t ROLL_RING_DWORDS = 4 * WAVE + 2 * ROLL_R * WAVE + 2 * WAVE;
 static_assert(ROLL_R == 8 && TRON_ROLLOUT_CHUNK % ROLL_R == 0, "a block's action bytes are one qword; blocks tile a launch");
 #ifdef TRON_STAMPS
@@ -1104,7 +1114,7 @@ __device__ __forceinline__ void roll_flush_tally(uint32_t &tally, uint32_t &n_st
 // 4.8, where drawing every block's ROLL_R anew was 8).  The prologue draws (0, len_0]: hi = len_0 at P.  Behind a masked
 // entry (roll_resident) the last game_starts = min(ROLL_GAME_STARTS, len_0) of these ordinals are the GAME wave's: the helper
 // draws (0, len_0 - game_starts], the game wave (len_0 - game_starts, len_0] with the same make_game_starts (a clash goes
-// through make_game_general there as here) into the same slots j % (2 ROLL_R), both before P; hi = len_0 at P as before.
+// through make_game_general there as here) into the same slots (episode0 + j) % (2 ROLL_R), both before P; hi = len_0 at P as before.
 // The two sets of slots are disjoint (len_0 <= ROLL_R consecutive ordinals), nobody reads the ring before P, and the helper's
 // next write is behind P: the invariant below holds with "the ring holds (0, len_0] at P" whoever wrote which slot.
 // Invariant: at B_(b+1) the ring holds (c_b, hi] with hi >= c_b + ROLL_R + len_(b+1), which contains block b + 1's (c_(b+1),
@@ -1112,7 +1122,10 @@ __device__ __forceinline__ void roll_flush_tally(uint32_t &tally, uint32_t &n_st
 // c_b + len_b (full blocks but the last: hi >= c_b + ROLL_R wherever a block b + 1 exists).  During block b the helper
 // writes the ordinals of (hi, c_b + 2 ROLL_R] alone, a subset of (c_b + ROLL_R, c_b + 2 ROLL_R]: not the slots block b
 // reads — (c_b, c_b + ROLL_R] and the written set lie in one window of 2 ROLL_R consecutive ordinals — and not the slots
-// of (c_b, hi], by the same window; the ordinals those slots held before are 2 ROLL_R lower, at most c_b: consumed.  A
+// of (c_b, hi], by the same window; the ordinals those slots held before are 2 ROLL_R lower, at most c_b: consumed.  The
+// slot of ordinal j is (episode0 + j) % (2 ROLL_R): episode0 is one constant per lane and launch, so 2 ROLL_R consecutive
+// ordinals still fall on 2 ROLL_R different slots and two ordinals share a slot exactly when they are a multiple of
+// 2 ROLL_R apart — the window argument concerns consecutive ordinals and is the same as for j % (2 ROLL_R).  A
 // count-blind helper (ordinals by block number alone) would need a ring as deep as the launch: an env that has not
 // restarted yet still needs ordinal 1 in the last block.  The lanes' counts differ, so the draw loop runs the wave's
 // slowest lane's count, the others masked; a clash's general routine runs in it as before, for a third of the draws.
@@ -1131,10 +1144,32 @@ __device__ __forceinline__ void roll_flush_tally(uint32_t &tally, uint32_t &n_st
 // without an env of its own (mine false) and a step past k_steps load nothing.  A finished env that restarts in step s
 // makes no move in it, as in the per-step kernels: row s is then not used, and nothing is shifted.  The starts ring is
 // drawn as ever: a restart's position is keyed by (env, episode), whoever chose the actions.
+// Hand-off.  Under autoreset no env is finished when a launch ends and every env has moved in every step, so the launch
+// behind this one on the handle — if nobody touches the state words in between, which the host knows (rollout_wave) — starts
+// at tick tick0 + k_steps and at episode episode0 + c_final, c_final the env's restarts in this launch.  Its block-0 action
+// bytes and its first starts are functions of those and (seed, stream, W, fair) alone, and this helper has nothing to do
+// during the last block.  So pass nb - 1 (behind B_(nb-1); behind P in a launch of one block) does not end at once:
+//   (a) it tops the start ring up as during any block, as if a block of len_(nb-1) steps followed: it draws
+//       (hi, c_(nb-1) + ROLL_R + len_(nb-1)].  The writes obey the window above (at most c_(nb-1) + 2 ROLL_R; in a launch of
+//       one block whose prologue drew hi = len_0 < ROLL_R the written (len_0, len_0 + ROLL_R] and the read (0, len_0] lie in
+//       (0, 2 ROLL_R]), so the game lane's reads of the last block are undisturbed.  Afterwards the ring holds
+//       (c_(nb-1), hi] with hi >= c_(nb-1) + len_(nb-1) + ROLL_R >= c_final + ROLL_R and hi <= c_(nb-1) + 2 ROLL_R <=
+//       c_final + 2 ROLL_R: everything in (c_final, c_final + ROLL_R], whatever c_final turns out to be;
+//   (b) it draws the next launch's block-0 action bytes, ticks tick0 + k_steps .. + ROLL_R - 1 (TAPE: nothing, the next
+//       tape is not known; ROLL_HAND_NO_ACTIONS);
+//   (c) it stores the ring's 2 ROLL_R slots as they are in LDS (the slots of consumed ordinals included: nobody reads
+//       them), the action qword and episode0 + hi to hand[.][env]: plain stores, nothing waits for them, no barrier.
+//       A lane without an env stores nothing.
+// Behind a handed entry (ROLL_ENTRY_HANDED) the prologue pass loads these ROLL_HAND_DWORDS words, all loads before the first
+// wait, writes the ring and action slot 0, sets hi = word - episode0 (in [ROLL_R, 2 ROLL_R]: "the ring holds (0, hi] at P",
+// the invariant's base case with a larger hi) and draws nothing; the game wave draws no start either (game_starts 0).  A
+// lane without an env gets hi = 2 ROLL_R, so that it asks for no draw.  Block 0's top-up (hi, ROLL_R + len_1] is then what
+// the handed level lacks — nothing for most lanes.  A launch that draws its actions behind a tape launch finds
+// ROLL_HAND_NO_ACTIONS and draws block 0's bytes itself; a tape launch copies its rows as ever and takes the starts.
 template <bool TAPE>
 __device__ __forceinline__ void roll_helper(const Params &P, int env, bool autoreset, const uint4 &st, const uint4 &rs, int k_steps,
                                             int lane, uint2 *aring, uint32_t *sring, const uint32_t *cring, const StepOut &out,
-                                            int wave, int gw, bool mine, const int8_t *tape, uint32_t game_starts)
+                                            int wave, int gw, bool mine, const int8_t *tape, uint32_t game_starts, uint32_t *hand, bool handed)
 {
     ROLL_HSTAMP(0);
     const uint32_t seed = P.seed, stream = P.stream;
@@ -1143,6 +1178,27 @@ __device__ __forceinline__ void roll_helper(const Params &P, int env, bool autor
     const int nb = (k_steps + ROLL_R - 1) / ROLL_R;
     uint32_t *abytes = reinterpret_cast<uint32_t *>(aring);
     uint32_t hi = 0u;                                               // this lane's highest ordinal drawn
+    uint32_t *const hme = hand + (mine ? (size_t)env : 0u);         // this env's column of hand[ROLL_HAND_DWORDS][N] (mine only)
+    const size_t hn = (size_t)P.N;
+    bool have_actions = false;                                      // block 0's bytes came with the hand-off (wave-uniform)
+    if (handed) {                                                   // (a launch argument; the host sets it under autoreset alone)
+        uint32_t hw[ROLL_HAND_DWORDS];
+#pragma unroll
+        for (int i = 0; i < ROLL_HAND_DWORDS; ++i) hw[i] = 0u;
+        hw[ROLL_HAND_DWORDS - 1] = ep0 + 2u * (uint32_t)ROLL_R;
+        if (mine) {
+            const uint32_t *q = hme;                                // (the word's address per lane, carried: no offset held in SGPRs)
+#pragma unroll
+            for (int i = 0; i < ROLL_HAND_DWORDS; ++i, q += hn) hw[i] = *q;   // (all in flight before the first is used)
+        }
+#pragma unroll
+        for (int i = 0; i < 2 * ROLL_R; ++i) sring[i * WAVE + lane] = hw[i];
+        hi = hw[ROLL_HAND_DWORDS - 1] - ep0;
+        if constexpr (!TAPE) {
+            have_actions = __all(hw[2 * ROLL_R + 1] != ROLL_HAND_NO_ACTIONS) != 0;
+            if (have_actions) aring[lane] = make_uint2(hw[2 * ROLL_R], hw[2 * ROLL_R + 1]);
+        }
+    }
     for (int b = -1; b < nb; ++b) {                                 // pass b draws for block b + 1: before P, then during block b
         uint32_t base = 0u;                                         // c_b + ROLL_R: what block b can have consumed at the most
         if (b > 0) {
@@ -1150,39 +1206,73 @@ __device__ __forceinline__ void roll_helper(const Params &P, int env, bool autor
             __syncthreads();                                        // B_b
             ROLL_HSTAMP(3 + 2 * b);
         }
-        if (b + 1 >= nb) break;
+        const bool last = b + 1 >= nb;                              // the hand-off pass: the launch has no block b + 1
+        if (last && !autoreset) break;
         if (b >= 0) base = (b ? cring[(b & 1) * WAVE + lane] : 0u) + (uint32_t)ROLL_R;
-        const uint32_t to = base + (uint32_t)min(ROLL_R, k_steps - (b + 1) * ROLL_R);
-        if constexpr (!TAPE) {
+        const uint32_t to = base + (uint32_t)min(ROLL_R, k_steps - (last ? b : b + 1) * ROLL_R);
+        if (last) {
+            // (b) the next launch's block 0, straight to memory
+            if constexpr (!TAPE) {
 #pragma nounroll
-            for (int d = 0; d < ROLL_R / 4; ++d) {                  // four steps' bytes, one dword
-                const uint32_t s0 = (uint32_t)((b + 1) * ROLL_R + d * 4);
-                uint32_t v = 0u;
+                for (int d = 0; d < ROLL_R / 4; ++d) {
+                    uint32_t v = 0u;
 #pragma unroll
-                for (uint32_t i = 0; i < 4u; ++i) {
-                    uint32_t x[4];
-                    philox4x32_10((uint32_t)env, tick0 + s0 + i, RNG_STEP, 0u, seed, stream, x);
-                    v |= action_byte(x[0], x[1]) << (8u * i);
+                    for (uint32_t i = 0; i < 4u; ++i) {
+                        uint32_t x[4];
+                        philox4x32_10((uint32_t)env, tick0 + (uint32_t)k_steps + (uint32_t)(d * 4) + i, RNG_STEP, 0u, seed, stream, x);
+                        v |= action_byte(x[0], x[1]) << (8u * i);
+                    }
+                    if (mine) hme[(size_t)(2 * ROLL_R + d) * hn] = v;
                 }
-                abytes[(((s0 / ROLL_R) & 1u) * WAVE + (uint32_t)lane) * (ROLL_R / 4) + ((s0 / 4u) & (ROLL_R / 4 - 1))] = v;
+            } else if (mine) {
+                hme[(size_t)(2 * ROLL_R + 1) * hn] = ROLL_HAND_NO_ACTIONS;
             }
-        } else {
-            const int s0 = (b + 1) * ROLL_R;                        // the block's eight rows: loads first, then the bytes
-            const uint16_t *row = reinterpret_cast<const uint16_t *>(tape) + (size_t)s0 * (size_t)P.N + (size_t)env;
-            uint32_t t[ROLL_R];
+        } else if (TAPE || !(b < 0 && have_actions)) {       // (block 0's bytes may have come with the hand-off)
+            if constexpr (!TAPE) {
+#pragma nounroll
+                for (int d = 0; d < ROLL_R / 4; ++d) {                  // four steps' bytes, one dword
+                    const uint32_t s0 = (uint32_t)((b + 1) * ROLL_R + d * 4);
+                    uint32_t v = 0u;
 #pragma unroll
-            for (int i = 0; i < ROLL_R; ++i) t[i] = (mine && s0 + i < k_steps) ? row[(size_t)i * (size_t)P.N] : 0u;
-            uint32_t v[2] = {0u, 0u};
+                    for (uint32_t i = 0; i < 4u; ++i) {
+                        uint32_t x[4];
+                        philox4x32_10((uint32_t)env, tick0 + s0 + i, RNG_STEP, 0u, seed, stream, x);
+                        v |= action_byte(x[0], x[1]) << (8u * i);
+                    }
+                    abytes[(((s0 / ROLL_R) & 1u) * WAVE + (uint32_t)lane) * (ROLL_R / 4) + ((s0 / 4u) & (ROLL_R / 4 - 1))] = v;
+                }
+            } else {
+                const int s0 = (b + 1) * ROLL_R;                        // the block's eight rows: loads first, then the bytes
+                const uint16_t *row = reinterpret_cast<const uint16_t *>(tape) + (size_t)s0 * (size_t)P.N + (size_t)env;
+                uint32_t t[ROLL_R];
 #pragma unroll
-            for (int i = 0; i < ROLL_R; ++i) v[i >> 2] |= ((t[i] & 3u) | ((t[i] >> 6) & 0xCu)) << (8 * (i & 3));
-            aring[((b + 1) & 1) * WAVE + lane] = make_uint2(v[0], v[1]);
+                for (int i = 0; i < ROLL_R; ++i) t[i] = (mine && s0 + i < k_steps) ? row[(size_t)i * (size_t)P.N] : 0u;
+                uint32_t v[2] = {0u, 0u};
+#pragma unroll
+                for (int i = 0; i < ROLL_R; ++i) v[i >> 2] |= ((t[i] & 3u) | ((t[i] >> 6) & 0xCu)) << (8 * (i & 3));
+                aring[((b + 1) & 1) * WAVE + lane] = make_uint2(v[0], v[1]);
+            }
         }
         if (autoreset) {
             const uint32_t upto = b < 0 ? to - min(game_starts, to) : to;   // (block 0's last ordinals may be the game wave's)
 #pragma nounroll
             for (uint32_t j = hi + 1u; j <= upto; ++j)              // (per lane: nothing where hi >= upto)
-                sring[(j & (2u * ROLL_R - 1u)) * WAVE + (uint32_t)lane] = make_game_starts(seed, stream, W, fair, (uint32_t)env, ep0 + j);
+                sring[((ep0 + j) & (2u * ROLL_R - 1u)) * WAVE + (uint32_t)lane] = make_game_starts(seed, stream, W, fair, (uint32_t)env, ep0 + j);
             hi = max(hi, to);
+        }
+        if (last) {
+            // (c) the ring as this lane's own writes (and, in front of P, its game lane's) left it, and its level
+            if (mine) {
+                uint32_t hw[2 * ROLL_R];
+#pragma unroll
+                for (int i = 0; i < 2 * ROLL_R; ++i) hw[i] = sring[i * WAVE + lane];
+                uint32_t *q = hme;
+#pragma unroll
+                for (int i = 0; i < 2 * ROLL_R; ++i, q += hn) *q = hw[i];
+                q[2u * hn] = ep0 + hi;                              // (behind the two action dwords)
+            }
+            ROLL_HSTAMP(ROLL_HSTAMPS - 2);
+            break;
         }
         if (b < 0) {
             ROLL_HSTAMP(1);
@@ -1208,7 +1298,7 @@ __device__ __forceinline__ void lds_set_nibble(uint32_t dword_lds, uint32_t shif
 
 template <bool TAPE, bool REC = false>
 __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uint32_t cpe, uint32_t flags, const StepOut &out,
-                                              int k_steps, unsigned char *smem, const int8_t *tape, unsigned long long *emask)
+                                              int k_steps, unsigned char *smem, const int8_t *tape, unsigned long long *emask, uint32_t *hand)
 {
     const uint32_t sd = 2u * cpe + 1u;                              // dwords per board
     uint32_t *boards = reinterpret_cast<uint32_t *>(smem);          // [E][sd]
@@ -1263,7 +1353,9 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         oenv = P.obs_state + (size_t)(mine ? env : 0) * 2u * G;
         const bool masked = (flags & ROLL_ENTRY_MASKED) != 0u;      // (wave-uniform: a launch argument)
         // the ordinals of block 0 that the game wave draws itself behind a masked entry (roll_helper: Starts)
-        const uint32_t game_starts = masked && autoreset ? (uint32_t)min(ROLL_GAME_STARTS, min(ROLL_R, k_steps)) : 0u;
+        // (none behind a handed entry: the starts came with the hand-off)
+        const bool handed = (flags & ROLL_ENTRY_HANDED) != 0u;
+        const uint32_t game_starts = masked && autoreset && !handed ? (uint32_t)min(ROLL_GAME_STARTS, min(ROLL_R, k_steps)) : 0u;
         if (mine) {
             st = P.st4[env];
             if (autoreset) rs = P.rs4[env];
@@ -1283,7 +1375,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         }
         __syncthreads();
         if (helper) {
-            roll_helper<TAPE>(P, env, autoreset, st, rs, k_steps, lane, aring, sring, cring, out, wave, gw, mine, tape, game_starts);
+            roll_helper<TAPE>(P, env, autoreset, st, rs, k_steps, lane, aring, sring, cring, out, wave, gw, mine, tape, game_starts, hand, handed);
             return;
         }
         if (masked) {
@@ -1350,7 +1442,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
                 const uint32_t to = (uint32_t)min(ROLL_R, k_steps);
 #pragma nounroll
                 for (uint32_t j = to - game_starts + 1u; j <= to; ++j)
-                    sring[(j & (2u * ROLL_R - 1u)) * WAVE + (uint32_t)lane] = make_game_starts(P.seed, P.stream, P.W, P.fair, (uint32_t)env, rs.y + j);
+                    sring[((rs.y + j) & (2u * ROLL_R - 1u)) * WAVE + (uint32_t)lane] = make_game_starts(P.seed, P.stream, P.W, P.fair, (uint32_t)env, rs.y + j);
             }
         } else {
             // The wave reads its envs' player-1 planes one env at a time, lane = chunk (coalesced), packs them into the env's
@@ -1560,7 +1652,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
                 board[2u * k2 + 1u] = tb[1];
                 rs.y += 1u;
                 nres += 1u;
-                rs.z = sring[(nres & (2u * ROLL_R - 1u)) * WAVE + lane];  // make_game_starts(env, rs.y), drawn by the helper
+                rs.z = sring[(rs.y & (2u * ROLL_R - 1u)) * WAVE + lane];  // make_game_starts(env, rs.y), drawn by the helper, in the episode's slot
             }
             ROLL_STAMP(2);
 
@@ -1705,36 +1797,36 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
 // even side, cpe <= 64 (roll_resident).  TRON_ROLLOUT_RESIDENT asks for what this kernel does by itself; the flag is
 // accepted for its callers' sake.
 __global__ __launch_bounds__(2 * BLOCK) void k_obs_roll(Params P, int E, int epw, uint32_t cpe, uint32_t flags, StepOut out, int k_steps,
-                                                        unsigned long long *__restrict__ emask)
+                                                        unsigned long long *__restrict__ emask, uint32_t *__restrict__ hand)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // Params is read from the kernel-argument segment where it is needed (scalar loads through a pointer the compiler
     // cannot see through: the prologue, the epilogue, REC's steps) instead of kept live across the loop: 26 words of
     // Params in SGPRs for the whole launch spill, and every spilled word is a v_readlane per use.  S and W do stay live.
     kernarg_t *kp = (kernarg_t *)__builtin_amdgcn_kernarg_segment_ptr();       // (Params is the first argument)
-    roll_resident<false>(kp, E, epw, cpe, flags & ~TRON_ROLLOUT_RESIDENT, out, k_steps, smem, nullptr, emask);
+    roll_resident<false>(kp, E, epw, cpe, flags & ~TRON_ROLLOUT_RESIDENT, out, k_steps, smem, nullptr, emask, hand);
 }
 
 // The same launch with the caller's actions (tron_rollout_actions): the second instantiation of roll_resident.  Its game
 // waves run k_obs_roll's loop on bytes of the same ring; only its helper differs (roll_helper<true>), and tape points at the
 // launch's own first step.
 __global__ __launch_bounds__(2 * BLOCK) void k_obs_roll_tape(Params P, int E, int epw, uint32_t cpe, uint32_t flags, StepOut out, int k_steps,
-                                                             const int8_t *__restrict__ tape, unsigned long long *__restrict__ emask)
+                                                             const int8_t *__restrict__ tape, unsigned long long *__restrict__ emask, uint32_t *__restrict__ hand)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     kernarg_t *kp = (kernarg_t *)__builtin_amdgcn_kernarg_segment_ptr();       // (Params is the first argument: see k_obs_roll)
-    roll_resident<true>(kp, E, epw, cpe, flags, out, k_steps, smem, tape, emask);
+    roll_resident<true>(kp, E, epw, cpe, flags, out, k_steps, smem, tape, emask, hand);
 }
 
 // k_obs_roll_tape with the per-step records (tron_rollout_actions_records): the third instantiation of roll_resident.  Same
 // step loop, same helper; out.done / out.winner / out.reward are step-major tapes here and point, like tape, at the launch's
 // own first step.
 __global__ __launch_bounds__(2 * BLOCK) void k_obs_roll_tape_rec(Params P, int E, int epw, uint32_t cpe, uint32_t flags, StepOut out, int k_steps,
-                                                                 const int8_t *__restrict__ tape, unsigned long long *__restrict__ emask)
+                                                                 const int8_t *__restrict__ tape, unsigned long long *__restrict__ emask, uint32_t *__restrict__ hand)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     kernarg_t *kp = (kernarg_t *)__builtin_amdgcn_kernarg_segment_ptr();       // (Params is the first argument: see k_obs_roll)
-    roll_resident<true, true>(kp, E, epw, cpe, flags, out, k_steps, smem, tape, emask);
+    roll_resident<true, true>(kp, E, epw, cpe, flags, out, k_steps, smem, tape, emask, hand);
 }
 
 // Fewer workgroups than tiles (the TRON_ROLL_GRID override): workgroup w owns tiles w, w + gridDim.x, ... and
@@ -2179,9 +2271,15 @@ struct tron_env {
     int roll_E;               // envs per tile of the persistent rollout (0: not chosen yet), see roll_tile_envs
     int roll_waves;           // waves per workgroup of k_obs_roll (0: not chosen yet), see roll_waves
     unsigned long long *emask; // [N] in the blob: k_obs_roll's entry masks, written by every launch of the roll_resident family
+    uint32_t *hand;           // [ROLL_HAND_DWORDS][N] in the blob, next to the entry masks: the helper's hand-off (roll_helper)
     bool entry_masks;         // the entry masks describe the attached planes: the last call that could write the planes or the
                               // state words enqueued was such a launch over all envs (set in rollout_wave, cleared by
                               // planes_written; it follows the order of the calls, as the planes follow the order of the stream)
+    bool handed;              // `hand` is what the next launch of the family would draw: the last call enqueued that could write
+                              // the state words was such a launch with autoreset, made with the four values below (set in
+                              // rollout_wave, cleared by planes_written and by a launch without autoreset)
+    uint32_t hand_seed, hand_stream;
+    int hand_fair, hand_W;
 };
 
 namespace {
@@ -2189,8 +2287,8 @@ namespace {
 inline hipStream_t S_(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 // Every entry point that can write the planes or the state words other than through the roll_resident family: k_obs_roll's
-// next launch reads whole planes again.
-inline void planes_written(tron_env *h) { h->entry_masks = false; }
+// next launch reads whole planes again and draws its own first block (the state words' tick and episode may have moved).
+inline void planes_written(tron_env *h) { h->entry_masks = h->handed = false; }
 
 inline int launch_status()
 {
@@ -2379,7 +2477,7 @@ int tron_create(int32_t n_envs, int32_t W, int32_t mode, int32_t fair, uint32_t 
     P.r_step = -1.0f; P.r_win = 100.0f; P.r_lose = -100.0f; P.r_draw = 0.0f; P.r_index = 0;   // DDQN.py:289-305
     h->device = dev;
     h->side = nullptr; h->fork = nullptr; h->join = nullptr; h->part0 = 0; h->nparts = 1;
-    h->entry_masks = false;
+    h->entry_masks = h->handed = false;
     h->aligned = (P.G % 4) == 0;
     h->cpe = ((uint32_t)P.G + 15u) / 16u;
     h->cpe_magic = (uint32_t)((0x100000000ull + h->cpe - 1) / h->cpe);   // exact i / cpe for i < 2^32 / cpe
@@ -2401,7 +2499,8 @@ int tron_create(int32_t n_envs, int32_t W, int32_t mode, int32_t fair, uint32_t 
     const size_t log_bytes = P.mode != TRON_MODE_NONE ? N * (size_t)slide_log_len(P.W) * sizeof(uint16_t) : 0;
     const size_t o_grid = 0, o_st4 = align(o_grid + N * P.G + 64), o_rs4 = align(o_st4 + 16 * N),
                  o_slide = align(o_rs4 + 16 * N), o_log = align(o_slide + 8 * N), o_fresh = align(o_log + log_bytes),
-                 o_emask = align(o_fresh + (size_t)P.G + 16), total = align(o_emask + 8 * N);
+                 o_emask = align(o_fresh + (size_t)P.G + 16), o_hand = align(o_emask + 8 * N),
+                 total = align(o_hand + 4 * (size_t)ROLL_HAND_DWORDS * N);
     char *blob = nullptr;
     if (hipMalloc(reinterpret_cast<void **>(&blob), total) != hipSuccess) {
         (void)hipGetLastError();
@@ -2416,6 +2515,7 @@ int tron_create(int32_t n_envs, int32_t W, int32_t mode, int32_t fair, uint32_t 
     P.obs_state = nullptr;
     P.fresh = reinterpret_cast<const int8_t *>(blob + o_fresh);
     h->emask = reinterpret_cast<unsigned long long *>(blob + o_emask);
+    h->hand = reinterpret_cast<uint32_t *>(blob + o_hand);
     if (hipMemsetAsync(blob, 0, total, nullptr) != hipSuccess) { (void)hipGetLastError(); }
     hipLaunchKernelGGL(k_fresh, dim3((P.G + 255) / 256), dim3(256), 0, nullptr, const_cast<int8_t *>(P.fresh), P.S);
     hipLaunchKernelGGL(k_fill_f64, dim3((n_envs + 255) / 256), dim3(256), 0, nullptr, P.slide, 0.15,
@@ -2694,7 +2794,11 @@ int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags_in, StepOut out, h
     if (rec) allow_big_lds(reinterpret_cast<const void *>(k_obs_roll_tape_rec), h->device, prepared_r);
     // TRON_ROLL_FULL_ENTRY: every launch reads whole planes, as if no entry mask were valid (A/B runs, the tests' twin)
     static const bool full_entry = getenv("TRON_ROLL_FULL_ENTRY") != nullptr;
+    // TRON_ROLL_NO_HANDOFF: every launch draws its own first block, as if nothing had been handed over (A/B runs, the tests' twin)
+    static const bool no_handoff = getenv("TRON_ROLL_NO_HANDOFF") != nullptr;
     static bool report = getenv("TRON_ROLL_REPORT") != nullptr;         // the launch shape and its occupancy on stderr, once per process
+    static const bool report_entry = report;                            // and the entry a launch took, whenever it is not the last one reported
+    static int reported_entry = -1;
     if (report) {
         report = false;
         int per_cu = 0;
@@ -2708,21 +2812,35 @@ int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags_in, StepOut out, h
     for (int left = k_steps; left > 0; left -= chunk) {
         // The launch covers all envs (grid x E >= N) and writes every env's entry mask; the one behind it on the stream may
         // enter by them.  Nothing is assumed of a launch that failed.
-        const uint32_t flags = flags_in | (h->entry_masks && !full_entry ? ROLL_ENTRY_MASKED : 0u);
-        h->entry_masks = false;
+        // It hands its helper's rings over as well (autoreset alone); the one behind it takes them if it would draw the same
+        // words: same seed, stream, fair and W.
+        const bool autoreset = (flags_in & TRON_STEP_AUTORESET) != 0u;
+        const bool take = h->handed && autoreset && !no_handoff && h->hand_seed == h->P.seed && h->hand_stream == h->P.stream &&
+                          h->hand_fair == h->P.fair && h->hand_W == h->P.W;
+        const uint32_t flags = flags_in | (h->entry_masks && !full_entry ? ROLL_ENTRY_MASKED : 0u) | (take ? ROLL_ENTRY_HANDED : 0u);
+        h->entry_masks = h->handed = false;
+        if (report_entry) {
+            const int entry = (flags & ROLL_ENTRY_MASKED ? 1 : 0) | (take ? 2 : 0);
+            if (entry != reported_entry)
+                fprintf(stderr, "k_obs_roll: a launch of %d steps enters by %s, its first block's starts%s %s\n", left < chunk ? left : chunk,
+                        entry & 1 ? "the entry masks" : "whole planes", tape ? "" : " and actions", entry & 2 ? "handed over" : "drawn");
+            reported_entry = entry;
+        }
         if (rec) {
             const size_t at = (size_t)(k_steps - left) * (size_t)h->P.N;   // the launch's first row, in envs
             const StepOut rows{out.done ? out.done + at : nullptr, out.winner ? out.winner + at : nullptr,
                                out.reward ? out.reward + 2u * at : nullptr, out.totals};
             hipLaunchKernelGGL(k_obs_roll_tape_rec, dim3(grid), dim3(2 * waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, rows,
-                               left < chunk ? left : chunk, tape + 2u * at, h->emask);
+                               left < chunk ? left : chunk, tape + 2u * at, h->emask, h->hand);
         } else if (tape)
             hipLaunchKernelGGL(k_obs_roll_tape, dim3(grid), dim3(2 * waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, out,
-                               left < chunk ? left : chunk, tape + (size_t)(k_steps - left) * 2u * (size_t)h->P.N, h->emask);
+                               left < chunk ? left : chunk, tape + (size_t)(k_steps - left) * 2u * (size_t)h->P.N, h->emask, h->hand);
         else
-            hipLaunchKernelGGL(k_obs_roll, dim3(grid), dim3(2 * waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, out, left < chunk ? left : chunk, h->emask);
+            hipLaunchKernelGGL(k_obs_roll, dim3(grid), dim3(2 * waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, out, left < chunk ? left : chunk, h->emask, h->hand);
         if (launch_status() != TRON_OK) return TRON_ERR_LAUNCH;
         h->entry_masks = true;
+        h->handed = autoreset;
+        h->hand_seed = h->P.seed; h->hand_stream = h->P.stream; h->hand_fair = h->P.fair; h->hand_W = h->P.W;
     }
     return TRON_OK;
 }

@@ -190,7 +190,18 @@ int tron_encode(tron_handle h, int32_t obs_fmt, void *obs, void *stream);
  * enqueued on streams that order them (one stream, or events), as they already must
  * be for the planes to mean anything.  Results are the same bit for bit either way;
  * the environment variable TRON_ROLL_FULL_ENTRY (read once per process) makes every
- * launch read whole planes, for A/B measurements.                                  */
+ * launch read whole planes, for A/B measurements.
+ * Hand-off.  Every such launch also leaves, in the handle, 76 bytes per env: the
+ * start positions of the env's next restarts, keyed by its episode count, the random
+ * actions of the next launch's first eight steps (not behind an action tape) and the
+ * highest episode held.  They are functions of (env, episode), (env, tick) and the
+ * handle's seed, stream, fair and W alone, and a launch ends with no env finished, so
+ * the next launch of that family loads them instead of drawing them — under the
+ * condition of the entry masks and one more: the call in between may not have written
+ * the state words either, which is the same list of calls.  A second flag per handle
+ * follows the order of the calls in the same way.  Results are the same bit for bit
+ * either way; TRON_ROLL_NO_HANDOFF (read once per process) makes every launch draw
+ * its own first block, for A/B measurements.                                       */
 int tron_rollout_random(tron_handle h, int32_t k_steps, uint32_t flags, int32_t obs_fmt, void *obs,
                         unsigned long long *totals, void *stream);
 

@@ -15,7 +15,11 @@ those steps and for the others; a library from before the helper waves shows the
 Helper rows (a library whose helpers stamp; none are printed for an older one).  Behind the game waves' region, at ceil(N / 64)
 * 2 * (TRON_ROLLOUT_CHUNK + 1) * 4, the helper of each stamped game wave has 4 + 2 * TRON_ROLLOUT_CHUNK / ROLL_R slots: 0
 kernel entry, 1 prologue draws done, 2 arrival at P, 3 departure from P, 2 + 2 b / 3 + 2 b arrival at / departure from the
-barrier B_b in front of block b; the last slot is the game wave's arrival at P.  A game wave arrives at B_b with slot 3 of
+barrier B_b in front of block b; the last slot but one is the end of the hand-off pass (the helper's last block: the next
+launch's first starts and action bytes, stored for it), zero in a library from before it; the last slot is the game wave's
+arrival at P.  Run once as it is (the handed entry: every launch after the first takes what the one before it handed over)
+and once with TRON_ROLL_NO_HANDOFF=1 (the draw entry); the header line says which, and the rows "P: helper's arrival -
+game's", "helper: block 0's work" (its top-up) and "B_1: helper's arrival - game's" are the ones the two entries differ in.  A game wave arrives at B_b with slot 3 of
 step b R - 1 and leaves it with slot 0 of step b R.  Printed per role: the work of a block (release of B_b -> arrival at
 B_(b+1)), the wait at the barriers, and per barrier which role of a pair arrives last and by how much (helper - game).
 usage: roll_stamps.py [--envs N] [--launches L] [--block R] [--old-layout]"""
@@ -101,7 +105,8 @@ def main():
         bs = np.arange(1, nb)                                       # the barriers B_1 .. B_(nb-1)
         g_arr, g_dep = t[:, :, bs * a.block - 1, 3], t[:, :, bs * a.block, 0]
         h_arr, h_dep = h[:, :, 2 + 2 * bs], h[:, :, 3 + 2 * bs]
-        print("the helper beside its game wave")
+        entry = "drawn (TRON_ROLL_NO_HANDOFF)" if os.environ.get("TRON_ROLL_NO_HANDOFF") else "handed over by the launch before"
+        print(f"the helper beside its game wave; block 0's starts and actions: {entry}")
         row("helper: prologue draws (entry -> done)", h[:, :, 1] - h[:, :, 0])
         row("helper: wait at P", h[:, :, 3] - h[:, :, 2])
         row("game: entry -> arrival at P", h[:, :, HS - 1] - t[:, :, K, 0])
@@ -111,7 +116,13 @@ def main():
         print(f"    the helper is the later one at P in {100.0 * (late > 0).mean():.0f} % of the pairs")
         row("game: block's work (release -> next arrival)", g_arr[:, :, 1:] - g_dep[:, :, :-1])
         row("helper: block's work (release -> next arrival)", h_arr[:, :, 1:] - h_dep[:, :, :-1])
-        row("helper: block 0's work (P -> arrival at B_1)", h_arr[:, :, 0] - h[:, :, 3])
+        row("helper: block 0's work, its top-up (P -> arrival at B_1)", h_arr[:, :, 0] - h[:, :, 3])
+        late1 = h_arr[:, :, 0] - g_arr[:, :, 0]
+        row("B_1: helper's arrival - game's", late1)
+        print(f"    the helper is the later one at B_1 in {100.0 * (late1 > 0).mean():.0f} % of the pairs")
+        if (h[:, :, HS - 2] > 0).all():
+            row("helper: hand-off pass (B_(nb-1) left -> stores issued)", h[:, :, HS - 2] - h_dep[:, :, -1])
+            row("helper: hand-off pass ends before its game wave leaves the loop by", t[:, :, K, 1] - h[:, :, HS - 2])
         row("game: wait at a block barrier", g_dep - g_arr)
         row("helper: wait at a block barrier", h_dep - h_arr)
         late = h_arr - g_arr
