@@ -87,6 +87,31 @@ __device__ __forceinline__ bool settle(uint32_t alive, const int r[2], const int
     if (n_alive == 1 && (r[0] != r[1] || c[0] != c[1])) winner = (alive & 1u) ? 1 : 2;
     return true;
 }
+// The same two in CELL SPACE, for a caller that carries the heads as indices into the padded S x S board and no r / c.
+// The padded index determines both (cell = (r + 1) S + (c + 1) with 0 <= r + 1, c + 1 < S), so nothing is lost, and
+// the on_board test folds into the target test:
+//   (a) every border cell of a fresh board is WALL (k_fresh), and in mode None nothing ever writes EMPTY to a cell of a
+//       game in progress (a move writes bodies and heads; a restart brings back the fresh board, border WALL included);
+//   (b) a player that moves is alive (a step moves only while the game is not done: both alive), so its old head is an
+//       interior cell and its new head, one cell further, lies in the padded board — on the border ring exactly when
+//       it left the board.
+// Hence !on_board(W, r, c) implies that the target cell is not EMPTY, and collide is the target test alone.  Two heads
+// are on one cell exactly when their indices are equal: settle's head-on test.
+__device__ __forceinline__ uint32_t collide(uint32_t alive, int p, bool target_empty)
+{
+    return !target_empty ? alive & ~(1u << p) : alive;
+}
+__device__ __forceinline__ bool settle(uint32_t alive, const int cell[2], int &winner)
+{
+    const int n_alive = (int)(alive & 1u) + (int)((alive >> 1) & 1u);
+    if (n_alive > 1) return false;
+    if (n_alive == 1 && cell[0] != cell[1]) winner = (alive & 1u) ? 1 : 2;
+    return true;
+}
+// player.py:124-132 in cell space: the four actions' cell deltas {-S, +1, +S, -1} as signed bytes of one word (S <= 32:
+// -S fits a byte), and the delta of action a taken from it
+__device__ __forceinline__ uint32_t cell_deltas(int S) { return pack_pos(-S, 1, S, -1); }   // (four int8 in a word)
+__device__ __forceinline__ int cell_delta(uint32_t deltas, int a) { return (int)(int8_t)(deltas >> (8u * (uint32_t)a)); }
 // util.py:87-94 / DDQN.py:289-305 / DQN.py:224-241; eplen = steps of this game before the move
 __device__ __forceinline__ void step_rewards(const Params &P, bool done, int winner, uint32_t eplen, float &rw0, float &rw1)
 {

@@ -970,12 +970,17 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 // prologue to the epilogue.  Nobody else touches an env's planes or state words during the launch, and nobody can read them
 // before it ends, so everything a step reads or writes is carried from the step before: the env's state, rs4 and the
 // block's action bytes in the lane's registers, the board in the lane's own region of LDS (4 bits per cell, above).
-// The state is carried DECODED: the two heads' r and c (collide and settle take them), their cell indices, the LDS address
+// The state is carried DECODED and in CELL SPACE: the two heads' indices into the padded board (no r and no c: the index
+// determines both, and collide / settle have cell-space overloads with the argument, tron_device.hpp), the LDS address
 // and nibble shift of each head's dword and its chunk's mask bit, alive, done, winner, the two last actions + 1 (the
 // non-reversing policy), eplen and tick.  The prologue unpacks st4 into them once; a step moves a head's cell by +-1 or
-// +-S and derives the rest of the new head from that, and the old heads' cells, addresses and bits are simply the ones the
-// step before computed; a restart sets them all from rs4.nstart; the epilogue packs st4 once, under st_dirty, into the bytes
-// stepped_st4 / restarted_st4 of the env's last event would have left.  The helper reads st and rs as loaded.  The game
+// +-S — one signed byte of the launch-uniform word cell_deltas(S), picked by the action — and derives the rest of the new
+// head from that, and the old heads' cells, addresses and bits are simply the ones the step before computed; a restart
+// sets them all from rs4.nstart; the epilogue divides r and c back out of the cells (one division by S per env and
+// launch) and packs st4 once, under st_dirty, into the bytes stepped_st4 / restarted_st4 of the env's last event would
+// have left.  A block's action bytes are consumed once where they are loaded, so no step waits for them: between a
+// step's last LDS operation and the next step's reads stands no s_waitcnt, and the restart's start-ring read is waited
+// for where rs.z is next used, the lane's next restart.  The helper reads st and rs as loaded.  The game
 // wave does the move, a restarted env's board, the records and the lane's tally of the totals; what is random — the actions
 // of every step and the starts of every restarted env's next game — its helper wave draws ahead of it into rings in LDS
 // (roll_helper above: the rings, their invariants and the barriers).  The step loop has ONE workgroup barrier per block of
@@ -1338,7 +1343,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
     uint32_t nres = 0u;                                             // this env's restarts in the launch
     uint32_t n_steps = 0u, n_w1 = 0u, n_w2 = 0u, n_draw = 0u;        // this wave's totals (uniform)
     uint32_t tally = 0u;                                            // this env's share of them, a byte each, since the last flush
-    int S = 0, W = 0;                                               // all the step loop needs of Params: two SGPRs for the whole launch
+    int S = 0;                                                      // all the step loop needs of Params (as S and cell_deltas(S): two SGPRs)
 
     ROLL_STAMP_LAUNCH(0);
     // ---- prologue: the only loads from memory of the launch
@@ -1347,7 +1352,6 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         load_params_scalar(P, kp);
         const int G = P.G;
         S = P.S;
-        W = P.W;
         const int ne = min(min(epw, E - we0), P.N - e0);            // this wave's envs (<= 0: none)
         mine = lane < ne;
         oenv = P.obs_state + (size_t)(mine ? env : 0) * 2u * G;
@@ -1488,9 +1492,14 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
     size_t row = 0;                                                 // in envs: N per step (no multiply in the loop)
 
     // ---- the env's state, decoded once: the loop carries these in place of st and the epilogue packs them again
-    int r[2], c[2];                                                 // the heads (a dead player's may be off the board)
-    unpack_pos(st.x, r, c);
-    int cell[2] = {roll_cell(S, r[0], c[0]), roll_cell(S, r[1], c[1])};
+    int cell[2];                                                    // the heads, in cell space (a dead player's may be on the border ring)
+    {
+        int r[2], c[2];
+        unpack_pos(st.x, r, c);
+        cell[0] = roll_cell(S, r[0], c[0]);
+        cell[1] = roll_cell(S, r[1], c[1]);
+    }
+    const uint32_t deltas = cell_deltas(S);                         // launch-uniform: one SGPR
     unsigned long long hbit[2] = {1ull << (cell[0] >> 4), 1ull << (cell[1] >> 4)};   // the heads' chunks, as mask bits
     uint32_t alive = st.y & 3u;
     bool done = (st.y & META_DONE) != 0u;
@@ -1511,6 +1520,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
             __syncthreads();
         }
         ab = aring[((s0 / ROLL_R) & 1) * WAVE + lane];
+        asm volatile("" : "+v"(ab.x), "+v"(ab.y));                  // consumed here, once: the wait for the block's bytes stands in front of the inner loop, not in every step's tail
         const int s1 = min(s0 + ROLL_R, k_steps);
 #pragma nounroll
         for (int s = s0; s < s1; ++s) {                             // the block's steps: ab.x's low byte is this step's
@@ -1529,11 +1539,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
                 uint32_t nk[2], ndw[2], nsh[2];
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
-                    int dr, dc;
-                    action_delta(a[p], dr, dc);
-                    r[p] += dr;
-                    c[p] += dc;
-                    ncell[p] = cell[p] + __mul24(dr, S) + dc;
+                    ncell[p] = cell[p] + cell_delta(deltas, a[p]);
                     nk[p] = (uint32_t)ncell[p] >> 4;
                     asm("" : "+v"(nk[p]));                           // (the chunk index as one value: its two dwords are one ds_read2 / ds_write2)
                     nbit[p] = 1ull << nk[p];
@@ -1560,8 +1566,8 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
                 }
                 plain_targets(cell, ncell, tf, NIB_P1_BODY, NIB_P2_BODY, NIB_P1_HEAD);
 #pragma unroll
-                for (int p = 0; p < 2; ++p) alive = collide(alive, p, W, r[p], c[p], tf[p] == NIB_EMPTY);
-                done = settle(alive, r, c, winner);
+                for (int p = 0; p < 2; ++p) alive = collide(alive, p, tf[p] == NIB_EMPTY);   // (cell space: off the board is a border WALL)
+                done = settle(alive, ncell, winner);
                 if constexpr (REC)
                     if (out.reward) step_rewards(P, done, winner, eplen, rw0, rw1);
                 last[0] = (uint32_t)a[0] + 1u;
@@ -1614,6 +1620,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
             // rs4.envp and rs4.nenvp stay as the prologue read them until the epilogue (no step of mode None reads them).
             // The carried state becomes restarted_st4's: the heads at rs4.nstart, both alive, no last action, eplen 0.
             if (mine && done && autoreset) {
+                int r[2], c[2];
                 unpack_pos(rs.z, r, c);
                 alive = META_ALIVE0 | META_ALIVE1;
                 done = false;
@@ -1755,8 +1762,15 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         ROLL_STAMP_LAUNCH(2);
         // st4 is packed here alone, from the carried state: the bytes stepped_st4 or restarted_st4 of the env's last event
         // would have left (last[] is the stored action + 1, and 0 behind a restart; a dead player's head may be off the board)
-        if (mine && st_dirty)
+        // r and c come back from the cells, one division by S per env and launch: cell = (r + 1) S + (c + 1) with both terms
+        // in [0, S), so the quotient and the remainder are r + 1 and c + 1 — a dead player's head on the border ring gives
+        // the -1 or W that carrying r and c through the moves gave
+        if (mine && st_dirty) {
+            const uint32_t q0 = (uint32_t)cell[0] / (uint32_t)S, q1 = (uint32_t)cell[1] / (uint32_t)S;
+            const int r[2] = {(int)q0 - 1, (int)q1 - 1};
+            const int c[2] = {cell[0] - (int)q0 * S - 1, cell[1] - (int)q1 * S - 1};
             P.st4[env] = make_uint4(pack_pos(r[0], c[0], r[1], c[1]), pack_meta(alive, done, winner, (int)last[0] - 1, (int)last[1] - 1), eplen, tick);
+        }
         // The next launch's entry mask (the masked entry above): what differs from the template now lies inside mask, and the
         // stores above left memory outside it the template.  Every env of the launch, a lane that did not step (the mask it
         // entered with) included.
