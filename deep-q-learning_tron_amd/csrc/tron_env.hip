@@ -27,7 +27,7 @@
 //   k_tile / tile_step      board-owning layout (grid[N][G] + caller's obs): every mode, format, side
 //   k_obs / obs_tile        observation-is-state (mode None, int8 codes, even side): the caller's
 //                           attached obs buffer is the env state; read G, write 2G per env-step
-//   k_obs_roll, k_tile_roll tron_rollout_random: up to TRON_ROLLOUT_CHUNK steps in ONE launch.  k_obs_roll (roll_resident):
+//   k_obs_roll, k_tile_roll tron_rollout_random: up to ROLL_LAUNCH_CAP (k_obs_roll) / TRON_ROLLOUT_CHUNK steps in ONE launch.  k_obs_roll (roll_resident):
 //                           one lane per env and a game wave that owns its envs for the whole launch, with a helper wave
 //                           beside it on its SIMD that draws every Philox word of the launch into LDS rings (one
 //                           workgroup barrier per block of ROLL_R steps, none inside a block: roll_helper),
@@ -96,6 +96,10 @@ struct StepOut {
 // departure from P, 2 + 2 b / 3 + 2 b arrival at / departure from B_b; the last slot but one is the end of the hand-off
 // pass, which begins at the departure from B_(nb-1), or from P in a launch of one block; behind a handed entry slot 1 is
 // "the handed words are in the rings"; the last slot is the GAME wave's arrival at P, which its own layout has no place for).
+// A launch may be longer than TRON_ROLLOUT_CHUNK steps (ROLL_LAUNCH_CAP) and the regions are not: the first
+// TRON_ROLLOUT_CHUNK steps and the barriers in front of the first TRON_ROLLOUT_CHUNK / 8 blocks are stamped (ROLL_STAMP,
+// ROLL_HSTAMP_BLOCK: the step or block is tested against the region before the store), the later ones are not, and the
+// launch-level slots are the whole launch's.
 #ifdef TRON_STAMPS
 constexpr int ROLL_HSTAMPS = 4 + 2 * (TRON_ROLLOUT_CHUNK / 8);
 #define ROLL_HSTAMP(slot)                                                                         \
@@ -108,9 +112,13 @@ constexpr int ROLL_HSTAMPS = 4 + 2 * (TRON_ROLLOUT_CHUNK / 8);
         if (out.totals && (tid == 0 || tid == 64))                                                \
             out.totals[((size_t)blockIdx.x * 2 + (tid >> 6)) * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); \
     } while (0)
+#define ROLL_HSTAMP_BLOCK(b, k)                                                                   \
+    do {                                                                                          \
+        if ((b) < TRON_ROLLOUT_CHUNK / 8) ROLL_HSTAMP(2 + 2 * (b) + (k));                         \
+    } while (0)
 #define ROLL_STAMP(slot)                                                                          \
     do {                                                                                          \
-        if (out.totals && (tid == 0 || (tid == 64 && gw > 1)))                                              \
+        if (out.totals && s < TRON_ROLLOUT_CHUNK && (tid == 0 || (tid == 64 && gw > 1)))                    \
             out.totals[(((size_t)blockIdx.x * 2 + (tid >> 6)) * (TRON_ROLLOUT_CHUNK + 1) + s) * 4 + (slot)] = __builtin_amdgcn_s_memrealtime(); \
     } while (0)
 #define ROLL_STAMP_LAUNCH(slot)                                                                   \
@@ -123,6 +131,7 @@ constexpr int ROLL_HSTAMPS = 4 + 2 * (TRON_ROLLOUT_CHUNK / 8);
 #define ROLL_STAMP(slot) do { } while (0)
 #define ROLL_STAMP_LAUNCH(slot) do { } while (0)
 #define ROLL_HSTAMP(slot) do { } while (0)
+#define ROLL_HSTAMP_BLOCK(b, k) do { } while (0)
 #endif
 
 struct __attribute__((packed, aligned(4))) U4A4 {   // 16 bytes at 4-byte alignment
@@ -1207,9 +1216,9 @@ __device__ __forceinline__ void roll_helper(const Params &P, int env, bool autor
     for (int b = -1; b < nb; ++b) {                                 // pass b draws for block b + 1: before P, then during block b
         uint32_t base = 0u;                                         // c_b + ROLL_R: what block b can have consumed at the most
         if (b > 0) {
-            ROLL_HSTAMP(2 + 2 * b);
+            ROLL_HSTAMP_BLOCK(b, 0);
             __syncthreads();                                        // B_b
-            ROLL_HSTAMP(3 + 2 * b);
+            ROLL_HSTAMP_BLOCK(b, 1);
         }
         const bool last = b + 1 >= nb;                              // the hand-off pass: the launch has no block b + 1
         if (last && !autoreset) break;
@@ -2728,7 +2737,8 @@ int tron_get_state(tron_handle h, int8_t *pos, int8_t *alive, int8_t *dir, int8_
 
 namespace {
 
-// k_steps steps of the observation-is-state kernel as persistent launches of at most TRON_ROLLOUT_CHUNK steps, one tile per
+// k_steps steps of the observation-is-state kernel as persistent launches of at most TRON_ROLLOUT_CHUNK steps (k_obs_roll and
+// its tape forms: ROLL_LAUNCH_CAP, above rollout_wave), one tile per
 // workgroup: with more workgroups than the chip holds at once the late ones start as the early ones finish their steps.
 // TRON_ROLL_E / TRON_ROLL_GRID / TRON_ROLL_CHUNK override tile size, grid and steps per launch.
 // Tile size for the kernels that run obs_tile every step (the sliding modes; k_obs_roll_walk has the same code and occupancy
@@ -2785,6 +2795,19 @@ size_t roll_smem(const tron_env *h, int E, int waves)
 {
     return ((size_t)E * (2u * h->cpe + 1u) + 2u * h->cpe + (size_t)waves * (32u * h->cpe) + 1u + (size_t)waves * ROLL_RING_DWORDS) * 4u;
 }
+
+// Steps per launch of the roll_resident family (k_obs_roll, k_obs_roll_tape, k_obs_roll_tape_rec): the whole call, up to this
+// many.  A launch pays its prologue, its epilogue and the ramp and tail of the grid once, about 20 us at 65 536 x 24x24
+// where a step is 0.8 us: a quarter of a 64-step launch (TRON_ROLLOUT_CHUNK, chosen when a step was 20 us and still the
+// other kernels' length), and between two launches stands a device-wide barrier between workgroups that exchange nothing,
+// with an epilogue that stores what the next prologue loads straight back.  At 1 024 steps the fixed share is 2 % — nothing
+// left worth a longer launch — and a launch stays near 1 ms, so that a call of 100 000 steps does not hold the chip in one
+// dispatch: it splits into launches of the cap, the remainder last, as it always split at 64.  Nothing in the kernel counts
+// on a length: the byte tallies are flushed every 128 steps, the start ring is keyed by the absolute episode and
+// topped up by count, restart counts, ticks and rows are 32-bit and wider.  TRON_ROLL_CHUNK overrides it (A/B runs:
+// TRON_ROLL_CHUNK=64 is the launches as they were; scripts/roll_sweep.py, scripts/roll_fixed_cost.sh).
+constexpr int ROLL_LAUNCH_CAP = 1024;
+static_assert(ROLL_LAUNCH_CAP % 128 == 0, "whole tally periods and whole blocks: the launches of a long call are all alike");
 
 // tape: null for k_obs_roll's own draws; else the caller's int8[k_steps][N][2], and every launch gets it advanced to its
 // own first step (k_obs_roll_tape: same grid, same workgroup, same LDS).  A tape call that asks for records (any of
@@ -2863,13 +2886,16 @@ int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags_in, StepOut out, h
 // caller then steps per launch.
 int rollout_persistent(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipStream_t st, const int8_t *tape = nullptr)
 {
-    static int env_e = 0, env_grid = 0, env_waves = 0, chunk = TRON_ROLLOUT_CHUNK;
+    // chunk: steps per launch of the kernels that run obs_tile every step (k_obs_roll_walk, k_obs_roll_slide);
+    // wave_chunk: of the roll_resident family (ROLL_LAUNCH_CAP).  TRON_ROLL_CHUNK sets both.
+    static int env_e = 0, env_grid = 0, env_waves = 0, chunk = TRON_ROLLOUT_CHUNK, wave_chunk = ROLL_LAUNCH_CAP;
     static bool probed = false;
     if (!probed) {
         if (const char *v = getenv("TRON_ROLL_E")) env_e = atoi(v);
         if (const char *v = getenv("TRON_ROLL_WAVES")) env_waves = atoi(v);
         if (const char *v = getenv("TRON_ROLL_GRID")) env_grid = atoi(v);
-        if (const char *v = getenv("TRON_ROLL_CHUNK")) chunk = atoi(v) > 0 ? atoi(v) : TRON_ROLLOUT_CHUNK;
+        if (const char *v = getenv("TRON_ROLL_CHUNK"))
+            if (atoi(v) > 0) chunk = wave_chunk = atoi(v);
         probed = true;
     }
     const bool sliding = h->P.mode != TRON_MODE_NONE;
@@ -2882,7 +2908,7 @@ int rollout_persistent(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out
         // the same way; a TRON_ROLL_E that needs more waves than fit (256 envs at 30x30) is TRON_ERR_BAD_ARG in rollout_wave.
         while (env_e <= 0 && waves > 1 && roll_smem(h, waves * ROLL_EPW, waves) > 160u * 1024u) --waves;
         const int E = env_e > 0 ? env_e : waves * ROLL_EPW;
-        if (!(env_grid > 0 && env_grid < (h->P.N + E - 1) / E)) return rollout_wave(h, k_steps, flags, out, st, E, waves, chunk, tape);
+        if (!(env_grid > 0 && env_grid < (h->P.N + E - 1) / E)) return rollout_wave(h, k_steps, flags, out, st, E, waves, wave_chunk, tape);
     }
     if (tape) return TRON_ERR_UNSUPPORTED;
     planes_written(h);              // k_obs_roll_walk, k_obs_roll_slide

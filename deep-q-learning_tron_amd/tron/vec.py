@@ -182,8 +182,9 @@ class VecTron:
 
     def rollout_random(self, k_steps, totals=None, nonreversing=False, per_step_launches=False, two_streams=False,
                        resident=False):
-        """k_steps random-action steps with autoreset (the BASELINE synthetic rollout): persistent launches of
-        up to 64 steps each, or — per_step_launches=True — one launch per step, or — two_streams=True — one launch
+        """k_steps random-action steps with autoreset (the BASELINE synthetic rollout): one persistent
+        launch for up to 1 024 steps in mode None on the attached int8 codes (a longer call splits into launches of 1 024
+        steps; the sliding modes: up to 64 steps each), or — per_step_launches=True — one launch per step, or — two_streams=True — one launch
         per step and per half of the envs on two streams (same results every way).  self.obs holds the observations of the
         last step once the call's work completes on the stream: a persistent launch in mode None writes them at its end, and
         only per_step_launches=True puts every step's observations into memory.  resident=True (observation-is-state
@@ -200,8 +201,8 @@ class VecTron:
         """K steps with autoreset whose actions come from a tape: `actions` is a contiguous int8 tensor [K, N, 2] in 0..3 on
         this env's device, row k what step(actions[k]) would take (recorded games, scripted openings, a planner's candidate
         sequences, action repeat).  Same boards, state, observations and totals, bit for bit, as K calls of
-        step(actions[k], autoreset=True).  Mode None on the attached int8 codes runs as persistent launches of up to 64
-        steps (the launch of rollout_random, its action bytes copied from the tape); every other mode, side and format —
+        step(actions[k], autoreset=True).  Mode None on the attached int8 codes runs as one persistent launch for up to 1 024
+        steps, a longer tape as launches of 1 024 (the launch of rollout_random, its action bytes copied from the tape); every other mode, side and format —
         and per_step_launches=True — is one launch per step.  self.obs holds the observations of the last step once the
         call's work completes on the stream; the tape must not be overwritten before that.
         records: None (nothing is recorded and None is returned), True, or a tuple (reward, done, winner) in the order of

@@ -61,7 +61,9 @@ enum {
                                    * that do not reverse its last move (all four before its first move) instead
                                    * of from all four — the longer-episode synthetic policy of SURVEY.md §8(d) */
 
-#define TRON_ROLLOUT_CHUNK 64     /* steps per persistent rollout launch (tron_rollout_random) */
+#define TRON_ROLLOUT_CHUNK 64     /* steps per persistent rollout launch of the sliding modes, of boards of more than 64 chunks and
+                                   * without an attached buffer; the mode None launches of the attached int8 codes run a whole call
+                                   * of up to 1 024 steps (tron_rollout_random) */
 #define TRON_ROLLOUT_PER_STEP 8u  /* tron_rollout_random flag: one launch per step instead (for A/B measurements); the
                                    * form in which every step's observations are in memory, one after the other     */
 #define TRON_ROLLOUT_RESIDENT 32u  /* tron_rollout_random flag, attached observation buffer only: within a persistent launch
@@ -162,7 +164,9 @@ int tron_encode(tron_handle h, int32_t obs_fmt, void *obs, void *stream);
 
 /* K random-action steps with autoreset on `stream` (the synthetic rollout of
  * BASELINE.json).  With an attached observation buffer (tron_attach_obs_state) the
- * steps run as persistent launches of at most TRON_ROLLOUT_CHUNK steps each: envs
+ * steps run as persistent launches — in mode None on boards of at most 64 chunks ONE
+ * launch per call of up to 1 024 steps (longer calls: launches of 1 024 steps, the
+ * remainder last), elsewhere launches of at most TRON_ROLLOUT_CHUNK steps each: envs
  * never interact, so every workgroup steps its own envs without a chip-wide drain
  * between steps — same results, bit for bit, as one launch per step (the other
  * storage modes / formats do launch per step).  flags: 0 or TRON_STEP_NONREVERSING.
@@ -184,7 +188,7 @@ int tron_encode(tron_handle h, int32_t obs_fmt, void *obs, void *stream);
  * does not run as persistent mode-None launches (one step, TRON_ROLLOUT_PER_STEP,
  * TRON_ROLLOUT_TWO_STREAMS, the sliding modes, boards of more than 64 chunks) make the
  * next launch read whole planes again.  That holds between the launches of one call of
- * more than TRON_ROLLOUT_CHUNK steps and between consecutive calls.  The host keeps
+ * more than 1 024 steps and between consecutive calls.  The host keeps
  * this as one flag per handle that follows the ORDER OF THE CALLS, as the planes
  * themselves follow the order of the work on the stream: calls on one handle are
  * enqueued on streams that order them (one stream, or events), as they already must
@@ -215,7 +219,7 @@ int tron_rollout_random(tron_handle h, int32_t k_steps, uint32_t flags, int32_t 
  * finished when a step begins (stepped without autoreset before) restarts in that step and makes no move: the step's
  * row is not used for it.
  * Mode None with an attached observation buffer and TRON_OBS_CODES_I8 (or TRON_OBS_NONE): persistent launches of at
- * most TRON_ROLLOUT_CHUNK steps, the launch of tron_rollout_random with the action bytes copied from the tape (2 bytes
+ * most 1 024 steps (one launch for a shorter tape), the launch of tron_rollout_random with the action bytes copied from the tape (2 bytes
  * read per env-step) — and, as there, the planes and the state words are written when a launch ends.  Everywhere else
  * — the sliding modes, odd W, f32 planes, no attached buffer, boards of more than 64 chunks — and with
  * TRON_ROLLOUT_PER_STEP the call is a loop over tron_step_encode's launch with row k: the same results, no new kernel.

@@ -22,7 +22,11 @@ and once with TRON_ROLL_NO_HANDOFF=1 (the draw entry); the header line says whic
 game's", "helper: block 0's work" (its top-up) and "B_1: helper's arrival - game's" are the ones the two entries differ in.  A game wave arrives at B_b with slot 3 of
 step b R - 1 and leaves it with slot 0 of step b R.  Printed per role: the work of a block (release of B_b -> arrival at
 B_(b+1)), the wait at the barriers, and per barrier which role of a pair arrives last and by how much (helper - game).
-usage: roll_stamps.py [--envs N] [--launches L] [--block R] [--old-layout]"""
+--steps K: the launches are K steps long (default 64; 320 is the benchmark's call as one launch).  The regions are not
+longer for it: a build stamps the first TRON_ROLLOUT_CHUNK = 64 steps and the barriers of the first 8 blocks, and the
+launch-level slots (kernel entry, loop left, stores issued, kernel end; the hand-off pass's end) are the whole launch's.  The
+per-step rows are then those of the first 64 steps; "step loop" and "first kernel entry -> last kernel end" are the K steps'.
+usage: roll_stamps.py [--envs N] [--launches L] [--block R] [--steps K] [--old-layout]"""
 import argparse
 import os
 import sys
@@ -41,14 +45,16 @@ def main():
     ap.add_argument("--envs", type=int, default=65536)
     ap.add_argument("--launches", type=int, default=4)
     ap.add_argument("--block", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--old-layout", action="store_true")
     a = ap.parse_args()
-    N, W, K = a.envs, 24, 64
+    N, W, K = a.envs, 24, 64                                        # K: the stamped steps of a launch
+    assert a.steps >= K
     R = K if a.old_layout else K + 1                                # stamp blocks per wave
     env = tv.VecTron(N, W, seed=0x5EED, obs_format="codes")
     env.reset()
     for _ in range(3):
-        env.rollout_random(K)                                       # (the stamped build leaves a totals pointer alone when it is None)
+        env.rollout_random(a.steps)                                 # (the stamped build leaves a totals pointer alone when it is None)
     # The buffer is sized for the largest grid the host can choose, one 64-env wave per workgroup; with four waves per
     # workgroup (256 envs) the grid is a quarter of that.  Slots nobody wrote (a workgroup past the grid, the helper wave
     # that is wave 1 of a one-wave-shape workgroup) are told by a zero first stamp and left out.
@@ -58,7 +64,7 @@ def main():
     runs, hruns = [], []
     for _ in range(a.launches):
         buf = torch.zeros(blocks * 2 * R * 4 + nh, dtype=torch.int64, device="cuda")
-        env.rollout_random(K, buf)
+        env.rollout_random(a.steps, buf)
         torch.cuda.synchronize()
         flat = buf.cpu().numpy()
         r = flat[:blocks * 2 * R * 4].reshape(blocks * 2, R, 4)
@@ -75,8 +81,8 @@ def main():
 
     phases = [("move (0->1)", 0, 1), ("restart: state, board, next starts (1->2)", 1, 2), ("records (+ Philox) (2->3)", 2, 3), ("restart + records (+ Philox) (1->3)", 1, 3),
               ("whole (0->3)", 0, 3)]
-    print(f"{N} envs x {W}x{W}, {waves} stamped waves, {a.launches} launches of {K} steps; us, median [p10 p90], mean")
-    for label, steps in (("step 0 (first of the launch)", [0]), ("steps 1..62", list(range(1, K - 1))), ("step 63 (last: no Philox block after it)", [K - 1])):
+    print(f"{N} envs x {W}x{W}, {waves} stamped waves, {a.launches} launches of {a.steps} steps" + (f" (the first {K} stamped)" if a.steps > K else "") + "; us, median [p10 p90], mean")
+    for label, steps in (("step 0 (first of the launch)", [0]), ("steps 1..62", list(range(1, K - 1))), ("step 63 (last: no Philox block after it)" if a.steps == K else "step 63", [K - 1])):
         print(label)
         for name, i, j in phases:
             row(name, t[:, :, steps, j] - t[:, :, steps, i])
@@ -95,6 +101,10 @@ def main():
         print("the launch, per wave")
         row("prologue (kernel entry -> first step)", t[:, :, 0, 0] - t[:, :, K, 0])
         row("step loop (first step -> loop left)", t[:, :, K, 1] - t[:, :, 0, 0])
+        if a.steps > K:
+            loop = t[:, :, K, 1] - t[:, :, 0, 0]
+            print(f"    per launch, p90 - p10 of the waves' loop times: " + " ".join(f"{np.percentile(x, 90) - np.percentile(x, 10):.2f}" for x in loop) + " us")
+            row(f"the first {K} steps of the loop (first step -> step {K - 1}'s last stamp)", t[:, :, K - 1, 3] - t[:, :, 0, 0])
         row("epilogue: plane stores issued", t[:, :, K, 2] - t[:, :, K, 1])
         row("epilogue: state words", t[:, :, K, 3] - t[:, :, K, 2])
         whole = t[:, :, K, 3].reshape(a.launches, -1).max(1) - t[:, :, K, 0].reshape(a.launches, -1).min(1)
@@ -120,7 +130,7 @@ def main():
         late1 = h_arr[:, :, 0] - g_arr[:, :, 0]
         row("B_1: helper's arrival - game's", late1)
         print(f"    the helper is the later one at B_1 in {100.0 * (late1 > 0).mean():.0f} % of the pairs")
-        if (h[:, :, HS - 2] > 0).all():
+        if (h[:, :, HS - 2] > 0).all() and a.steps == K:          # (a longer launch: B_(nb-1) is not among the stamped barriers)
             row("helper: hand-off pass (B_(nb-1) left -> stores issued)", h[:, :, HS - 2] - h_dep[:, :, -1])
             row("helper: hand-off pass ends before its game wave leaves the loop by", t[:, :, K, 1] - h[:, :, HS - 2])
         row("game: wait at a block barrier", g_dep - g_arr)
