@@ -2296,11 +2296,11 @@ struct tron_env {
     unsigned long long *emask; // [N] in the blob: k_obs_roll's entry masks, written by every launch of the roll_resident family
     uint32_t *hand;           // [ROLL_HAND_DWORDS][N] in the blob, next to the entry masks: the helper's hand-off (roll_helper)
     bool entry_masks;         // the entry masks describe the attached planes: the last call that could write the planes or the
-                              // state words enqueued was such a launch over all envs (set in rollout_wave, cleared by
-                              // planes_written; it follows the order of the calls, as the planes follow the order of the stream)
+                              // state words enqueued was such a launch over all envs (set in rollout_wave, cleared by launch()
+                              // per writes_state; it follows the order of the calls, as the planes follow the order of the stream)
     bool handed;              // `hand` is what the next launch of the family would draw: the last call enqueued that could write
                               // the state words was such a launch with autoreset, made with the four values below (set in
-                              // rollout_wave, cleared by planes_written and by a launch without autoreset)
+                              // rollout_wave, cleared like entry_masks and by a launch without autoreset)
     uint32_t hand_seed, hand_stream;
     int hand_fair, hand_W;
 };
@@ -2309,24 +2309,94 @@ namespace {
 
 inline hipStream_t S_(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
-// Every entry point that can write the planes or the state words other than through the roll_resident family: k_obs_roll's
-// next launch reads whole planes again and draws its own first block (the state words' tick and episode may have moved).
-inline void planes_written(tron_env *h) { h->entry_masks = h->handed = false; }
+constexpr size_t LDS_LIMIT = 160u * 1024u;   // a CU's LDS: the most a workgroup can be given, and only after the opt-in (allow_big_lds)
 
-inline int launch_status()
+inline bool is_f32_planes(int fmt) { return fmt == TRON_OBS_PLANES3_F32 || fmt == TRON_OBS_PLANES4_F32; }
+
+// The TRON_* overrides of the environment, all of them: read once per process, at the first call that looks at one.
+//   name                  meaning                                                                         used by
+//   TRON_TILE_ENVS        envs per workgroup tile of the per-step kernels (1..64, while the tile fits)    scripts/microbench.py, scripts/stamps.py
+//   TRON_ROLL_E           envs per workgroup of the persistent launches                                   scripts/roll_sweep.py
+//   TRON_ROLL_WAVES       game waves per workgroup of roll_resident, instead of roll_waves()              A/B runs by hand (the sweep above roll_waves)
+//   TRON_ROLL_GRID        workgroups of a persistent launch; below the tile count: k_obs_roll_walk        scripts/roll_sweep.py, tests/test_gpu_rollout_steady.py
+//   TRON_ROLL_CHUNK       steps per persistent launch, of BOTH kernel families (64: as they once were)    tests/test_gpu_rollout_long_launch.py, scripts/roll_sweep.py, scripts/roll_fixed_cost.sh
+//   TRON_ROLL_PER_STEP    set: every rollout is one launch per step                                       bench.py (A/B switch)
+//   TRON_ROLL_FULL_ENTRY  set: every roll_resident launch reads whole planes, as if no mask were valid    A/B runs by hand (the masked entry)
+//   TRON_ROLL_NO_HANDOFF  set: every roll_resident launch draws its own first block                       tests/test_gpu_rollout_handoff.py, scripts/roll_stamps.py
+//   TRON_ROLL_REPORT      set: k_obs_roll's launch shape (once) and each change of entry, on stderr       by hand (the launch shape)
+struct Overrides {
+    int tile_envs, roll_e, roll_waves, roll_grid, roll_chunk;      // 0 (or an unusable value): not set
+    bool per_step, full_entry, no_handoff, report;
+};
+const Overrides &overrides()
 {
-    return hipGetLastError() == hipSuccess ? TRON_OK : TRON_ERR_LAUNCH;
+    static const Overrides o = [] {
+        auto num = [](const char *name) { const char *v = getenv(name); return v ? atoi(v) : 0; };
+        auto set = [](const char *name) { return getenv(name) != nullptr; };
+        return Overrides{num("TRON_TILE_ENVS"), num("TRON_ROLL_E"), num("TRON_ROLL_WAVES"), num("TRON_ROLL_GRID"), num("TRON_ROLL_CHUNK"),
+                         set("TRON_ROLL_PER_STEP"), set("TRON_ROLL_FULL_ENTRY"), set("TRON_ROLL_NO_HANDOFF"), set("TRON_ROLL_REPORT")};
+    }();
+    return o;
 }
 
-// hipFuncSetAttribute acts on the current device only: remember, per kernel, which devices it was
-// prepared on (one bit per device ordinal) instead of a per-process flag.
-inline void allow_big_lds(const void *kern, int device, uint64_t &prepared)
+// Does a kernel write the attached planes or the state words (st4 / rs4) outside the hand-over protocol of the roll_resident
+// family?  Behind one that does, k_obs_roll's next launch must read whole planes again and draw its own first block (the
+// state words' tick and episode may have moved): launch() clears the handle's entry_masks and handed for it.  Every kernel
+// of this file has a row; one without does not compile.
+template <auto Kernel> struct writes_state;
+#define TRON_KERNEL(WRITES, ...) template <> struct writes_state<__VA_ARGS__> : std::bool_constant<WRITES> {}
+// k_tile: its step (DO_STEP) moves st4 / rs4 and the handle's own boards; encode-only reads them and writes the caller's
+// observations.  k_tile_roll: k_tile's step, k_steps of them.
+#define TRON_TILE(F, A) TRON_KERNEL(true, k_tile<F, true, A>); TRON_KERNEL(false, k_tile<F, false, A>); TRON_KERNEL(true, k_tile_roll<F, A>)
+TRON_TILE(TRON_OBS_NONE, true); TRON_TILE(TRON_OBS_CODES_I8, true); TRON_TILE(TRON_OBS_PLANES3_F32, true); TRON_TILE(TRON_OBS_PLANES4_F32, true);
+TRON_TILE(TRON_OBS_NONE, false); TRON_TILE(TRON_OBS_CODES_I8, false); TRON_TILE(TRON_OBS_PLANES3_F32, false); TRON_TILE(TRON_OBS_PLANES4_F32, false);
+#undef TRON_TILE
+TRON_KERNEL(true, k_obs<true>);           // a step on the attached planes: planes, st4, rs4
+TRON_KERNEL(true, k_obs_slide);           // the sliding modes' step on the attached planes
+TRON_KERNEL(true, k_inc<0>);              // the incremental step: the cells a move touches, the boards that restart, st4, rs4
+TRON_KERNEL(true, k_obs_roll_walk);       // obs_tile steps that leave no entry mask and hand nothing over
+TRON_KERNEL(true, k_obs_roll_slide);      // the same, sliding
+TRON_KERNEL(true, k_reset);               // the masked envs' boards, st4 and rs4
+TRON_KERNEL(true, k_obs_reset);           // the masked envs' planes, re-derived from their boards
+TRON_KERNEL(true, k_obs_attach_marks);    // moves the slide tiles from the planes to the log
+TRON_KERNEL(true, k_set_wd);              // rs4 alone, which no entry mask describes: cleared all the same, the call is rare
+TRON_KERNEL(false, k_obs_roll);           // the roll_resident family keeps the protocol itself: rollout_wave clears the two
+TRON_KERNEL(false, k_obs_roll_tape);      //   flags in front of each of its launches and sets them behind one that was
+TRON_KERNEL(false, k_obs_roll_tape_rec);  //   enqueued
+TRON_KERNEL(false, k_fresh);              // the fresh-board template, once in tron_create
+TRON_KERNEL(false, k_fill_f64);           // the slide rates (P.slide): no plane, no state word
+TRON_KERNEL(false, k_obs_planes);         // reads the planes, writes the caller's float planes
+TRON_KERNEL(false, k_copy16);             // reads boards or planes, writes the caller's copy
+TRON_KERNEL(false, k_obs_to_grid);        // reads the planes, writes the caller's boards
+TRON_KERNEL(false, k_obs_grid_marks);     //   and the slide log's tiles into them
+TRON_KERNEL(false, k_get_state);          // reads st4 / rs4 / slide
+TRON_KERNEL(false, k_encode_codes);       // no handle: the caller's tiles to the caller's codes
+TRON_KERNEL(false, k_pop_up);             // no handle: the caller's codes to the caller's planes
+#undef TRON_KERNEL
+
+// hipFuncSetAttribute acts on the current device only: remember, per kernel, which devices it was prepared on (one bit per
+// device ordinal) instead of a per-process flag.
+template <auto Kernel>
+void allow_big_lds(int device)
 {
+    static uint64_t prepared = 0;
     const uint64_t bit = 1ull << ((unsigned)device & 63u);
     if (prepared & bit) return;
-    if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT) != hipSuccess)
         (void)hipGetLastError();
     prepared |= bit;
+}
+
+// Every kernel launch of this file.  The LDS opt-in of a kernel that takes dynamic LDS, on first use; the invalidation its
+// row of the table asks for; an empty grid (a part without tiles) launches nothing.  h may be null where smem is 0 and the
+// kernel writes no state (the entry points without a handle).
+template <auto Kernel, class... Args>
+int launch(tron_env *h, dim3 grid, dim3 block, size_t smem, hipStream_t st, Args... args)
+{
+    if (smem) allow_big_lds<Kernel>(h->device);
+    if constexpr (writes_state<Kernel>::value) h->entry_masks = h->handed = false;
+    if (grid.x > 0) hipLaunchKernelGGL(Kernel, grid, block, smem, st, args...);
+    return hipGetLastError() == hipSuccess ? TRON_OK : TRON_ERR_LAUNCH;
 }
 
 // tiles [tile0, tile0 + blocks) of the handle's current part (all tiles unless a *_part entry point set one)
@@ -2338,97 +2408,86 @@ inline void part_tiles(const tron_env *h, int &tile0, int &blocks)
     blocks = (int)((long long)ntiles * (h->part0 + 1) / np) - tile0;
 }
 
-template <int FMT, bool DO_STEP, bool ALIGNED>
-int launch_one(tron_env *h, const int8_t *actions, const float *uniforms, uint32_t flags, void *obs, StepOut out,
-               hipStream_t st)
+// Dynamic LDS of the kernels that run obs_tile (k_obs, k_obs_slide, k_obs_roll_walk, k_obs_roll_slide) on tiles of E envs
+size_t obs_tile_smem(const tron_env *h, int E)
 {
-    auto kern = k_tile<FMT, DO_STEP, ALIGNED>;
-    static uint64_t prepared = 0;    // per instantiation, one bit per device
-    allow_big_lds(reinterpret_cast<const void *>(kern), h->device, prepared);
-    int tile0, blocks;
-    part_tiles(h, tile0, blocks);
-    if (blocks > 0)
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK), h->smem, st, h->P, h->E, h->cpe, h->cpe_magic, actions,
-                           uniforms, flags, obs, out, tile0);
-    return launch_status();
+    return ((size_t)E + 1u) * h->cpe * 16u + 4u * (size_t)E * 16u;
 }
 
-template <int FMT, bool ALIGNED>
-int launch_roll_one(tron_env *h, int k_steps, uint32_t flags, void *obs, StepOut out, hipStream_t st)
+// LDS of k_obs_roll (roll_resident): the packed boards, the template, and per game wave the epilogue's store list and the
+// helper's rings (on an even dword: one of padding)
+size_t roll_smem(const tron_env *h, int E, int waves)
 {
-    auto kern = k_tile_roll<FMT, ALIGNED>;
-    static uint64_t prepared = 0;    // per instantiation, one bit per device
-    allow_big_lds(reinterpret_cast<const void *>(kern), h->device, prepared);
-    const int ntiles = (h->P.N + h->E - 1) / h->E;
-    hipLaunchKernelGGL(kern, dim3(ntiles), dim3(BLOCK), h->smem, st, h->P, h->E, h->cpe, h->cpe_magic, flags, obs, out,
-                       k_steps, ntiles);
-    return launch_status();
+    return ((size_t)E * (2u * h->cpe + 1u) + 2u * h->cpe + (size_t)waves * (32u * h->cpe) + 1u + (size_t)waves * ROLL_RING_DWORDS) * 4u;
+}
+
+// f(format, aligned): the observation format and the handle's alignment as compile-time constants
+template <class F>
+int with_fmt(const tron_env *h, int fmt, F f)
+{
+#define TRON_CASE(FMT)                                                                                               \
+    case FMT:                                                                                                        \
+        return h->aligned ? f(std::integral_constant<int, FMT>{}, std::true_type{}) : f(std::integral_constant<int, FMT>{}, std::false_type{});
+    switch (fmt) {
+        TRON_CASE(TRON_OBS_NONE)
+        TRON_CASE(TRON_OBS_CODES_I8)
+        TRON_CASE(TRON_OBS_PLANES3_F32)
+        TRON_CASE(TRON_OBS_PLANES4_F32)
+    default:
+        return TRON_ERR_BAD_ARG;
+    }
+#undef TRON_CASE
+}
+
+// k_tile over the handle's current part
+template <bool DO_STEP>
+int launch_fmt(tron_env *h, int fmt, const int8_t *a, const float *u, uint32_t flags, void *obs, StepOut out, hipStream_t st)
+{
+    int tile0, blocks;
+    part_tiles(h, tile0, blocks);
+    return with_fmt(h, fmt, [&](auto F, auto A) {
+        return launch<k_tile<F(), DO_STEP, A()>>(h, dim3(blocks), dim3(BLOCK), h->smem, st, h->P, h->E, h->cpe, h->cpe_magic, a, u, flags,
+                                                 obs, out, tile0);
+    });
 }
 
 int launch_roll_fmt(tron_env *h, int fmt, int k_steps, uint32_t flags, void *obs, StepOut out, hipStream_t st)
 {
-#define TRON_CASE(F)                                                                        \
-    case F:                                                                                 \
-        return h->aligned ? launch_roll_one<F, true>(h, k_steps, flags, obs, out, st)       \
-                          : launch_roll_one<F, false>(h, k_steps, flags, obs, out, st);
-    switch (fmt) {
-        TRON_CASE(TRON_OBS_NONE)
-        TRON_CASE(TRON_OBS_CODES_I8)
-        TRON_CASE(TRON_OBS_PLANES3_F32)
-        TRON_CASE(TRON_OBS_PLANES4_F32)
-    default:
-        return TRON_ERR_BAD_ARG;
-    }
-#undef TRON_CASE
+    const int ntiles = (h->P.N + h->E - 1) / h->E;
+    return with_fmt(h, fmt, [&](auto F, auto A) {
+        return launch<k_tile_roll<F(), A()>>(h, dim3(ntiles), dim3(BLOCK), h->smem, st, h->P, h->E, h->cpe, h->cpe_magic, flags, obs, out,
+                                             k_steps, ntiles);
+    });
 }
 
-template <bool DO_STEP>
-int launch_fmt(tron_env *h, int fmt, const int8_t *a, const float *u, uint32_t flags, void *obs, StepOut out,
-               hipStream_t st)
-{
-#define TRON_CASE(F)                                                                          \
-    case F:                                                                                   \
-        return h->aligned ? launch_one<F, DO_STEP, true>(h, a, u, flags, obs, out, st)        \
-                          : launch_one<F, DO_STEP, false>(h, a, u, flags, obs, out, st);
-    switch (fmt) {
-        TRON_CASE(TRON_OBS_NONE)
-        TRON_CASE(TRON_OBS_CODES_I8)
-        TRON_CASE(TRON_OBS_PLANES3_F32)
-        TRON_CASE(TRON_OBS_PLANES4_F32)
-    default:
-        return TRON_ERR_BAD_ARG;
-    }
-#undef TRON_CASE
-}
-
-template <bool DO_STEP>
+// one step on the attached planes, over the handle's current part
 int launch_obs(tron_env *h, const int8_t *actions, uint32_t flags, StepOut out, hipStream_t st, const float *uniforms = nullptr)
 {
     int tile0, blocks;
     part_tiles(h, tile0, blocks);
-    const size_t smem = ((size_t)h->E + 1u) * h->cpe * 16u + 4u * (size_t)h->E * 16u;
-    if (DO_STEP && h->P.mode != TRON_MODE_NONE) {                       // the sliding modes' kernel
-        static uint64_t prepared_s = 0;
-        allow_big_lds(reinterpret_cast<const void *>(k_obs_slide), h->device, prepared_s);
-        if (blocks > 0)
-            hipLaunchKernelGGL(k_obs_slide, dim3(blocks), dim3(BLOCK), smem, st, h->P, h->E, h->cpe, h->cpe_magic, actions, uniforms, flags,
-                               out, tile0);
-        return launch_status();
-    }
-    auto kern = k_obs<DO_STEP>;
-    static uint64_t prepared = 0;    // per instantiation, one bit per device
-    allow_big_lds(reinterpret_cast<const void *>(kern), h->device, prepared);
-    if (blocks > 0)
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK), smem, st, h->P, h->E, h->cpe, h->cpe_magic, actions, flags, out,
-                           tile0);
-    return launch_status();
+    const size_t smem = obs_tile_smem(h, h->E);
+    if (h->P.mode != TRON_MODE_NONE)                                    // the sliding modes' kernel
+        return launch<k_obs_slide>(h, dim3(blocks), dim3(BLOCK), smem, st, h->P, h->E, h->cpe, h->cpe_magic, actions, uniforms, flags,
+                                   out, tile0);
+    return launch<k_obs<true>>(h, dim3(blocks), dim3(BLOCK), smem, st, h->P, h->E, h->cpe, h->cpe_magic, actions, flags, out, tile0);
+}
+
+// one launch of a kernel of the roll_resident family (k_obs_roll takes no tape)
+template <auto Kernel>
+int launch_roll_resident(tron_env *h, int grid, int waves, size_t smem, hipStream_t st, int E, int epw, uint32_t flags, StepOut out,
+                         int steps, const int8_t *tape)
+{
+    if constexpr (std::is_same_v<decltype(Kernel), decltype(&k_obs_roll)>)
+        return launch<Kernel>(h, dim3(grid), dim3(2 * waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, out, steps, h->emask, h->hand);
+    else
+        return launch<Kernel>(h, dim3(grid), dim3(2 * waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, out, steps, tape, h->emask,
+                              h->hand);
 }
 
 inline int obs_planes(tron_env *h, int fmt, void *obs, hipStream_t st)
 {
     const int ch = (fmt == TRON_OBS_PLANES3_F32) ? 3 : 4;
-    hipLaunchKernelGGL(k_obs_planes, dim3(4096), dim3(256), 0, st, h->P, ch, reinterpret_cast<float *>(obs));
-    return launch_status();
+    return launch<k_obs_planes>(h, dim3(4096), dim3(256), 0, st, h->P, ch, reinterpret_cast<float *>(obs));
 }
 
 inline bool bad_handle(tron_handle h)
@@ -2508,10 +2567,8 @@ int tron_create(int32_t n_envs, int32_t W, int32_t mode, int32_t fair, uint32_t 
     // tile size: keep the LDS tile near 24 KB so ~6 workgroups share a CU
     int E = (int)((24u * 1024u) / (h->cpe * 16u));
     E = E >= 64 ? 64 : E >= 32 ? 32 : E >= 16 ? 16 : E >= 8 ? 8 : 4;
-    if (const char *s = getenv("TRON_TILE_ENVS")) {
-        const int v = atoi(s);
-        if (v >= 1 && v <= 64 && ((size_t)v + 1u) * h->cpe * 16u + 8192u <= 160u * 1024u) E = v;
-    }
+    const int v = overrides().tile_envs;
+    if (v >= 1 && v <= 64 && ((size_t)v + 1u) * h->cpe * 16u + 8192u <= LDS_LIMIT) E = v;
     h->E = E;
     h->smem = ((size_t)E + 1u) * h->cpe * 16u + 3u * (size_t)E * 16u + (size_t)E * 4u + 4u * (((size_t)E * h->cpe + 31u) / 32u + 1u) + 16u;
 
@@ -2540,10 +2597,10 @@ int tron_create(int32_t n_envs, int32_t W, int32_t mode, int32_t fair, uint32_t 
     h->emask = reinterpret_cast<unsigned long long *>(blob + o_emask);
     h->hand = reinterpret_cast<uint32_t *>(blob + o_hand);
     if (hipMemsetAsync(blob, 0, total, nullptr) != hipSuccess) { (void)hipGetLastError(); }
-    hipLaunchKernelGGL(k_fresh, dim3((P.G + 255) / 256), dim3(256), 0, nullptr, const_cast<int8_t *>(P.fresh), P.S);
-    hipLaunchKernelGGL(k_fill_f64, dim3((n_envs + 255) / 256), dim3(256), 0, nullptr, P.slide, 0.15,
-                       (const double *)nullptr, n_envs);                                     // config.py:31 slide
-    if (launch_status() != TRON_OK || hipStreamSynchronize(nullptr) != hipSuccess) {
+    if (launch<k_fresh>(h, dim3((P.G + 255) / 256), dim3(256), 0, nullptr, const_cast<int8_t *>(P.fresh), P.S) != TRON_OK ||
+        launch<k_fill_f64>(h, dim3((n_envs + 255) / 256), dim3(256), 0, nullptr, P.slide, 0.15, (const double *)nullptr,
+                           n_envs) != TRON_OK ||                                             // config.py:31 slide
+        hipStreamSynchronize(nullptr) != hipSuccess) {
         (void)hipGetLastError();
         (void)hipFree(blob);
         delete h;
@@ -2584,30 +2641,24 @@ int tron_set_reward(tron_handle h, float step, float win, float lose, float draw
 int tron_set_slide(tron_handle h, double slide, const double *slide_dev, void *stream)
 {
     if (bad_handle(h)) return h ? TRON_ERR_NO_DEVICE : TRON_ERR_BAD_ARG;
-    hipLaunchKernelGGL(k_fill_f64, dim3((h->P.N + 255) / 256), dim3(256), 0, S_(stream), h->P.slide, slide, slide_dev,
-                       h->P.N);
-    return launch_status();
+    return launch<k_fill_f64>(h, dim3((h->P.N + 255) / 256), dim3(256), 0, S_(stream), h->P.slide, slide, slide_dev, h->P.N);
 }
 
 int tron_set_weight_degree(tron_handle h, const int16_t *weight, const int16_t *degree, void *stream)
 {
     if (bad_handle(h)) return h ? TRON_ERR_NO_DEVICE : TRON_ERR_BAD_ARG;
-    planes_written(h);              // (rs4 only, which no entry mask describes: cleared all the same, the call is rare)
-    hipLaunchKernelGGL(k_set_wd, dim3((h->P.N + 255) / 256), dim3(256), 0, S_(stream), h->P, weight, degree);
-    return launch_status();
+    return launch<k_set_wd>(h, dim3((h->P.N + 255) / 256), dim3(256), 0, S_(stream), h->P, weight, degree);
 }
 
 int tron_reset(tron_handle h, const int8_t *env_mask, const int8_t *start_pos, const int16_t *weight,
                const int16_t *degree, void *stream)
 {
     if (bad_handle(h)) return h ? TRON_ERR_NO_DEVICE : TRON_ERR_BAD_ARG;
-    planes_written(h);
     const int per = BLOCK / 64;
-    hipLaunchKernelGGL(k_reset, dim3((h->P.N + per - 1) / per), dim3(BLOCK), 0, S_(stream), h->P, env_mask, start_pos,
-                       weight, degree);
-    if (h->P.obs_state)     // observation-is-state: the masked envs' planes are re-derived from their fresh boards
-        hipLaunchKernelGGL(k_obs_reset, dim3((h->P.N + per - 1) / per), dim3(BLOCK), 0, S_(stream), h->P, env_mask);
-    return launch_status();
+    int rc = launch<k_reset>(h, dim3((h->P.N + per - 1) / per), dim3(BLOCK), 0, S_(stream), h->P, env_mask, start_pos, weight, degree);
+    if (rc == TRON_OK && h->P.obs_state)     // observation-is-state: the masked envs' planes are re-derived from their fresh boards
+        rc = launch<k_obs_reset>(h, dim3((h->P.N + per - 1) / per), dim3(BLOCK), 0, S_(stream), h->P, env_mask);
+    return rc;
 }
 
 int tron_attach_obs_state(tron_handle h, int8_t *obs_codes, void *stream)
@@ -2616,14 +2667,13 @@ int tron_attach_obs_state(tron_handle h, int8_t *obs_codes, void *stream)
     if (!obs_codes || (reinterpret_cast<uintptr_t>(obs_codes) & 15u)) return TRON_ERR_BAD_ARG;
     if (!h->aligned || h->P.G >= 0x3FFF) return TRON_ERR_UNSUPPORTED;                 // (cell + 1 travels in 14 bits: restart word, slide marks)
     if (h->P.obs_state) return TRON_ERR_BAD_ARG;                                      // already attached
-    planes_written(h);
+    h->entry_masks = h->handed = false;   // the planes are another buffer from here on, whatever the launches below do
     h->P.obs_state = obs_codes;
     const int per = BLOCK / 64;     // derive the planes from the boards as they are now
-    hipLaunchKernelGGL(k_obs_reset, dim3((h->P.N + per - 1) / per), dim3(BLOCK), 0, S_(stream), h->P,
-                       (const int8_t *)nullptr);
-    if (h->P.mode != TRON_MODE_NONE)  // slide tiles are not codable (Map.color shows them as bodies): they go to the log (lane_move_codes_slide)
-        hipLaunchKernelGGL(k_obs_attach_marks, dim3((h->P.N + 255) / 256), dim3(256), 0, S_(stream), h->P);
-    return launch_status();
+    int rc = launch<k_obs_reset>(h, dim3((h->P.N + per - 1) / per), dim3(BLOCK), 0, S_(stream), h->P, (const int8_t *)nullptr);
+    if (rc == TRON_OK && h->P.mode != TRON_MODE_NONE)  // slide tiles are not codable (Map.color shows them as bodies): they go to the log (lane_move_codes_slide)
+        rc = launch<k_obs_attach_marks>(h, dim3((h->P.N + 255) / 256), dim3(256), 0, S_(stream), h->P);
+    return rc;
 }
 
 int tron_step_encode(tron_handle h, const int8_t *actions, const float *uniforms, uint32_t flags, int32_t obs_fmt,
@@ -2633,20 +2683,14 @@ int tron_step_encode(tron_handle h, const int8_t *actions, const float *uniforms
     if ((obs_fmt != TRON_OBS_NONE) != (obs != nullptr)) return TRON_ERR_BAD_ARG;
     if (flags & ~(TRON_STEP_AUTORESET | TRON_STEP_INCREMENTAL | TRON_STEP_NONREVERSING)) return TRON_ERR_BAD_ARG;
     if ((flags & TRON_STEP_INCREMENTAL) && (!h->P.obs_state || h->P.mode != TRON_MODE_NONE)) return TRON_ERR_UNSUPPORTED;
-    planes_written(h);              // tron_step, the part steps and the incremental path (k_inc) all come through here
     StepOut out{out_done, out_winner, out_reward, nullptr};
     if (h->P.obs_state) {
         if (obs_fmt == TRON_OBS_CODES_I8 && obs != h->P.obs_state) return TRON_ERR_BAD_ARG;   // the attached buffer is the output
         if (obs_fmt < TRON_OBS_NONE || obs_fmt > TRON_OBS_PLANES4_F32) return TRON_ERR_BAD_ARG;
-        int rc;
-        if (flags & TRON_STEP_INCREMENTAL) {
-            hipLaunchKernelGGL((k_inc<0>), dim3((h->P.N + WAVE - 1) / WAVE), dim3(BLOCK), 0, S_(stream), h->P, h->cpe,
-                               actions, flags, out);
-            rc = launch_status();
-        } else {
-            rc = launch_obs<true>(h, actions, flags, out, S_(stream), uniforms);
-        }
-        if (rc != TRON_OK || obs_fmt == TRON_OBS_NONE || obs_fmt == TRON_OBS_CODES_I8) return rc;
+        const int rc = (flags & TRON_STEP_INCREMENTAL)
+                           ? launch<k_inc<0>>(h, dim3((h->P.N + WAVE - 1) / WAVE), dim3(BLOCK), 0, S_(stream), h->P, h->cpe, actions, flags, out)
+                           : launch_obs(h, actions, flags, out, S_(stream), uniforms);
+        if (rc != TRON_OK || !is_f32_planes(obs_fmt)) return rc;
         return obs_planes(h, obs_fmt, obs, S_(stream));
     }
     return launch_fmt<true>(h, obs_fmt, actions, uniforms, flags, obs, out, S_(stream));
@@ -2677,7 +2721,7 @@ int tron_step_encode_part(tron_handle h, int32_t part, int32_t nparts, const int
     if (bad_handle(h)) return h ? TRON_ERR_NO_DEVICE : TRON_ERR_BAD_ARG;
     if (nparts < 1 || part < 0 || part >= nparts) return TRON_ERR_BAD_ARG;
     if (flags & TRON_STEP_INCREMENTAL) return TRON_ERR_UNSUPPORTED;
-    if (h->P.obs_state && (obs_fmt == TRON_OBS_PLANES3_F32 || obs_fmt == TRON_OBS_PLANES4_F32)) return TRON_ERR_UNSUPPORTED;
+    if (h->P.obs_state && is_f32_planes(obs_fmt)) return TRON_ERR_UNSUPPORTED;
     h->part0 = part;
     h->nparts = nparts;
     const int rc = tron_step_encode(h, actions, uniforms, flags, obs_fmt, obs, out_done, out_winner, out_reward, stream);
@@ -2696,12 +2740,10 @@ int tron_encode(tron_handle h, int32_t obs_fmt, void *obs, void *stream)
             if (obs == h->P.obs_state) return TRON_OK;            // the attached planes are always current
             const size_t nbytes = (size_t)h->P.N * 2u * h->P.G;
             if (reinterpret_cast<uintptr_t>(obs) & 15u) return TRON_ERR_BAD_ARG;
-            hipLaunchKernelGGL(k_copy16, dim3(2048), dim3(256), 0, S_(stream), reinterpret_cast<const uint4 *>(h->P.obs_state),
-                               reinterpret_cast<uint4 *>(obs), nbytes / 16, h->P.obs_state, reinterpret_cast<int8_t *>(obs),
-                               nbytes);
-            return launch_status();
+            return launch<k_copy16>(h, dim3(2048), dim3(256), 0, S_(stream), reinterpret_cast<const uint4 *>(h->P.obs_state),
+                                    reinterpret_cast<uint4 *>(obs), nbytes / 16, h->P.obs_state, reinterpret_cast<int8_t *>(obs), nbytes);
         }
-        if (obs_fmt != TRON_OBS_PLANES3_F32 && obs_fmt != TRON_OBS_PLANES4_F32) return TRON_ERR_BAD_ARG;
+        if (!is_f32_planes(obs_fmt)) return TRON_ERR_BAD_ARG;
         return obs_planes(h, obs_fmt, obs, S_(stream));
     }
     return launch_fmt<false>(h, obs_fmt, nullptr, nullptr, 0u, obs, out, S_(stream));
@@ -2712,27 +2754,25 @@ int tron_get_grid(tron_handle h, int8_t *grid_out, void *stream)
     if (bad_handle(h)) return h ? TRON_ERR_NO_DEVICE : TRON_ERR_BAD_ARG;
     if (!grid_out) return TRON_ERR_BAD_ARG;
     if (h->P.obs_state) {
-        hipLaunchKernelGGL(k_obs_to_grid, dim3(2048), dim3(256), 0, S_(stream), h->P, grid_out);
-        if (h->P.mode != TRON_MODE_NONE)
-            hipLaunchKernelGGL(k_obs_grid_marks, dim3((h->P.N + 255) / 256), dim3(256), 0, S_(stream), h->P, grid_out);
-        return launch_status();
+        int rc = launch<k_obs_to_grid>(h, dim3(2048), dim3(256), 0, S_(stream), h->P, grid_out);
+        if (rc == TRON_OK && h->P.mode != TRON_MODE_NONE)
+            rc = launch<k_obs_grid_marks>(h, dim3((h->P.N + 255) / 256), dim3(256), 0, S_(stream), h->P, grid_out);
+        return rc;
     }
     const size_t nbytes = (size_t)h->P.N * h->P.G;
     const bool aligned = (reinterpret_cast<uintptr_t>(grid_out) & 15u) == 0;
     const size_t n16 = aligned ? nbytes / 16 : 0;
     const int blocks = (int)((n16 / 256 < 2048 ? n16 / 256 : 2048) + 1);
-    hipLaunchKernelGGL(k_copy16, dim3(blocks), dim3(256), 0, S_(stream), reinterpret_cast<const uint4 *>(h->P.grid),
-                       reinterpret_cast<uint4 *>(grid_out), n16, h->P.grid, grid_out, nbytes);
-    return launch_status();
+    return launch<k_copy16>(h, dim3(blocks), dim3(256), 0, S_(stream), reinterpret_cast<const uint4 *>(h->P.grid),
+                            reinterpret_cast<uint4 *>(grid_out), n16, h->P.grid, grid_out, nbytes);
 }
 
 int tron_get_state(tron_handle h, int8_t *pos, int8_t *alive, int8_t *dir, int8_t *done, int8_t *winner,
                    int16_t *weight, int16_t *degree, double *slide, uint32_t *counters, void *stream)
 {
     if (bad_handle(h)) return h ? TRON_ERR_NO_DEVICE : TRON_ERR_BAD_ARG;
-    hipLaunchKernelGGL(k_get_state, dim3((h->P.N + 255) / 256), dim3(256), 0, S_(stream), h->P, pos, alive, dir, done,
-                       winner, weight, degree, slide, counters);
-    return launch_status();
+    return launch<k_get_state>(h, dim3((h->P.N + 255) / 256), dim3(256), 0, S_(stream), h->P, pos, alive, dir, done, winner, weight,
+                               degree, slide, counters);
 }
 
 namespace {
@@ -2740,7 +2780,6 @@ namespace {
 // k_steps steps of the observation-is-state kernel as persistent launches of at most TRON_ROLLOUT_CHUNK steps (k_obs_roll and
 // its tape forms: ROLL_LAUNCH_CAP, above rollout_wave), one tile per
 // workgroup: with more workgroups than the chip holds at once the late ones start as the early ones finish their steps.
-// TRON_ROLL_E / TRON_ROLL_GRID / TRON_ROLL_CHUNK override tile size, grid and steps per launch.
 // Tile size for the kernels that run obs_tile every step (the sliding modes; k_obs_roll_walk has the same code and occupancy
 // and is what is asked here).  The chip holds `slots` workgroups at once (occupancy x CUs), so the launch runs in
 // ceil(ntiles / slots) rounds and the last one should be full.  Picks the E in [3/4 E0, E0] with the fullest last round
@@ -2750,12 +2789,12 @@ int roll_tile_envs(const tron_env *h)
     const int E0 = h->E;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) { (void)hipGetLastError(); return E0; }
+    allow_big_lds<k_obs_roll_walk>(h->device);                          // (the query below is made in front of its first launch)
     int best = E0;
     double best_fill = -1.0;
     for (int E = E0; E >= (3 * E0 + 3) / 4 && E >= 1; --E) {
-        const size_t smem = ((size_t)E + 1u) * h->cpe * 16u + 4u * (size_t)E * 16u;
         int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_obs_roll_walk, BLOCK, smem) != hipSuccess || per_cu < 1) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_obs_roll_walk, BLOCK, obs_tile_smem(h, E)) != hipSuccess || per_cu < 1) {
             (void)hipGetLastError();
             continue;
         }
@@ -2789,13 +2828,6 @@ int roll_waves(tron_env *h)
     return h->roll_waves;
 }
 
-// LDS of k_obs_roll (roll_resident): the packed boards, the template, and per game wave the epilogue's store list and the
-// helper's rings (on an even dword: one of padding)
-size_t roll_smem(const tron_env *h, int E, int waves)
-{
-    return ((size_t)E * (2u * h->cpe + 1u) + 2u * h->cpe + (size_t)waves * (32u * h->cpe) + 1u + (size_t)waves * ROLL_RING_DWORDS) * 4u;
-}
-
 // Steps per launch of the roll_resident family (k_obs_roll, k_obs_roll_tape, k_obs_roll_tape_rec): the whole call, up to this
 // many.  A launch pays its prologue, its epilogue and the ramp and tail of the grid once, about 20 us at 65 536 x 24x24
 // where a step is 0.8 us: a quarter of a 64-step launch (TRON_ROLLOUT_CHUNK, chosen when a step was 20 us and still the
@@ -2809,6 +2841,40 @@ size_t roll_smem(const tron_env *h, int E, int waves)
 constexpr int ROLL_LAUNCH_CAP = 1024;
 static_assert(ROLL_LAUNCH_CAP % 128 == 0, "whole tally periods and whole blocks: the launches of a long call are all alike");
 
+// out with its record tapes `envs` entries on (a step is N of them): the rows of a later step; a null tape stays null
+inline StepOut rows_from(StepOut out, size_t envs)
+{
+    return StepOut{out.done ? out.done + envs : nullptr, out.winner ? out.winner + envs : nullptr,
+                   out.reward ? out.reward + 2u * envs : nullptr, out.totals};
+}
+
+// TRON_ROLL_REPORT: the launch shape and its occupancy on stderr, once per process
+void report_roll_shape(const tron_env *h, int E, int waves, int epw, size_t smem, int grid)
+{
+    static bool reported = false;
+    if (reported) return;
+    reported = true;
+    allow_big_lds<k_obs_roll>(h->device);
+    int per_cu = 0;
+    hipDeviceProp_t prop;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_obs_roll, 2 * waves * WAVE, smem) == hipSuccess &&
+        hipGetDeviceProperties(&prop, h->device) == hipSuccess)
+        fprintf(stderr, "k_obs_roll: %d envs per workgroup, %d game waves of %d envs and as many helper waves, %zu B of LDS, grid %d; %d workgroups per CU x %d CUs = %d resident\n",
+                E, waves, epw, smem, grid, per_cu, prop.multiProcessorCount, per_cu * prop.multiProcessorCount);
+    (void)hipGetLastError();
+}
+
+// TRON_ROLL_REPORT: the entry a launch takes, whenever it is not the last one reported
+void report_roll_entry(uint32_t flags, int steps, bool tape)
+{
+    static int reported = -1;
+    const int entry = (flags & ROLL_ENTRY_MASKED ? 1 : 0) | (flags & ROLL_ENTRY_HANDED ? 2 : 0);
+    if (entry != reported)
+        fprintf(stderr, "k_obs_roll: a launch of %d steps enters by %s, its first block's starts%s %s\n", steps,
+                entry & 1 ? "the entry masks" : "whole planes", tape ? "" : " and actions", entry & 2 ? "handed over" : "drawn");
+    reported = entry;
+}
+
 // tape: null for k_obs_roll's own draws; else the caller's int8[k_steps][N][2], and every launch gets it advanced to its
 // own first step (k_obs_roll_tape: same grid, same workgroup, same LDS).  A tape call that asks for records (any of
 // out.done / out.winner / out.reward) runs k_obs_roll_tape_rec, and its launches get the record tapes advanced by the same rows.
@@ -2821,60 +2887,27 @@ int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags_in, StepOut out, h
     const int epw = (E + waves - 1) / waves;
     const int grid = (h->P.N + E - 1) / E;
     const size_t smem = roll_smem(h, E, waves);
-    if (smem > 160u * 1024u) return TRON_ERR_BAD_ARG;
-    static uint64_t prepared = 0;
-    allow_big_lds(reinterpret_cast<const void *>(k_obs_roll), h->device, prepared);
-    static uint64_t prepared_t = 0;
+    if (smem > LDS_LIMIT) return TRON_ERR_BAD_ARG;
     const bool rec = tape && (out.done || out.winner || out.reward);
-    if (tape && !rec) allow_big_lds(reinterpret_cast<const void *>(k_obs_roll_tape), h->device, prepared_t);
-    static uint64_t prepared_r = 0;
-    if (rec) allow_big_lds(reinterpret_cast<const void *>(k_obs_roll_tape_rec), h->device, prepared_r);
-    // TRON_ROLL_FULL_ENTRY: every launch reads whole planes, as if no entry mask were valid (A/B runs, the tests' twin)
-    static const bool full_entry = getenv("TRON_ROLL_FULL_ENTRY") != nullptr;
-    // TRON_ROLL_NO_HANDOFF: every launch draws its own first block, as if nothing had been handed over (A/B runs, the tests' twin)
-    static const bool no_handoff = getenv("TRON_ROLL_NO_HANDOFF") != nullptr;
-    static bool report = getenv("TRON_ROLL_REPORT") != nullptr;         // the launch shape and its occupancy on stderr, once per process
-    static const bool report_entry = report;                            // and the entry a launch took, whenever it is not the last one reported
-    static int reported_entry = -1;
-    if (report) {
-        report = false;
-        int per_cu = 0;
-        hipDeviceProp_t prop;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_obs_roll, 2 * waves * WAVE, smem) == hipSuccess &&
-            hipGetDeviceProperties(&prop, h->device) == hipSuccess)
-            fprintf(stderr, "k_obs_roll: %d envs per workgroup, %d game waves of %d envs and as many helper waves, %zu B of LDS, grid %d; %d workgroups per CU x %d CUs = %d resident\n",
-                    E, waves, epw, smem, grid, per_cu, prop.multiProcessorCount, per_cu * prop.multiProcessorCount);
-        (void)hipGetLastError();
-    }
-    for (int left = k_steps; left > 0; left -= chunk) {
+    const auto launch_it = rec ? &launch_roll_resident<k_obs_roll_tape_rec> : tape ? &launch_roll_resident<k_obs_roll_tape>
+                                                                                   : &launch_roll_resident<k_obs_roll>;
+    const Overrides &o = overrides();
+    if (o.report) report_roll_shape(h, E, waves, epw, smem, grid);
+    const bool autoreset = (flags_in & TRON_STEP_AUTORESET) != 0u;
+    for (int done = 0; done < k_steps; done += chunk) {
         // The launch covers all envs (grid x E >= N) and writes every env's entry mask; the one behind it on the stream may
         // enter by them.  Nothing is assumed of a launch that failed.
         // It hands its helper's rings over as well (autoreset alone); the one behind it takes them if it would draw the same
         // words: same seed, stream, fair and W.
-        const bool autoreset = (flags_in & TRON_STEP_AUTORESET) != 0u;
-        const bool take = h->handed && autoreset && !no_handoff && h->hand_seed == h->P.seed && h->hand_stream == h->P.stream &&
+        const int steps = k_steps - done < chunk ? k_steps - done : chunk;
+        const bool take = h->handed && autoreset && !o.no_handoff && h->hand_seed == h->P.seed && h->hand_stream == h->P.stream &&
                           h->hand_fair == h->P.fair && h->hand_W == h->P.W;
-        const uint32_t flags = flags_in | (h->entry_masks && !full_entry ? ROLL_ENTRY_MASKED : 0u) | (take ? ROLL_ENTRY_HANDED : 0u);
+        const uint32_t flags = flags_in | (h->entry_masks && !o.full_entry ? ROLL_ENTRY_MASKED : 0u) | (take ? ROLL_ENTRY_HANDED : 0u);
         h->entry_masks = h->handed = false;
-        if (report_entry) {
-            const int entry = (flags & ROLL_ENTRY_MASKED ? 1 : 0) | (take ? 2 : 0);
-            if (entry != reported_entry)
-                fprintf(stderr, "k_obs_roll: a launch of %d steps enters by %s, its first block's starts%s %s\n", left < chunk ? left : chunk,
-                        entry & 1 ? "the entry masks" : "whole planes", tape ? "" : " and actions", entry & 2 ? "handed over" : "drawn");
-            reported_entry = entry;
-        }
-        if (rec) {
-            const size_t at = (size_t)(k_steps - left) * (size_t)h->P.N;   // the launch's first row, in envs
-            const StepOut rows{out.done ? out.done + at : nullptr, out.winner ? out.winner + at : nullptr,
-                               out.reward ? out.reward + 2u * at : nullptr, out.totals};
-            hipLaunchKernelGGL(k_obs_roll_tape_rec, dim3(grid), dim3(2 * waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, rows,
-                               left < chunk ? left : chunk, tape + 2u * at, h->emask, h->hand);
-        } else if (tape)
-            hipLaunchKernelGGL(k_obs_roll_tape, dim3(grid), dim3(2 * waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, out,
-                               left < chunk ? left : chunk, tape + (size_t)(k_steps - left) * 2u * (size_t)h->P.N, h->emask, h->hand);
-        else
-            hipLaunchKernelGGL(k_obs_roll, dim3(grid), dim3(2 * waves * WAVE), smem, st, h->P, E, epw, h->cpe, flags, out, left < chunk ? left : chunk, h->emask, h->hand);
-        if (launch_status() != TRON_OK) return TRON_ERR_LAUNCH;
+        if (o.report) report_roll_entry(flags, steps, tape != nullptr);
+        const size_t at = (size_t)done * (size_t)h->P.N;              // the launch's first row, in envs (record tapes: behind a tape alone)
+        if (launch_it(h, grid, waves, smem, st, E, epw, flags, rows_from(out, at), steps, tape ? tape + 2u * at : nullptr) != TRON_OK)
+            return TRON_ERR_LAUNCH;
         h->entry_masks = true;
         h->handed = autoreset;
         h->hand_seed = h->P.seed; h->hand_stream = h->P.stream; h->hand_fair = h->P.fair; h->hand_W = h->P.W;
@@ -2886,76 +2919,56 @@ int rollout_wave(tron_env *h, int32_t k_steps, uint32_t flags_in, StepOut out, h
 // caller then steps per launch.
 int rollout_persistent(tron_env *h, int32_t k_steps, uint32_t flags, StepOut out, hipStream_t st, const int8_t *tape = nullptr)
 {
+    const Overrides &o = overrides();
     // chunk: steps per launch of the kernels that run obs_tile every step (k_obs_roll_walk, k_obs_roll_slide);
     // wave_chunk: of the roll_resident family (ROLL_LAUNCH_CAP).  TRON_ROLL_CHUNK sets both.
-    static int env_e = 0, env_grid = 0, env_waves = 0, chunk = TRON_ROLLOUT_CHUNK, wave_chunk = ROLL_LAUNCH_CAP;
-    static bool probed = false;
-    if (!probed) {
-        if (const char *v = getenv("TRON_ROLL_E")) env_e = atoi(v);
-        if (const char *v = getenv("TRON_ROLL_WAVES")) env_waves = atoi(v);
-        if (const char *v = getenv("TRON_ROLL_GRID")) env_grid = atoi(v);
-        if (const char *v = getenv("TRON_ROLL_CHUNK"))
-            if (atoi(v) > 0) chunk = wave_chunk = atoi(v);
-        probed = true;
-    }
+    const int chunk = o.roll_chunk > 0 ? o.roll_chunk : TRON_ROLLOUT_CHUNK, wave_chunk = o.roll_chunk > 0 ? o.roll_chunk : ROLL_LAUNCH_CAP;
     const bool sliding = h->P.mode != TRON_MODE_NONE;
     if (!sliding && h->cpe <= 64u) {
         // (mode None ONLY: k_obs_roll leaves rs4.envp / rs4.nenvp alone until its epilogue, which no sliding step could bear)
         // TRON_ROLL_E stays envs per workgroup, TRON_ROLL_WAVES its waves; a TRON_ROLL_GRID below the workgroup count asks for
         // the walking kernel below
-        int waves = env_waves > 0 ? env_waves : roll_waves(h);
+        int waves = o.roll_waves > 0 ? o.roll_waves : roll_waves(h);
         // 30x30 (64 chunks): four waves' boards and lists (165 376 B) are past the 160 KB of a CU, three fit (124 160 B).  TRON_ROLL_WAVES is clamped
         // the same way; a TRON_ROLL_E that needs more waves than fit (256 envs at 30x30) is TRON_ERR_BAD_ARG in rollout_wave.
-        while (env_e <= 0 && waves > 1 && roll_smem(h, waves * ROLL_EPW, waves) > 160u * 1024u) --waves;
-        const int E = env_e > 0 ? env_e : waves * ROLL_EPW;
-        if (!(env_grid > 0 && env_grid < (h->P.N + E - 1) / E)) return rollout_wave(h, k_steps, flags, out, st, E, waves, wave_chunk, tape);
+        while (o.roll_e <= 0 && waves > 1 && roll_smem(h, waves * ROLL_EPW, waves) > LDS_LIMIT) --waves;
+        const int E = o.roll_e > 0 ? o.roll_e : waves * ROLL_EPW;
+        if (!(o.roll_grid > 0 && o.roll_grid < (h->P.N + E - 1) / E)) return rollout_wave(h, k_steps, flags, out, st, E, waves, wave_chunk, tape);
     }
     if (tape) return TRON_ERR_UNSUPPORTED;
-    planes_written(h);              // k_obs_roll_walk, k_obs_roll_slide
-    static uint64_t prepared_w = 0;
-    allow_big_lds(reinterpret_cast<const void *>(k_obs_roll_walk), h->device, prepared_w);
     if (!h->roll_E) h->roll_E = roll_tile_envs(h);
     // obs_tile every step (the sliding modes; mode None on boards of more than 64 chunks or with TRON_ROLL_GRID: k_obs_roll_walk).
     // The sliding modes: the per-step tile for a call that fits ONE launch and for the resident variant, else the tile with the
     // fullest last round — measured at 65 536 x 24x24.  Mode None: the per-step tile.
-    const int E = env_e > 0 ? env_e : !sliding ? h->E : ((flags & TRON_ROLLOUT_RESIDENT) || k_steps <= chunk) ? h->E : h->roll_E;
+    const int E = o.roll_e > 0 ? o.roll_e : !sliding ? h->E : ((flags & TRON_ROLLOUT_RESIDENT) || k_steps <= chunk) ? h->E : h->roll_E;
     const int ntiles = (h->P.N + E - 1) / E;
-    const int grid = (env_grid > 0 && env_grid < ntiles) ? env_grid : ntiles;
-    const size_t smem = ((size_t)E + 1u) * h->cpe * 16u + 4u * (size_t)E * 16u;
-    if (smem > 160u * 1024u) return TRON_ERR_BAD_ARG;
-    if (sliding) {
-        static uint64_t prepared_s = 0;
-        allow_big_lds(reinterpret_cast<const void *>(k_obs_roll_slide), h->device, prepared_s);
-    }
+    const int grid = (o.roll_grid > 0 && o.roll_grid < ntiles) ? o.roll_grid : ntiles;
+    const size_t smem = obs_tile_smem(h, E);
+    if (smem > LDS_LIMIT) return TRON_ERR_BAD_ARG;
     for (int left = k_steps; left > 0; left -= chunk) {
-        if (sliding)
-            hipLaunchKernelGGL(k_obs_roll_slide, dim3(grid), dim3(BLOCK), smem, st, h->P, E, h->cpe, h->cpe_magic, flags, out,
-                               left < chunk ? left : chunk, ntiles);
-        else
-            hipLaunchKernelGGL(k_obs_roll_walk, dim3(grid), dim3(BLOCK), smem, st, h->P, E, h->cpe, h->cpe_magic, flags, out,
-                               left < chunk ? left : chunk, ntiles);
-        if (launch_status() != TRON_OK) return TRON_ERR_LAUNCH;
+        const int steps = left < chunk ? left : chunk;
+        const int rc = sliding ? launch<k_obs_roll_slide>(h, dim3(grid), dim3(BLOCK), smem, st, h->P, E, h->cpe, h->cpe_magic, flags, out, steps, ntiles)
+                               : launch<k_obs_roll_walk>(h, dim3(grid), dim3(BLOCK), smem, st, h->P, E, h->cpe, h->cpe_magic, flags, out, steps, ntiles);
+        if (rc != TRON_OK) return TRON_ERR_LAUNCH;
     }
     return TRON_OK;
 }
 
-int rollout_launches(tron_env *h, int32_t k_steps, uint32_t flags, int32_t obs_fmt, void *obs, StepOut out,
-                     hipStream_t st)
+// actions: null for the env's own draws; else a tape of [k_steps][N][2] for launches of one step each (TRON_ROLLOUT_PER_STEP),
+// with row k of out's record tapes to step k
+int rollout_launches(tron_env *h, int32_t k_steps, uint32_t flags, int32_t obs_fmt, void *obs, StepOut out, hipStream_t st,
+                     const int8_t *actions = nullptr)
 {
-    static const bool env_per_step = getenv("TRON_ROLL_PER_STEP") != nullptr;   // A/B switch: one launch per step
     const bool two_streams = (flags & TRON_ROLLOUT_TWO_STREAMS) != 0u;
     if (!(h->P.obs_state && !(flags & (TRON_ROLLOUT_PER_STEP | TRON_ROLLOUT_TWO_STREAMS)))) flags &= ~TRON_ROLLOUT_RESIDENT;   // persistent obs-is-state launches only
-    const bool per_step = env_per_step || two_streams || (flags & TRON_ROLLOUT_PER_STEP) != 0u;
+    const bool per_step = overrides().per_step || two_streams || (flags & TRON_ROLLOUT_PER_STEP) != 0u;
     flags &= ~(TRON_ROLLOUT_PER_STEP | TRON_ROLLOUT_TWO_STREAMS);
     if (h->P.obs_state && !per_step && k_steps > 1) {
         const int rc = rollout_persistent(h, k_steps, flags, out, st);
         if (rc != TRON_OK) return rc;
-        k_steps = 0;
-        if (obs_fmt == TRON_OBS_PLANES3_F32 || obs_fmt == TRON_OBS_PLANES4_F32) return obs_planes(h, obs_fmt, obs, st);
-        return TRON_OK;
+        return is_f32_planes(obs_fmt) ? obs_planes(h, obs_fmt, obs, st) : TRON_OK;
     }
     flags &= ~TRON_ROLLOUT_RESIDENT;                               // only k_obs_roll knows it
-    planes_written(h);              // k_tile_roll, two streams, one launch per step
     if (!h->P.obs_state && !per_step && k_steps > 1) {             // board-owning layout: same idea, k_tile_roll
         for (int left = k_steps; left > 0; left -= TRON_ROLLOUT_CHUNK) {
             const int rc = launch_roll_fmt(h, obs_fmt, left < TRON_ROLLOUT_CHUNK ? left : TRON_ROLLOUT_CHUNK, flags, obs, out, st);
@@ -2963,10 +2976,12 @@ int rollout_launches(tron_env *h, int32_t k_steps, uint32_t flags, int32_t obs_f
         }
         return TRON_OK;
     }
-    if (two_streams && k_steps > 0) {
-        // The env batch as two independent halves, each a launch sequence of its own on its own stream: a half's
-        // step s+1 only depends on its own step s, so the drain of one half's launch overlaps the ramp-up of the
-        // other's.  Fork / join events order both against what came before and comes after on `st`.
+    // One launch per step; TRON_ROLLOUT_TWO_STREAMS: per step and per half of the envs.  The env batch as two independent
+    // halves, each a launch sequence of its own on its own stream: a half's step s+1 only depends on its own step s, so the
+    // drain of one half's launch overlaps the ramp-up of the other's.  Fork / join events order both against what came
+    // before and comes after on `st`.
+    const int parts = two_streams && k_steps > 0 ? 2 : 1;
+    if (parts == 2) {
         if (!h->side) {
             if (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess ||
                 hipEventCreateWithFlags(&h->fork, hipEventDisableTiming) != hipSuccess ||
@@ -2979,30 +2994,26 @@ int rollout_launches(tron_env *h, int32_t k_steps, uint32_t flags, int32_t obs_f
             (void)hipGetLastError();
             return TRON_ERR_LAUNCH;
         }
-        h->nparts = 2;
-        int rc = TRON_OK;
-        for (int k = 0; k < k_steps && rc == TRON_OK; ++k)
-            for (int part = 0; part < 2 && rc == TRON_OK; ++part) {
-                h->part0 = part;
-                hipStream_t s2 = part ? h->side : st;
-                rc = h->P.obs_state ? launch_obs<true>(h, nullptr, flags, out, s2)
-                                    : launch_fmt<true>(h, obs_fmt, nullptr, nullptr, flags, obs, out, s2);
-            }
-        h->part0 = 0;
-        h->nparts = 1;
-        if (hipEventRecord(h->join, h->side) != hipSuccess || hipStreamWaitEvent(st, h->join, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            return TRON_ERR_LAUNCH;
-        }
-        if (rc != TRON_OK) return rc;
-    } else {
-        for (int k = 0; k < k_steps; ++k) {
-            const int rc = h->P.obs_state ? launch_obs<true>(h, nullptr, flags, out, st)
-                                          : launch_fmt<true>(h, obs_fmt, nullptr, nullptr, flags, obs, out, st);
-            if (rc != TRON_OK) return rc;
-        }
     }
-    if (h->P.obs_state && (obs_fmt == TRON_OBS_PLANES3_F32 || obs_fmt == TRON_OBS_PLANES4_F32) && k_steps > 0)
+    const size_t n = (size_t)h->P.N;
+    int rc = TRON_OK;
+    h->nparts = parts;
+    for (int k = 0; k < k_steps && rc == TRON_OK; ++k)
+        for (int part = 0; part < parts && rc == TRON_OK; ++part) {
+            h->part0 = part;
+            hipStream_t s2 = part ? h->side : st;
+            const int8_t *a = actions ? actions + 2u * (k * n) : nullptr;
+            rc = h->P.obs_state ? launch_obs(h, a, flags, rows_from(out, k * n), s2)
+                                : launch_fmt<true>(h, obs_fmt, a, nullptr, flags, obs, rows_from(out, k * n), s2);
+        }
+    h->part0 = 0;
+    h->nparts = 1;
+    if (parts == 2 && (hipEventRecord(h->join, h->side) != hipSuccess || hipStreamWaitEvent(st, h->join, 0) != hipSuccess)) {
+        (void)hipGetLastError();
+        return TRON_ERR_LAUNCH;
+    }
+    if (rc != TRON_OK) return rc;
+    if (h->P.obs_state && is_f32_planes(obs_fmt) && k_steps > 0)
         return obs_planes(h, obs_fmt, obs, st);
     return TRON_OK;
 }
@@ -3039,25 +3050,13 @@ int tron_rollout_actions_records(tron_handle h, int32_t k_steps, const int8_t *a
     // the record tapes (any of them null): k_obs_roll_tape_rec in the persistent launches, row k to step k below
     StepOut out{out_done, out_winner, out_reward, totals};
     hipStream_t st = S_(stream);
-    const bool f32 = obs_fmt == TRON_OBS_PLANES3_F32 || obs_fmt == TRON_OBS_PLANES4_F32;
     // the persistent launches: mode None on the attached codes (k_obs_roll_tape); a single step is one per-step launch
-    if (h->P.obs_state && h->P.mode == TRON_MODE_NONE && !f32 && !(flags & TRON_ROLLOUT_PER_STEP) && k_steps > 1) {
+    if (h->P.obs_state && h->P.mode == TRON_MODE_NONE && !is_f32_planes(obs_fmt) && !(flags & TRON_ROLLOUT_PER_STEP) && k_steps > 1) {
         const int rc = rollout_persistent(h, k_steps, TRON_STEP_AUTORESET, out, st, actions);
         if (rc != TRON_ERR_UNSUPPORTED) return rc;                   // (boards past 64 chunks, a TRON_ROLL_GRID override: below)
     }
     // everywhere else: tron_step_encode's launch with row k, and the totals tron_rollout_random's per-step form keeps
-    planes_written(h);
-    const size_t row = 2u * (size_t)h->P.N, n = (size_t)h->P.N;
-    for (int k = 0; k < k_steps; ++k) {
-        const int rc = h->P.obs_state ? launch_obs<true>(h, actions + k * row, TRON_STEP_AUTORESET, out, st)
-                                      : launch_fmt<true>(h, obs_fmt, actions + k * row, nullptr, TRON_STEP_AUTORESET, obs, out, st);
-        if (rc != TRON_OK) return rc;
-        if (out.done) out.done += n;
-        if (out.winner) out.winner += n;
-        if (out.reward) out.reward += 2u * n;
-    }
-    if (h->P.obs_state && f32 && k_steps > 0) return obs_planes(h, obs_fmt, obs, st);
-    return TRON_OK;
+    return rollout_launches(h, k_steps, TRON_STEP_AUTORESET | TRON_ROLLOUT_PER_STEP, obs_fmt, obs, out, st, actions);
 }
 
 int tron_minimax_actions(tron_handle h, int32_t player, int32_t depth, int32_t mode, int8_t *out_actions,
@@ -3090,9 +3089,7 @@ int tron_encode_codes(const int8_t *tiles, int64_t n, int32_t cells, int32_t pla
     size_t blocks = (nbytes / 16 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(k_encode_codes, dim3((unsigned)blocks), dim3(256), 0, S_(stream), tiles, nbytes, player == 2,
-                       codes_out);
-    return launch_status();
+    return launch<k_encode_codes>(nullptr, dim3((unsigned)blocks), dim3(256), 0, S_(stream), tiles, nbytes, player == 2, codes_out);
 }
 
 int tron_pop_up(const int8_t *codes, int64_t n, int32_t cells, float *planes_out, void *stream)
@@ -3101,8 +3098,7 @@ int tron_pop_up(const int8_t *codes, int64_t n, int32_t cells, float *planes_out
     if (n == 0) return TRON_OK;
     size_t blocks = ((size_t)n * cells + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_pop_up, dim3((unsigned)blocks), dim3(256), 0, S_(stream), codes, (size_t)n, cells, planes_out);
-    return launch_status();
+    return launch<k_pop_up>(nullptr, dim3((unsigned)blocks), dim3(256), 0, S_(stream), codes, (size_t)n, cells, planes_out);
 }
 
 }  // extern "C"

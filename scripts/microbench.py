@@ -3,6 +3,7 @@
 step without obs}.  Development tool; bench.py is the judged entry point."""
 import argparse
 import os
+import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,6 +36,11 @@ def main():
     ap.add_argument("--tile", default="16,32,64", help="envs per workgroup tile (TRON_TILE_ENVS)")
     ap.add_argument("--extra-env", default="", help="KEY=VAL,... extra env vars for the native lib")
     a = ap.parse_args()
+    tiles = a.tile.split(",")
+    if len(tiles) > 1:                  # the library reads TRON_TILE_ENVS once per process: one child per tile size
+        for e in tiles:
+            subprocess.run([sys.executable, os.path.abspath(__file__), *sys.argv[1:], "--tile", e], check=True)
+        return
     for kv in filter(None, a.extra_env.split(",")):
         k, v = kv.split("=")
         os.environ[k] = v
