@@ -12,6 +12,8 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 F = torch.nn.functional
 
+from activation_range_support import to_px as _to_px                   # the host PX16 packer (one copy for the suite)
+
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
@@ -30,19 +32,6 @@ def _codes(B, S, seed):
     vals = torch.tensor([1, 1, 1, -1, -2, -3, 10, -10], dtype=torch.int8, device="cuda")
     return vals[torch.randint(0, 8, (B, S, S), device="cuda", generator=g)].contiguous()
 
-
-def _to_px(fused, x, scale=None):
-    """f32 [B, C, S, S] -> a PX16 image (host-side packing: test infrastructure) of x * scale."""
-    B, C, S, _ = x.shape
-    v = (x.double() * (1.0 if scale is None else scale) / 64.0)
-    hi = v.to(torch.float16)
-    lo = ((v - hi.double()) * 2048.0).to(torch.float16)
-    def lay(t):                                                      # [B, C, S, S] -> [B][octet][pixel][8 channels]
-        return t.reshape(B, C // 8, 8, S * S).permute(0, 1, 3, 2).contiguous()
-    img = torch.stack([lay(hi), lay(lo)], 1).contiguous()            # [B][hi | lo][octet][pixel][8]
-    px = fused.PX16(B, C, S, x.device)
-    px.buf.copy_(img.view(torch.uint8).reshape(-1))
-    return px
 
 
 def _grad_px(fused, g):
