@@ -1,0 +1,290 @@
+// Stateless batched playouts from observation-code boards (tron_playout_codes, include/tron_hip.h): every board is played
+// forward up to K steps under mode None's rule (Game.step, game.py:149-277) with no restart, and the call reports how it
+// ended.  A pure function of its arguments: no handle, nothing to invalidate.
+//
+//   k_playout   one lane per playout, one wave per workgroup.  A lane's board is packed two bits per cell in LDS, word w
+//               of lane l at [w * 64 + l]: whatever cell a lane touches, its bank is its lane number, so the step loop has
+//               no bank conflict.  The board is the reference's grid at the moment moves are judged — after both heads
+//               have turned into bodies (game.py:155-156) — so a head's cell holds its owner's trail; the heads
+//               themselves, the alive bits and the step count are registers.  A step costs two LDS reads and two LDS
+//               writes, a drawn move four reads more per player.
+//               Boards come in and go out through groups of four lanes per board (64-byte runs of global memory, a
+//               four-way bank conflict in LDS; sixteen boards per instruction).  Reads are 16-byte aligned chunks put
+//               together with v_alignbyte, whatever a board's base address is (odd sides, sliced tensors); only a chunk
+//               that sticks out of the caller's buffer is read byte by byte.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/tron_hip.h"
+#include "tron_device.hpp"
+
+namespace {
+
+using namespace tron;
+
+constexpr int PO_LANES = 64;                       // playouts per workgroup: one wave
+constexpr int PO_GROUP = 4;                        // lanes that share a board while boards are loaded and stored
+constexpr int PO_BOARDS = PO_LANES / PO_GROUP;     // boards per load / store instruction
+// a cell's two bits; PO_P1_HEAD is never stored: it is what plain_targets hands player 2 on player 1's new head
+constexpr uint32_t PO_EMPTY = 0u, PO_P1 = 1u, PO_P2 = 2u, PO_WALL = 3u, PO_P1_HEAD = 4u;
+constexpr uint32_t PO_COPY = 0x80000000u;          // info word of the store phase: this board's output is its input
+
+// The 16 bytes at offset `at` (16-byte aligned as an address) of base[0, total); bytes outside the buffer read as 0 and are
+// not loaded.
+__device__ __forceinline__ uint4 chunk16(const int8_t *__restrict__ base, int64_t total, int64_t at)
+{
+    if (at >= 0 && at + 16 <= total) return *reinterpret_cast<const uint4 *>(base + at);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        if (at + i >= 0 && at + i < total) w[i >> 2] |= (uint32_t)(uint8_t)base[at + i] << (8 * (i & 3));
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+// The 16 bytes at offset f of base[0, total) from the two aligned chunks that hold them.
+__device__ __forceinline__ void load16(const int8_t *__restrict__ base, int64_t total, int64_t f, uint32_t out[4])
+{
+    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(base + f) & 15u);
+    const uint4 c0 = chunk16(base, total, f - mis), c1 = mis ? chunk16(base, total, f - mis + 16) : make_uint4(0u, 0u, 0u, 0u);
+    uint32_t t[9] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, 0u};
+    if (mis & 8u) {
+#pragma unroll
+        for (int j = 0; j < 7; ++j) t[j] = t[j + 2];
+    }
+    if (mis & 4u) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) t[j] = t[j + 1];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) out[j] = __builtin_amdgcn_alignbyte(t[j + 1], t[j], mis & 3u);
+}
+// The first nvalid of 16 bytes to p: one 16-byte store where p allows it, dwords where it allows those, else bytes.
+__device__ __forceinline__ void store16(int8_t *p, int nvalid, const uint32_t x[4])
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    if (nvalid == 16 && (a & 15u) == 0u) {
+        *reinterpret_cast<uint4 *>(p) = make_uint4(x[0], x[1], x[2], x[3]);
+        return;
+    }
+    const bool dwords = (a & 3u) == 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (dwords && 4 * j + 4 <= nvalid) {
+            reinterpret_cast<uint32_t *>(p)[j] = x[j];
+        } else {
+#pragma unroll
+            for (int i = 4 * j; i < 4 * j + 4; ++i)
+                if (i < nvalid) p[i] = (int8_t)(x[j] >> (8 * (i & 3)));
+        }
+    }
+}
+
+// Heads seen so far in a board, 16 bits per player: how many (0, 1, 2 = more than one) | the first one's cell << 2.
+__device__ __forceinline__ uint32_t head_seen(uint32_t heads, int p, int cell)
+{
+    const uint32_t f = (heads >> (16 * p)) & 0xFFFFu, cnt = f & 3u;
+    const uint32_t g = cnt ? (f & ~3u) | 2u : 1u | ((uint32_t)cell << 2);
+    return (heads & ~(0xFFFFu << (16 * p))) | (g << (16 * p));
+}
+__device__ __forceinline__ uint32_t heads_merged(uint32_t a, uint32_t b)
+{
+    uint32_t out = 0u;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const uint32_t fa = (a >> (16 * p)) & 0xFFFFu, fb = (b >> (16 * p)) & 0xFFFFu;
+        const uint32_t cnt = min((fa & 3u) + (fb & 3u), 2u);
+        out |= ((((fa & 3u) ? fa : fb) & ~3u) | cnt) << (16 * p);
+    }
+    return out;
+}
+
+// The lane's own board: word w of lane l at [w * 64 + l].
+struct Board {
+    uint32_t *words;                                                   // the lane's column: words + w * PO_LANES
+    __device__ __forceinline__ uint32_t cell(int i) const { return (words[(i >> 4) * PO_LANES] >> (2 * (i & 15))) & 3u; }
+};
+
+// A safe move: the first-to-last directions UP, RIGHT, DOWN, LEFT whose target is EMPTY on the board as it stands (the
+// heads' cells hold trails), candidates[mulhi(u, c)]; UP when there is none.
+__device__ __forceinline__ int safe_move(const Board &bd, int S, int r, int c, uint32_t u)
+{
+    const int at = cell_index(S, r, c);
+    uint32_t cand = 0u, cnt = 0u;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        int dr, dc;
+        action_delta(a, dr, dc);
+        if (bd.cell(at + dr * S + dc) == PO_EMPTY) {
+            cand |= (uint32_t)a << (2u * cnt);
+            ++cnt;
+        }
+    }
+    return cnt ? (int)((cand >> (2u * __umulhi(u, cnt))) & 3u) : 0;
+}
+
+__global__ __launch_bounds__(PO_LANES) void k_playout(const int8_t *__restrict__ codes, int64_t n, int S, int k_steps,
+                                                      const int8_t *__restrict__ actions, uint32_t seed, uint32_t stream,
+                                                      uint32_t call_lo, uint32_t call_hi, int32_t *__restrict__ out_steps,
+                                                      int8_t *__restrict__ out_winner, int8_t *__restrict__ out_codes)
+{
+    extern __shared__ uint32_t po_lds[];
+    const int lane = threadIdx.x, G = S * S, WORDS = (G + 15) >> 4, W = S - 2;
+    uint32_t *info = po_lds + WORDS * PO_LANES;                        // [64] one word per board, between the phases
+    const int64_t first = (int64_t)blockIdx.x * PO_LANES, idx = first + lane, total = n * (int64_t)G;
+    const int sub = lane % PO_GROUP, gb = lane / PO_GROUP;
+    const bool have = idx < n;
+
+    // ---- boards in: lane (gb, sub) packs words sub, sub + 4, ... of boards gb, gb + 16, ... and counts their heads
+    for (int b0 = 0; b0 < PO_LANES; b0 += PO_BOARDS) {
+        const int b = b0 + gb;
+        const bool have_b = first + b < n;
+        uint32_t heads = 0u;
+        for (int w = sub; w < WORDS; w += PO_GROUP) {
+            if (!have_b) continue;
+            uint32_t x[4];
+            load16(codes, total, (first + b) * (int64_t)G + 16 * w, x);
+            const int nvalid = min(16, G - 16 * w);                    // the bytes behind them are the next board's
+            uint32_t word = 0u;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int v = i < nvalid ? (int)(int8_t)(x[i >> 2] >> (8 * (i & 3))) : -1;
+                const uint32_t cls = v == 1 ? PO_EMPTY : (v == -2 || v == 10) ? PO_P1 : (v == -3 || v == -10) ? PO_P2 : PO_WALL;
+                word |= cls << (2 * i);
+                if (v == 10) heads = head_seen(heads, 0, 16 * w + i);
+                if (v == -10) heads = head_seen(heads, 1, 16 * w + i);
+            }
+            po_lds[w * PO_LANES + b] = word;
+        }
+        heads = heads_merged(heads, (uint32_t)__shfl_xor((int)heads, 1));
+        heads = heads_merged(heads, (uint32_t)__shfl_xor((int)heads, 2));
+        if (sub == 0) info[b] = heads;
+    }
+    __syncthreads();
+
+    // ---- playable: exactly one +10 and one -10, both strictly inside the border
+    const Board bd{po_lds + lane};
+    const uint32_t heads = info[lane];
+    int r[2], c[2];
+    bool playable = have;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const uint32_t f = (heads >> (16 * p)) & 0xFFFFu;
+        const int at = (int)(f >> 2), pr = at / S, pc = at - pr * S;
+        playable = playable && (f & 3u) == 1u && pr >= 1 && pc >= 1 && pr <= W && pc <= W;
+        r[p] = pr - 1;
+        c[p] = pc - 1;
+    }
+
+    // ---- the steps.  A lane that is finished or rejected idles; the wave leaves when its last lane is done
+    uint32_t alive = META_ALIVE0 | META_ALIVE1;
+    int winner = -1, steps = 0;
+    bool live = playable;
+    const int8_t *tape = actions ? actions + 2 * idx : nullptr;        // row t: tape + t * 2n
+    auto tape_row = [&](int t) {
+        uint16_t v;
+        __builtin_memcpy(&v, tape + (int64_t)t * 2 * n, 2);
+        return (uint32_t)v;
+    };
+    uint32_t ahead = (tape && live && k_steps > 0) ? tape_row(0) : 0xFFFFu;
+    for (int t = 0; t < k_steps; ++t) {
+        if (!__ballot(live)) break;
+        const uint32_t now = ahead;
+        if (tape && live && t + 1 < k_steps) ahead = tape_row(t + 1);  // one step ahead of its use
+        if (!live) continue;
+        int a[2] = {(int)(int8_t)now, (int)(int8_t)(now >> 8)};
+        if ((a[0] | a[1]) < 0) {                                       // a negative byte: one Philox block serves both players
+            uint32_t u[4];
+            philox4x32_10((uint32_t)idx, (uint32_t)t, call_lo, call_hi, seed, stream, u);
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+                if (a[p] < 0) a[p] = safe_move(bd, S, r[p], c[p], u[p]);
+        }
+        // Game.step: both move, then each is judged on the cell it entered, player 2 after player 1's head is down
+        int old[2], f[2];
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            int dr, dc;
+            action_delta(a[p] & 3, dr, dc);
+            old[p] = cell_index(S, r[p], c[p]);
+            r[p] += dr;
+            c[p] += dc;
+            f[p] = cell_index(S, r[p], c[p]);
+        }
+        uint32_t *w0 = bd.words + (f[0] >> 4) * PO_LANES, *w1 = bd.words + (f[1] >> 4) * PO_LANES;
+        const uint32_t s0 = 2u * (uint32_t)(f[0] & 15), s1 = 2u * (uint32_t)(f[1] & 15);
+        uint32_t x0 = *w0, x1 = *w1;
+        uint32_t tf[2] = {(x0 >> s0) & 3u, (x1 >> s1) & 3u};
+        plain_targets(old, f, tf, PO_P1, PO_P2, PO_P1_HEAD);
+#pragma unroll
+        for (int p = 0; p < 2; ++p) alive = collide(alive, p, W, r[p], c[p], tf[p] == PO_EMPTY);
+        // the new heads' cells take their owners' trails (what they are once the next step begins); a cell a player died
+        // on is a head's cell of the last position, which the head byte covers
+        x0 |= PO_P1 << s0;
+        if (w1 == w0) x1 = x0;
+        x1 |= PO_P2 << s1;
+        *w0 = x0;
+        *w1 = x1;
+        steps = t + 1;
+        int won = 0;
+        if (settle(alive, r, c, won)) {
+            winner = won;
+            live = false;
+        }
+    }
+    if (have) {
+        if (out_steps) out_steps[idx] = playable ? steps : 0;
+        if (out_winner) out_winner[idx] = (int8_t)(playable ? winner : -2);
+    }
+    if (!out_codes) return;
+
+    // ---- boards out: the last position's cells from LDS with the two head bytes on top, player 2's last (game.py:205-214);
+    // a rejected board, and every board of a call of no steps, is its input copied
+    info[lane] = (playable && k_steps > 0) ? (uint32_t)cell_index(S, r[0], c[0]) | ((uint32_t)cell_index(S, r[1], c[1]) << 11) : PO_COPY;
+    __syncthreads();
+    constexpr uint32_t CODE_OF = pack4(1, -2, -3, -1);                 // PO_EMPTY, PO_P1, PO_P2, PO_WALL as player 1 sees them
+    for (int b0 = 0; b0 < PO_LANES; b0 += PO_BOARDS) {
+        const int b = b0 + gb;
+        if (first + b >= n) continue;
+        const uint32_t inf = info[b];
+        for (int w = sub; w < WORDS; w += PO_GROUP) {
+            const int64_t at = (first + b) * (int64_t)G + 16 * w;
+            uint32_t x[4];
+            if (inf & PO_COPY) {
+                load16(codes, total, at, x);
+            } else {
+                const uint32_t word = po_lds[w * PO_LANES + b];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t q = word >> (8 * j);                // four cells' classes, one per selector byte
+                    x[j] = __builtin_amdgcn_perm(0u, CODE_OF, (q & 3u) | ((q & 0xCu) << 6) | ((q & 0x30u) << 12) | ((q & 0xC0u) << 18));
+                }
+#pragma unroll
+                for (int p = 0; p < 2; ++p) {
+                    const int h = (int)((inf >> (11 * p)) & 0x7FFu);
+                    if ((h >> 4) != w) continue;
+                    const uint32_t sh = 8u * (uint32_t)(h & 3), byte = p == 0 ? 10u : (uint32_t)(uint8_t)-10;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (((h & 15) >> 2) == j) x[j] = (x[j] & ~(0xFFu << sh)) | (byte << sh);
+                }
+            }
+            store16(out_codes + at, min(16, G - 16 * w), x);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int tron_playout_codes(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, const int8_t *actions,
+                                  uint32_t seed, uint32_t stream_id, uint64_t call, int32_t *out_steps, int8_t *out_winner,
+                                  int8_t *out_codes, void *stream)
+{
+    if (n < 0 || n > 0x7FFFFFFF || k_steps < 0 || (!codes && n > 0) || (out_codes && out_codes == codes)) return TRON_ERR_BAD_ARG;
+    if (side < 6 || side > 34) return TRON_ERR_UNSUPPORTED;
+    if (n == 0) return TRON_OK;
+    const int words = (side * side + 15) >> 4;
+    const size_t smem = (size_t)(words + 1) * PO_LANES * sizeof(uint32_t);     // 18 944 bytes at side 34: no LDS opt-in
+    hipLaunchKernelGGL(k_playout, dim3((unsigned)((n + PO_LANES - 1) / PO_LANES)), dim3(PO_LANES), smem,
+                       reinterpret_cast<hipStream_t>(stream), codes, n, side, k_steps, actions, seed, stream_id, (uint32_t)call,
+                       (uint32_t)(call >> 32), out_steps, out_winner, out_codes);
+    return hipGetLastError() == hipSuccess ? TRON_OK : TRON_ERR_LAUNCH;
+}

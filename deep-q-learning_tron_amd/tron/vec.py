@@ -29,6 +29,7 @@ class VecTron:
         self.S = self.W + 2
         self.G = self.S * self.S
         self.mode = mode
+        self.seed, self.rank = seed & 0xFFFFFFFF, rank & 0xFFFFFFFF
         self.obs_format = obs_format
         self._fmt = nat.OBS[obs_format]
         self._lib = nat.lib()
@@ -279,6 +280,23 @@ class VecTron:
                       "tron_minimax_actions")
         return (out, values, expanded) if want_values else out
 
+    def playout(self, actions=None, k_steps=None, copies=1, call=0, want_codes=False):
+        """playout_codes on every env's current board, `copies` times each: playout i * copies + j is env i, and the tape
+        (if any) is int8 [K, N * copies, 2].  The boards are the player-1 codes — the attached buffer's plane, or a fresh
+        encode("codes") — and the draws are keyed by this env's seed and rank; the env itself is left exactly as it was.
+        Mode None only.  Returns (steps, winner, final_codes | None) as playout_codes does; a finished env's row is what
+        playout_codes makes of its image."""
+        if self.mode not in (None, "none"):
+            raise ValueError("playout plays mode None's rule; the sliding modes have no playout")
+        if int(copies) < 1:
+            raise ValueError("copies is at least 1")
+        if self.obs_is_state:
+            p1 = self.obs[:, 0]
+        else:
+            p1 = self.encode("codes", out=self._alloc_obs(nat.OBS_CODES_I8))[:, 0]
+        return playout_codes(p1.repeat_interleave(int(copies), dim=0), actions, k_steps, seed=self.seed, stream_id=self.rank,
+                             call=call, want_codes=want_codes)
+
     # -- read-back ---------------------------------------------------------
     def grid(self):
         """int8 [N, W+2, W+2] Tile values (map.py:9-17)."""
@@ -335,6 +353,43 @@ def minimax_codes(codes, draws=None, mode="voronoi", depth=2):
                                                nat.ptr(act), nat.ptr(values), nat.ptr(expanded), nat.stream_ptr()),
                   "tron_minimax_codes")
     return act, values, expanded
+
+
+def playout_codes(codes, actions=None, k_steps=None, seed=0x5EED, stream_id=0, call=0, want_codes=False):
+    """Plays a stack of observation-code boards int8 [n, S, S] (player 1's view: encode_codes(.., 1), a VecTron's
+    obs[:, 0]) forward up to k_steps steps of mode None's Game.step, without restart (tron_playout_codes).  Returns
+    (steps int32 [n], winner int8 [n], final_codes int8 [n, S, S] or None): steps played, 0 draw / 1 / 2 / -1 not
+    finished / -2 rejected (not exactly one +10 and one -10 inside the border), and — want_codes=True — player 1's
+    observation of the last position reached.  actions: int8 tape [K, n, 2], step-major; a byte 0..127 is an action (its
+    low two bits), a negative byte draws a safe move for that player in that step; None draws every move.  k_steps
+    defaults to the tape's length.  The draws are Philox keyed by (seed, stream_id) at counter (playout, step, call):
+    pass another `call` for another set of playouts of the same boards; a fork is a repeat_interleave of the codes."""
+    c = codes.contiguous()
+    if c.dtype != torch.int8 or c.dim() != 3 or c.shape[1] != c.shape[2]:
+        raise ValueError(f"playout_codes takes int8 boards [n, S, S], got {c.dtype} {tuple(c.shape)}")
+    n, side = int(c.shape[0]), int(c.shape[-1])
+    a = None
+    if actions is not None:
+        if actions.dtype != torch.int8 or actions.dim() != 3 or tuple(actions.shape[1:]) != (n, 2):
+            raise ValueError(f"expected an int8 tape of shape (K, {n}, 2), got {actions.dtype} {tuple(actions.shape)}")
+        a = actions.contiguous()
+        if k_steps is None:
+            k_steps = int(a.shape[0])
+        elif int(k_steps) > int(a.shape[0]):
+            raise ValueError(f"k_steps {k_steps} is more than the tape's {int(a.shape[0])} rows")
+    elif k_steps is None:
+        raise ValueError("playout_codes needs k_steps when there is no tape")
+    cp, ap = nat.ptr(c), nat.ptr(a)                                   # host tensors are refused here
+    if a is not None and a.device != c.device:
+        raise ValueError(f"the tape must be on {c.device}, got {a.device}")
+    steps = torch.empty(n, dtype=torch.int32, device=c.device)
+    winner = torch.empty(n, dtype=torch.int8, device=c.device)
+    final = torch.empty_like(c) if want_codes else None
+    with torch.cuda.device(c.device):
+        nat.check(nat.lib().tron_playout_codes(cp, n, side, int(k_steps), ap, seed & 0xFFFFFFFF, stream_id & 0xFFFFFFFF,
+                                               int(call) & 0xFFFFFFFFFFFFFFFF, nat.ptr(steps), nat.ptr(winner),
+                                               nat.ptr(final), nat.stream_ptr()), "tron_playout_codes")
+    return steps, winner, final
 
 
 def pop_up_planes(codes):

@@ -388,6 +388,41 @@ int tron_minimax_codes(const int8_t *codes, int64_t n, int32_t side, int32_t dep
                        const uint32_t *draws, int8_t *out_actions, int32_t *out_values, int8_t *out_expanded,
                        void *stream);
 
+/* ---- stateless playouts from observation-code boards (csrc/tron_playout.hip) ---------------------------
+ * Plays each of n boards forward up to k_steps steps of mode None's Game.step (game.py:149-277: both heads become
+ * bodies, both players move, a player dies on a target that is off the board or not empty, player 2 after player 1's
+ * head is down) and reports how it ended.  No handle, no restart, no reward, no slide: a pure function of its
+ * arguments, like tron_minimax_codes.  A fork of a position is the same board given twice.
+ * codes     i8[n][side][side]: player 1's observation of each board (map.py:67-84; what tron_encode_codes(.., 1) and
+ *           the attached buffer's player-1 plane hold): 1 empty, -1 wall, -2 / -3 bodies, +10 / -10 heads.  Any other
+ *           byte is read as a wall.  A board is playable when it holds exactly one +10 and exactly one -10, both strictly
+ *           inside the border (tron_minimax_codes' condition); any other board is REJECTED.  A finished game's image
+ *           that still shows two heads cannot be told from a live one: not passing those is the caller's business.
+ * actions   i8[k_steps][n][2], step-major, or NULL.  A byte 0..127 is an action, read as tron_step_encode reads it
+ *           (its low two bits, 0..3 = UP, RIGHT, DOWN, LEFT).  A negative byte means: draw a safe move for this player in
+ *           this step; NULL means every byte is negative.  Rows after a playout's end are not used.
+ * safe move the directions, in the order UP, RIGHT, DOWN, LEFT, whose target cell is empty on the board as it stands
+ *           before the step (the opponent's simultaneous move is not looked at): with c >= 1 of them
+ *           candidates[mulhi(u, c)], with none UP.  u = word p (player 0 / 1) of Philox-4x32-10 at counter (playout
+ *           index, step, call low, call high) under key (seed, stream_id), tron_eps_greedy's conventions: a function
+ *           of (index, step, player, seed, stream_id, call) alone, whatever the launch looks like.
+ * out_steps  i32[n] or NULL: steps played — 1..k_steps for a playout that finished, k_steps for one that did not, 0
+ *            for a rejected board.
+ * out_winner i8[n] or NULL: 0 draw, 1, 2, -1 not finished within k_steps, -2 rejected.
+ * out_codes  i8[n][side][side] or NULL, not `codes` itself: player 1's observation of the last position reached (for a
+ *            finished playout bit for bit the reference's next_p1: the head bytes are written where the reference
+ *            writes them, on a wall or a body cell included); a rejected board's is its input copied.
+ * TRON_ERR_BAD_ARG: codes == NULL with n > 0, n < 0 or n >= 2^31, k_steps < 0, out_codes == codes;
+ * TRON_ERR_UNSUPPORTED: side outside 6..34 (boards 4x4 to 32x32, odd widths included).  n == 0 launches nothing;
+ * k_steps == 0 writes steps 0, winner -1 (or -2) and copies the codes.  Nothing outside [0, n) of an output is written. */
+int tron_playout_codes(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps,
+                       const int8_t *actions,            /* i8[k_steps][n][2] step-major, or NULL */
+                       uint32_t seed, uint32_t stream_id, uint64_t call,
+                       int32_t *out_steps,               /* i32[n]            or NULL */
+                       int8_t  *out_winner,              /* i8[n]             or NULL */
+                       int8_t  *out_codes,               /* i8[n][side][side] or NULL; may not alias codes */
+                       void *stream);
+
 /* ---- K-FAC helper of the ACKTR path (Net/kfac.py:28-38 `_extract_patches`; its TODO at kfac.py:9-12
  * asks for this kernel) -------------------------------------------------------------------------- */
 /* x f32[batch][channels][height][width] -> out f32[batch*OH*OW][channels*kh*kw], row = (sample, oy, ox),
