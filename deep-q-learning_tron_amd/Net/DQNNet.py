@@ -16,13 +16,8 @@ import torch.nn.functional as F
 from config import MAP_WIDTH
 from Net.activations import (mish as _mish, conv_bias_mish as _conv_bias_mish, pool_conv7_mish as _pool_conv7_mish,
                              pool_conv7_supported as _pool_conv7_supported, pool_s2 as _pool_s2, linear as _linear,
-                             pool_conv7_cl_mish as _pool_conv7_cl_mish, pool_conv7_cl_supported as _pool_conv7_cl_supported)
-
-
-def _pool_is_reference(pool):
-    """AvgPool2d(kernel_size=3, padding=1, stride=2) as DQNNet.py:20 builds it."""
-    return (isinstance(pool, nn.AvgPool2d) and pool.kernel_size == 3 and pool.stride == 2 and pool.padding == 1
-            and pool.count_include_pad and not pool.ceil_mode and pool.divisor_override is None)
+                             pool_conv7_cl_mish as _pool_conv7_cl_mish, pool_conv7_cl_supported as _pool_conv7_cl_supported,
+                             _planes_from_codes, _is_ref_pool as _pool_is_reference)
 
 
 def conv7_side(side):
@@ -74,11 +69,7 @@ class Net(nn.Module):
             if self.fuse_trunk and trunk_supported(self, codes):
                 return self._after_trunk(trunk_mish(self, codes, plane4))
             return self._after_conv1(conv1_codes_mish(self.conv1, codes, plane4))
-        from tron.vec import pop_up_planes
-        x = pop_up_planes(codes.reshape(-1, side, side))
-        if self.in_channels == 4:
-            x = torch.cat([x, torch.full_like(x[:, :1], plane4)], 1)
-        return self(x)
+        return self(_planes_from_codes(codes.reshape(-1, side, side), self.in_channels, plane4))
 
     def forward(self, x):                         # DQNNet.py:33-63
         x = x.to(self.conv1.weight.device)
@@ -174,10 +165,7 @@ class Net(nn.Module):
             if not (x.is_cuda and fused.supported(self.conv1, side) and fused.supported(self.conv6, side)
                     and (codes or x.dtype == torch.float32)):
                 if codes:
-                    from tron.vec import pop_up_planes
-                    x = pop_up_planes(x.reshape(-1, side, side))
-                    if self.in_channels == 4:
-                        x = torch.cat([x, torch.full_like(x[:, :1], plane4)], 1)
+                    x = _planes_from_codes(x.reshape(-1, side, side), self.in_channels, plane4)
                 was_training = self.training
                 self.eval()
                 try:

@@ -4,8 +4,24 @@ On the GPU both directions are one pass of csrc/tron_nn.hip (one exp and one div
 e = exp(x), tanh(softplus(x)) = n / (n + 2), n = e (e + 2)); torch's fused F.mish evaluates exp, log1p
 and tanh in turn and was 14 % of the DDQN trainer's GPU time.  CPU tensors (the parity tests against the
 reference's fixtures) and non-fp32 tensors take F.mish."""
+import os
+import threading
+
 import torch
 import torch.nn.functional as F
+
+_use_linear_hip = os.environ.get("TRON_LINEAR_HIP", "1") != "0"           # 0: the library's weight-gradient GEMMs (A/B measurements)
+# tron_linear_wgrad is plain f32 FMAs on 64 x 64 tiles: right for the head's small layers (<= 150 K outputs), 239 us for fc1 behind
+# 24x24 boards (256 x 3136 outputs over a batch of 4 096: 6.6 GFLOP) — from this many outputs on the weight gradient is tron_gemm_f16x3
+_LIN_WGRAD_GEMM = int(os.environ.get("TRON_LIN_WGRAD_GEMM", str(1 << 19)))
+_use_pool_conv7_cl = os.environ.get("TRON_POOL_CONV7_HIP", "1") != "0"
+
+# conv1 .. conv6 with their two residual connections, the trunk of every net here (DQNNet.py:10-15,33-50; ACNet.py:97-111): per
+# layer (cin, cout, index of the activation that is its residual, or None).  Activation k is conv k's output and activation 0 the
+# net's input (3 or 4 planes: conv1's cin is the net's), so a1 feeds conv3 and a4 feeds conv6.  Every trunk node below walks this.
+_TRUNK = ((None, 32, None), (32, 32, None), (32, 32, 1), (32, 64, None), (64, 64, None), (64, 64, 4))
+_TRUNK_CHANNELS = [(cin, cout) for cin, cout, _ in _TRUNK[1:]]              # conv2 .. conv6
+_RESIDUAL_SOURCES = {res for _, _, res in _TRUNK if res is not None}
 
 
 class _Mish(torch.autograd.Function):
@@ -23,9 +39,7 @@ class _Mish(torch.autograd.Function):
     def backward(ctx, grad_y):
         from tron import _native as nat
         (x,) = ctx.saved_tensors
-        g = grad_y.contiguous()
-        if not _aligned16(g):
-            g = g.clone(memory_format=torch.contiguous_format)
+        g = _grad_in(grad_y)
         gx = torch.empty_like(x)
         with torch.cuda.device(x.device):
             nat.check(nat.lib().tron_mish_bwd(nat.ptr(x), nat.ptr(g), nat.ptr(gx), x.numel(), nat.stream_ptr()),
@@ -36,6 +50,62 @@ class _Mish(torch.autograd.Function):
 def _aligned16(*tensors):
     """The HIP passes use 16-byte accesses: a contiguous view at an odd storage offset (t[1:]) is not eligible."""
     return all(t is None or (t.is_contiguous() and t.data_ptr() % 16 == 0) for t in tensors)
+
+
+# ---- what the nodes' backward passes share ---------------------------------------------------------------------------------
+def _grad_in(grad):
+    """A backward's incoming gradient as the kernels take it: contiguous and 16-byte aligned (a copy where it is not)."""
+    g = grad.contiguous()
+    return g if _aligned16(g) else g.clone(memory_format=torch.contiguous_format)
+
+
+def _conv3x3_bwd_library(gp, x, weight, want_input, want_weight):
+    """(input gradient, weight gradient) of a 3x3 / pad 1 layer from the library, for what the gradient kernels do not cover."""
+    return torch.ops.aten.convolution_backward(gp, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
+                                               [want_input, want_weight, False])[:2]
+
+
+def _conv3x3_wgrad(x, gp, weight, absmax=None):
+    """The weight gradient of a 3x3 / pad 1 layer from its f32 input and the gradient at its output: tron_conv3x3_wgrad where it
+    covers the shape (not the 24x24 boards' conv1 in f32 arithmetic, say), else the library."""
+    from Net import fused
+    if fused.wgrad_supported(weight, x.shape[-1]):
+        return fused.conv3x3_wgrad(x, gp, absmax)
+    return _conv3x3_bwd_library(gp, x, weight, False, True)[1]
+
+
+def _conv3x3_dgrad(gp, x, weight, absmax):
+    """The input gradient of a 3x3 / pad 1 layer: tron_conv3x3_dgrad for 32 or 64 input channels; conv1's planes asked for their
+    gradient (saliency, a layer in front): the library."""
+    from Net import fused
+    if weight.shape[1] in (32, 64):
+        return fused.conv3x3_dgrad(gp, weight.detach(), absmax)
+    return _conv3x3_bwd_library(gp, x, weight, True, False)[0]
+
+
+def _planes_from_codes(codes, cin, plane4):
+    """util.pop_up's f32 planes [B, cin, S, S] (util.py:11-37) of int8 observation codes [B, S, S]; a fourth plane is the constant
+    plane4."""
+    from tron.vec import pop_up_planes
+    x = pop_up_planes(codes)
+    if cin == 4:
+        x = torch.cat([x, torch.full_like(x[:, :1], plane4)], 1)
+    return x
+
+
+def _conv_params(convs):
+    """[w1, b1, w2, b2, ...]: how a node takes the parameters of a run of convolution modules."""
+    return [t for c in convs for t in (c.weight, c.bias)]
+
+
+def _param_grads(gw, gb, need, bias_shapes=None):
+    """The (weight, bias) part of a backward's return values for parameters passed as `_conv_params` from input 2 on: need is
+    ctx.needs_input_grad; bias_shapes: the shapes the biases came in with, where they were not flat."""
+    grads = []
+    for k in range(len(gw)):
+        b = gb[k] if bias_shapes is None else gb[k].reshape(bias_shapes[k])
+        grads += [gw[k], b if need[3 + 2 * k] else None]
+    return grads
 
 
 def mish(x):
@@ -61,7 +131,7 @@ def bias_mish_bwd(pre, g, want_absmax=False):
 class _ConvBiasMishHIP(torch.autograd.Function):
     """mish(conv3x3(x) + bias (+ residual)) with forward, input gradient and weight gradient on the hand-written kernels
     (csrc/tron_conv_f16.hip, tron_conv_wgrad.hip) and activation + bias gradient in one pass of csrc/tron_nn.hip.  Shapes
-    the gradient kernels do not cover (24x24 boards' weight gradient) go through aten.convolution_backward."""
+    the gradient kernels do not cover (24x24 boards' weight gradient) go through the library's convolution backward."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, residual, grad_pre_hook=None):
@@ -78,28 +148,15 @@ class _ConvBiasMishHIP(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from Net import fused
         x, weight, pre = ctx.saved_tensors
-        g = grad_out.contiguous()
-        if not _aligned16(g):
-            g = g.clone(memory_format=torch.contiguous_format)
-        gp, gb, absmax = bias_mish_bwd(pre, g, want_absmax=True)
+        gp, gb, absmax = bias_mish_bwd(pre, _grad_in(grad_out), want_absmax=True)
         if ctx.grad_pre_hook is not None:
             ctx.grad_pre_hook(gp)
-        gx = None
+        gx = gw = None
         if ctx.needs_input_grad[0]:
-            if weight.shape[1] in (32, 64):
-                gx = fused.conv3x3_dgrad(gp, weight.detach(), absmax)
-            else:                                 # conv1's planes asked for their gradient (saliency, a layer in front): the library
-                gx = torch.ops.aten.convolution_backward(gp, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
-                                                         [True, False, False])[0]
-        gw = None
+            gx = _conv3x3_dgrad(gp, x, weight, absmax)
         if ctx.needs_input_grad[1] and not (_skips_weight_gradient(ctx) and weight.shape[1] >= 16):
-            if fused.wgrad_supported(weight, x.shape[-1]):
-                gw = fused.conv3x3_wgrad(x, gp, absmax)
-            else:
-                gw = torch.ops.aten.convolution_backward(gp, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
-                                                         [False, True, False])[1]
+            gw = _conv3x3_wgrad(x, gp, weight, absmax)
         return gx, gw, (gb.reshape(ctx.bias_shape) if ctx.needs_input_grad[2] else None), (gp if ctx.has_res else None), None
 
 
@@ -118,23 +175,11 @@ class _Conv1CodesHIP(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from Net import fused
-        from tron.vec import pop_up_planes
         codes, weight, pre = ctx.saved_tensors
-        g = grad_out.contiguous()
-        if not _aligned16(g):
-            g = g.clone(memory_format=torch.contiguous_format)
-        gp, gb, absmax = bias_mish_bwd(pre, g, want_absmax=True)
+        gp, gb, absmax = bias_mish_bwd(pre, _grad_in(grad_out), want_absmax=True)
         gw = None
         if ctx.needs_input_grad[1]:
-            x = pop_up_planes(codes)
-            if weight.shape[1] == 4:
-                x = torch.cat([x, torch.full_like(x[:, :1], ctx.plane4)], 1)
-            if fused.wgrad_supported(weight, x.shape[-1]):
-                gw = fused.conv3x3_wgrad(x, gp, absmax)
-            else:
-                gw = torch.ops.aten.convolution_backward(gp, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
-                                                         [False, True, False])[1]
+            gw = _conv3x3_wgrad(_planes_from_codes(codes, weight.shape[1], ctx.plane4), gp, weight, absmax)
         return None, gw, (gb if ctx.needs_input_grad[2] else None), None
 
 
@@ -146,9 +191,6 @@ class _Conv1CodesHIP(torch.autograd.Function):
 # Brain flips `scope.skip_weight_gradients` around its statistics pass.  A backward of any other graph — the other player's
 # Brain, another thread — holds another scope (or none) and is unaffected.  (Backward itself runs on autograd's device
 # thread, which is why the node carries the scope instead of looking one up.)
-import threading as _threading
-
-
 class GradScope:
     __slots__ = ("skip_weight_gradients",)
 
@@ -156,7 +198,7 @@ class GradScope:
         self.skip_weight_gradients = False
 
 
-_forward_scope = _threading.local()
+_forward_scope = threading.local()
 
 
 class grad_scope:
@@ -199,11 +241,8 @@ class _Conv3x3HIP(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from Net import fused
         x, weight = ctx.saved_tensors
-        g = grad_out.contiguous()
-        if not _aligned16(g):
-            g = g.clone(memory_format=torch.contiguous_format)
+        g = _grad_in(grad_out)
         from tron import _native as nat                       # max |g| in one launch: the gradient's scale on its way into f16 (tron_conv3x3_dgrad)
         o4 = torch.zeros(4, dtype=torch.float32, device=g.device)
         with torch.cuda.device(g.device):
@@ -211,17 +250,9 @@ class _Conv3x3HIP(torch.autograd.Function):
         absmax = o4[1:2]
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            if weight.shape[1] in (32, 64):
-                gx = fused.conv3x3_dgrad(g, weight.detach(), absmax)
-            else:
-                gx = torch.ops.aten.convolution_backward(g, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
-                                                         [True, False, False])[0]
+            gx = _conv3x3_dgrad(g, x, weight, absmax)
         if ctx.needs_input_grad[1] and not (_skips_weight_gradient(ctx) and weight.shape[1] >= 16):
-            if fused.wgrad_supported(weight, x.shape[-1]):
-                gw = fused.conv3x3_wgrad(x, g, absmax)
-            else:                                             # (shapes the weight-gradient kernels do not cover)
-                gw = torch.ops.aten.convolution_backward(g, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
-                                                         [False, True, False])[1]
+            gw = _conv3x3_wgrad(x, g, weight, absmax)
         if ctx.needs_input_grad[2]:
             gb = g.sum((0, 2, 3))
         return gx, gw, gb
@@ -256,113 +287,119 @@ class _TrunkHIP(torch.autograd.Function):
         w, b = wb[0::2], wb[1::2]
         codes = x.dtype == torch.int8
         ws = fused.split_weights(list(w))                            # all six layers' split weights in one launch
-        a1, z1 = fused.conv3x3_raw(x, w[0], b[0], None, act=True, codes=codes, plane4=plane4, want_pre=True, presplit=ws[0])
-        a2, z2 = fused.conv3x3_raw(a1, w[1], b[1], None, act=True, want_pre=True, presplit=ws[1])
-        a3, z3 = fused.conv3x3_raw(a2, w[2], b[2], a1, act=True, want_pre=True, presplit=ws[2])
-        a4, z4 = fused.conv3x3_raw(a3, w[3], b[3], None, act=True, want_pre=True, presplit=ws[3])
-        a5, z5 = fused.conv3x3_raw(a4, w[4], b[4], None, act=True, want_pre=True, presplit=ws[4])
-        a6, z6 = fused.conv3x3_raw(a5, w[5], b[5], a4, act=True, want_pre=True, presplit=ws[5])
-        ctx.save_for_backward(x, a1, a2, a3, a4, a5, z1, z2, z3, z4, z5, z6, *w)
+        a, z = fused.conv3x3_raw(x, w[0], b[0], None, act=True, codes=codes, plane4=plane4, want_pre=True, presplit=ws[0])
+        acts, pres = [x, a], [z]                                     # a0 (the input), a1 ..; z1 ..
+        for k in range(1, 6):
+            res = _TRUNK[k][2]
+            a, z = fused.conv3x3_raw(a, w[k], b[k], None if res is None else acts[res], act=True, want_pre=True, presplit=ws[k])
+            acts.append(a)
+            pres.append(z)
+        ctx.save_for_backward(*acts[:6], *pres, *w)
         ctx.plane4 = plane4
-        return a6
+        return a
 
     @staticmethod
     def backward(ctx, grad_out):
         from Net import fused
-        x, a1, a2, a3, a4, a5, z1, z2, z3, z4, z5, z6, *w = ctx.saved_tensors
-        g = grad_out.contiguous()
-        if not _aligned16(g):
-            g = g.clone(memory_format=torch.contiguous_format)
-        side = g.shape[-1]
+        t = ctx.saved_tensors
+        acts, pres, w = t[:6], t[6:12], t[12:]
+        x = acts[0]
         need = ctx.needs_input_grad                                 # (x, plane4, w1, b1, ..., w6, b6)
-
-        def wgrad(layer, inp, gp, am):
-            if not need[2 + 2 * layer]:
-                return None
-            if fused.wgrad_supported(w[layer], side):
-                return fused.conv3x3_wgrad(inp, gp, am)
-            return torch.ops.aten.convolution_backward(gp, inp, w[layer], None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
-                                                       [False, True, False])[1]
-
-        gb = [None] * 6
-        gw = [None] * 6
-        gp6, gb[5], am = bias_mish_bwd(z6, g, want_absmax=True)
-        del g
-        gw[5] = wgrad(5, a5, gp6, am)
-        gp5, gb[4], am5 = fused.conv3x3_dgrad_mish(gp6, w[5], am, z5)
-        gw[4] = wgrad(4, a4, gp5, am5)
-        gp4, gb[3], am4 = fused.conv3x3_dgrad_mish(gp5, w[4], am5, z4, extra=gp6)    # a4 also feeds conv6's residual
-        del gp5, gp6
-        gw[3] = wgrad(3, a3, gp4, am4)
-        gp3, gb[2], am3 = fused.conv3x3_dgrad_mish(gp4, w[3], am4, z3)
-        del gp4
-        gw[2] = wgrad(2, a2, gp3, am3)
-        gp2, gb[1], am2 = fused.conv3x3_dgrad_mish(gp3, w[2], am3, z2)
-        gw[1] = wgrad(1, a1, gp2, am2)
-        gp1, gb[0], am1 = fused.conv3x3_dgrad_mish(gp2, w[1], am2, z1, extra=gp3)    # a1 also feeds conv3's residual
-        del gp2, gp3
+        gb, gw = [None] * 6, [None] * 6
+        gp, gb[5], am = bias_mish_bwd(pres[5], _grad_in(grad_out), want_absmax=True)
+        held = {}                                                   # gradients on their way to the activation a residual link took
+        for k in range(5, 0, -1):                                   # conv(k + 1): gp is the gradient at its pre-activation
+            res = _TRUNK[k][2]
+            if need[2 + 2 * k]:
+                gw[k] = _conv3x3_wgrad(acts[k], gp, w[k], am)
+            if res is not None:
+                held[res] = gp
+            gp, gb[k - 1], am = fused.conv3x3_dgrad_mish(gp, w[k], am, pres[k - 1], extra=held.pop(k, None))   # (frees what it replaces)
         gx = None
-        planes = x
         if x.dtype == torch.int8:
-            if need[2]:
-                from tron.vec import pop_up_planes
-                planes = pop_up_planes(x)
-                if w[0].shape[1] == 4:
-                    planes = torch.cat([planes, torch.full_like(planes[:, :1], ctx.plane4)], 1)
+            x = _planes_from_codes(x, w[0].shape[1], ctx.plane4) if need[2] else None
         elif need[0]:                                               # the planes asked for their gradient (saliency): the library
-            gx = torch.ops.aten.convolution_backward(gp1, x, w[0], None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
-                                                     [True, False, False])[0]
-        gw[0] = wgrad(0, planes, gp1, am1)
-        grads = [gx, None]
-        for k in range(6):
-            grads += [gw[k], gb[k] if need[3 + 2 * k] else None]
-        return tuple(grads)
+            gx = _conv3x3_bwd_library(gp, x, w[0], True, False)[0]
+        if need[2]:
+            gw[0] = _conv3x3_wgrad(x, gp, w[0], am)
+        return (gx, None, *_param_grads(gw, gb, need))
 
 
-def _trunk_px_forward(codes, plane4, w, b, last_f32, pooled12=False):
-    """conv1 .. conv6 on the weight-stationary chain with the pre-activations kept (csrc/tron_conv_ws_train.hip).  Returns conv6's
-    output (f32 NCHW if last_f32, else PX16; pooled12 at 12x12: its AvgPool2d(3, 2, 1) as f32 [B, 64 * 36] instead — conv6 and the
-    pooling are then one launch and conv6's output is never stored) and the tensors the backward needs."""
+def _px_forward(x, plane4, w, b, end):
+    """conv1 .. conv6 on the weight-stationary chain with the pre-activations kept (csrc/tron_conv_ws_train.hip).  x: the env's int8
+    codes (conv1 reads them: tron_conv1_px16_train) or f32 planes (conv1 on the chunked kernel, its output and pre-activation
+    turned into PX16 images once).  end: what conv6 writes — "f32" NCHW, "px16", or "pool12": its AvgPool2d(3, 2, 1) as f32
+    [B, 64 * 36] (12x12 only: conv6 and the pooling are one launch and conv6's output is never stored).  Returns that, the PX16
+    activations a1 .. a5 and the tensors the backward needs: (x, the buffers of a1 .. a5, of z1 .. z6)."""
     from Net import fused
-    frag = fused._split_jobs(list(w[1:6]), "tron_conv3x3_ws_split_weights", False)
-    a1, z1 = fused.conv1_px16_train(codes, w[0], b[0], plane4)
-    a2, z2 = fused.conv_ws_train(a1, 32, frag[0], b[1])
-    a3, z3 = fused.conv_ws_train(a2, 32, frag[1], b[2], residual=a1)
-    a4, z4 = fused.conv_ws_train(a3, 64, frag[2], b[3])
-    a5, z5 = fused.conv_ws_train(a4, 64, frag[3], b[4])
-    if pooled12 and fused.use_pool_fused_train and codes.shape[-1] == 12 and codes.shape[0] > 0 and not last_f32:
-        out, z6 = fused.conv_ws_train_pool12(a5, frag[4], b[5], a4)
+    if x.dtype == torch.int8:
+        frag = fused._split_jobs(list(w[1:6]), "tron_conv3x3_ws_split_weights", False)          # conv2 .. conv6, one launch
+        a, z = fused.conv1_px16_train(x, w[0], b[0], plane4)
     else:
-        out, z6 = fused.conv_ws_train(a5, 64, frag[4], b[5], residual=a4, want_f32=last_f32)
-    return out, (codes, a1.buf, a2.buf, a3.buf, a4.buf, a5.buf, z1.buf, z2.buf, z3.buf, z4.buf, z5.buf, z6.buf)
+        y1, z1 = fused.conv3x3_raw(x, w[0], b[0], None, act=True, want_pre=True)
+        a, z = fused.PX16.from_f32(y1), fused.PX16.from_f32(z1)
+        del y1, z1
+        frag = fused._split_jobs(list(w[1:6]), "tron_conv3x3_ws_split_weights", False)
+    acts, pres = [a], [z]                                                # a1 .., z1 ..
+    for k in range(1, 6):
+        _, cout, res = _TRUNK[k]
+        residual = None if res is None else acts[res - 1]
+        if k == 5 and end == "pool12":
+            a, z = fused.conv_ws_train_pool12(a, frag[k - 1], b[k], residual)
+        else:
+            a, z = fused.conv_ws_train(a, cout, frag[k - 1], b[k], residual=residual, want_f32=k == 5 and end == "f32")
+        if k < 5:
+            acts.append(a)
+        pres.append(z)
+    return a, acts, (x, *[t.buf for t in acts], *[t.buf for t in pres])
 
 
-def _trunk_px_backward(saved, w, plane4, gp6, gb6, need):
-    """The gradient chain below conv6's activation backward: gp6 = the gradient image at conv6's pre-activation, gb6 conv6's bias
-    gradient.  need[k]: conv(k+1)'s weight gradient is wanted.  Returns (gw[6], gb[6])."""
+def _px_backward(saved, w, plane4, top, want, want_input=False, on_grad=None):
+    """The gradient chain below conv6's activation backward, for what `_px_forward` saved: top = [the gradient image at conv6's
+    pre-activation, conv6's bias gradient] — a list, emptied here: an argument lives as long as the call, and the image is to go
+    when the chain is done with it.  Every input gradient is the weight-stationary kernel on the rotated weights
+    (residual gradient, mish' of the layer below, its bias sums and the next scale in the epilogue: tron_conv3x3_ws_dgrad), every
+    weight gradient comes straight from two PX16 images (tron_conv3x3_wgrad_px16).  want[k]: conv(k + 1)'s weight gradient is
+    wanted.  conv1's comes from the codes themselves (no f32 planes, no f32 gradient) or, behind f32 planes, from an f32
+    gradient that the last input-gradient launch then writes instead of an image; want_input: those planes' gradient as well.
+    on_grad(k, g): called with every layer's gradient as f32 (K-FAC's statistics: `TrunkHooks.grads`).
+    Returns (gw[6], gb[6], the planes' gradient or None)."""
     from Net import fused
-    codes, a1, a2, a3, a4, a5, z1, z2, z3, z4, z5, z6 = saved
-    B, S = gp6.shape[0], gp6.shape[-1]
+    x, acts, pres = saved[0], saved[1:6], saved[6:12]                    # a1 .. a5, z1 .. z6 (PX16 buffers)
+    gb6, gp = top.pop(), top.pop()
+    B, S = gp.shape[0], gp.shape[-1]
     px = lambda buf, c: fused._px((B, c, S, S), buf)
+    codes = x.dtype == torch.int8
+    stats = on_grad is not None
+    if stats:
+        on_grad(5, gp.float())
     rot, wn = fused._split_jobs(list(w[1:6]), "tron_conv3x3_ws_split_weights_bwd", True)      # conv2 .. conv6, one launch
     gb, gw = [None] * 6, [None] * 6
     gb[5] = gb6
-    gw[5] = fused.conv3x3_wgrad_px(px(a5, 64), gp6) if need[5] else None
-    gp5, _, gb[4] = fused.conv_ws_dgrad(gp6, 64, rot[4], wn[4:5], px(z5, 64))
-    gw[4] = fused.conv3x3_wgrad_px(px(a4, 64), gp5) if need[4] else None
-    gp4, _, gb[3] = fused.conv_ws_dgrad(gp5, 64, rot[3], wn[3:4], px(z4, 64), extra=gp6)      # a4 also feeds conv6's residual
-    del gp5, gp6
-    gw[3] = fused.conv3x3_wgrad_px(px(a3, 32), gp4) if need[3] else None
-    gp3, _, gb[2] = fused.conv_ws_dgrad(gp4, 32, rot[2], wn[2:3], px(z3, 32))
-    del gp4
-    gw[2] = fused.conv3x3_wgrad_px(px(a2, 32), gp3) if need[2] else None
-    gp2, _, gb[1] = fused.conv_ws_dgrad(gp3, 32, rot[1], wn[1:2], px(z2, 32))
-    gw[1] = fused.conv3x3_wgrad_px(px(a1, 32), gp2) if need[1] else None
-    gp1, _, gb[0] = fused.conv_ws_dgrad(gp2, 32, rot[0], wn[0:1], px(z1, 32), extra=gp3)    # a1 also feeds conv3's residual
-    del gp2, gp3
-    if need[0]:
-        gw[0] = fused.conv1_wgrad_px(codes, gp1, w[0].shape[1], plane4)       # from the codes themselves: no f32 planes, no f32 gradient
-    return gw, gb
+    held = {}                                                            # gradients on their way to the activation a residual link took
+    for k in range(5, 0, -1):                                            # conv(k + 1): gp is the gradient at its pre-activation
+        cin, _, res = _TRUNK[k]
+        if want[k]:
+            gw[k] = fused.conv3x3_wgrad_px(px(acts[k - 1], cin), gp)
+        if res is not None:
+            held[res] = gp
+        image = k > 1 or codes
+        gp, g32, gb[k - 1] = fused.conv_ws_dgrad(gp, cin, rot[k - 1], wn[k - 1:k], px(pres[k - 1], cin), extra=held.pop(k, None),
+                                                 want_px=image, want_f32=stats or not image)       # (frees what it replaces)
+        if stats:
+            on_grad(k - 1, g32)
+        if k > 1:
+            g32 = None                                                   # (an f32 image: gone before the next layer's launches)
+    gx = None
+    if codes:
+        if want[0]:
+            gw[0] = fused.conv1_wgrad_px(x, gp, w[0].shape[1], plane4)
+    else:                                                                # 3 or 4 planes in: cheap products in f32
+        if want[0]:
+            gw[0] = _conv3x3_wgrad(x, g32, w[0])
+        if want_input:                                                   # the planes asked for their gradient (saliency): the library
+            gx = _conv3x3_bwd_library(g32, x, w[0], True, False)[0]
+    return gw, gb, gx
 
 
 class _TrunkPX(torch.autograd.Function):
@@ -377,7 +414,7 @@ class _TrunkPX(torch.autograd.Function):
     @staticmethod
     def forward(ctx, codes, plane4, *wb):
         w, b = wb[0::2], wb[1::2]
-        out, saved = _trunk_px_forward(codes, plane4, w, b, True)
+        out, _, saved = _px_forward(codes, plane4, w, b, "f32")
         ctx.save_for_backward(*saved, *w)
         ctx.plane4 = plane4
         return out
@@ -385,19 +422,14 @@ class _TrunkPX(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         from Net import fused
-        *saved, w1, w2, w3, w4, w5, w6 = ctx.saved_tensors
-        g = grad_out.contiguous()
-        if not _aligned16(g):
-            g = g.clone(memory_format=torch.contiguous_format)
-        B, S = g.shape[0], g.shape[-1]
+        t = ctx.saved_tensors
+        saved, w = t[:12], t[12:]
+        g = _grad_in(grad_out)
         need = ctx.needs_input_grad                                 # (codes, plane4, w1, b1, ..., w6, b6)
-        gp6, gb6 = fused.grad_px_from_f32(g, fused._px((B, 64, S, S), saved[11]))
+        top = list(fused.grad_px_from_f32(g, fused._px(g.shape, saved[11])))
         del g
-        gw, gb = _trunk_px_backward(saved, (w1, w2, w3, w4, w5, w6), ctx.plane4, gp6, gb6, [need[2 + 2 * k] for k in range(6)])
-        grads = [None, None]
-        for k in range(6):
-            grads += [gw[k], gb[k] if need[3 + 2 * k] else None]
-        return tuple(grads)
+        gw, gb, _ = _px_backward(saved, w, ctx.plane4, top, need[2:14:2])
+        return (None, None, *_param_grads(gw, gb, need))
 
 
 class TrunkHooks:
@@ -436,86 +468,32 @@ class _ACTrunkPX(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, hooks, *wb):
-        from Net import fused
         w, b = wb[0::2], [t.reshape(-1) for t in wb[1::2]]
-        y1, z1f = fused.conv3x3_raw(x, w[0], b[0], None, act=True, want_pre=True)
-        a1, z1 = fused.PX16.from_f32(y1), fused.PX16.from_f32(z1f)
-        del y1, z1f
-        frag = fused._split_jobs(list(w[1:6]), "tron_conv3x3_ws_split_weights", False)
-        a2, z2 = fused.conv_ws_train(a1, 32, frag[0], b[1])
-        a3, z3 = fused.conv_ws_train(a2, 32, frag[1], b[2], residual=a1)
-        a4, z4 = fused.conv_ws_train(a3, 64, frag[2], b[3])
-        a5, z5 = fused.conv_ws_train(a4, 64, frag[3], b[4])
-        out, z6 = fused.conv_ws_train(a5, 64, frag[4], b[5], residual=a4, want_f32=True)
+        out, acts, saved = _px_forward(x, 0.0, w, b, "f32")
         if hooks is not None:
             like = x.new_empty((x.shape[0], 0))
             with torch.enable_grad():                               # (the hooks skip gradient-free forwards; a Function's forward runs as one)
-                for k, a in enumerate((x, a1, a2, a3, a4, a5)):
+                for k, a in enumerate((x, *acts)):
                     hooks.inputs(k, a, like)
-        ctx.save_for_backward(x, a1.buf, a2.buf, a3.buf, a4.buf, a5.buf, z1.buf, z2.buf, z3.buf, z4.buf, z5.buf, z6.buf, *w)
+        ctx.save_for_backward(*saved, *w)
         ctx.hooks, ctx.bias_shapes, ctx.grad_scope = hooks, [tuple(t.shape) for t in wb[1::2]], _current_scope()
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         from Net import fused
-        x, a1, a2, a3, a4, a5, z1, z2, z3, z4, z5, z6, *w = ctx.saved_tensors
-        g = grad_out.contiguous()
-        if not _aligned16(g):
-            g = g.clone(memory_format=torch.contiguous_format)
-        B, S = g.shape[0], g.shape[-1]
-        px = lambda buf, c: fused._px((B, c, S, S), buf)
+        t = ctx.saved_tensors
+        saved, w = t[:12], t[12:]
+        g = _grad_in(grad_out)
         need = ctx.needs_input_grad                                 # (x, hooks, w1, b1, ..., w6, b6)
         skip = _skips_weight_gradient(ctx)                          # the sampled-Fisher pass: statistics only
-        want = lambda k: need[2 + 2 * k] and not skip
+        want = [need[2]] + [n and not skip for n in need[4:14:2]]   # (conv1's weight: a cheap product, also in the statistics pass)
         hooks = ctx.hooks
         stats = hooks is not None and hooks.wants_grads()
-        gp6, gb6 = fused.grad_px_from_f32(g, px(z6, 64))
+        top = list(fused.grad_px_from_f32(g, fused._px(g.shape, saved[11])))
         del g
-        if stats:
-            hooks.grads(5, gp6.float())
-        rot, wn = fused._split_jobs(list(w[1:6]), "tron_conv3x3_ws_split_weights_bwd", True)
-        gw, gb = [None] * 6, [None] * 6
-        gb[5] = gb6
-        gw[5] = fused.conv3x3_wgrad_px(px(a5, 64), gp6) if want(5) else None
-        gp5, f5, gb[4] = fused.conv_ws_dgrad(gp6, 64, rot[4], wn[4:5], px(z5, 64), want_f32=stats)
-        if stats:
-            hooks.grads(4, f5)
-        del f5
-        gw[4] = fused.conv3x3_wgrad_px(px(a4, 64), gp5) if want(4) else None
-        gp4, f4, gb[3] = fused.conv_ws_dgrad(gp5, 64, rot[3], wn[3:4], px(z4, 64), extra=gp6, want_f32=stats)   # a4 also feeds conv6's residual
-        del gp5, gp6
-        if stats:
-            hooks.grads(3, f4)
-        del f4
-        gw[3] = fused.conv3x3_wgrad_px(px(a3, 32), gp4) if want(3) else None
-        gp3, f3, gb[2] = fused.conv_ws_dgrad(gp4, 32, rot[2], wn[2:3], px(z3, 32), want_f32=stats)
-        del gp4
-        if stats:
-            hooks.grads(2, f3)
-        del f3
-        gw[2] = fused.conv3x3_wgrad_px(px(a2, 32), gp3) if want(2) else None
-        gp2, f2, gb[1] = fused.conv_ws_dgrad(gp3, 32, rot[1], wn[1:2], px(z2, 32), want_f32=stats)
-        if stats:
-            hooks.grads(1, f2)
-        del f2
-        gw[1] = fused.conv3x3_wgrad_px(px(a1, 32), gp2) if want(1) else None
-        _, f1, gb[0] = fused.conv_ws_dgrad(gp2, 32, rot[0], wn[0:1], px(z1, 32), extra=gp3, want_px=False, want_f32=True)   # a1 also feeds conv3's residual
-        del gp2, gp3
-        if stats:
-            hooks.grads(0, f1)
-        if need[2]:                                                 # conv1's weight (3 or 4 planes in: a cheap product, also in the statistics pass)
-            if fused.wgrad_supported(w[0], S):
-                gw[0] = fused.conv3x3_wgrad(x, f1)
-            else:
-                gw[0] = torch.ops.aten.convolution_backward(f1, x, w[0], None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1, [False, True, False])[1]
-        gx = None
-        if need[0]:                                                 # the planes asked for their gradient (saliency): the library
-            gx = torch.ops.aten.convolution_backward(f1, x, w[0], None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1, [True, False, False])[0]
-        grads = [gx, None]
-        for k in range(6):
-            grads += [gw[k], gb[k].reshape(ctx.bias_shapes[k]) if need[3 + 2 * k] else None]
-        return tuple(grads)
+        gw, gb, gx = _px_backward(saved, w, 0.0, top, want, want_input=need[0], on_grad=hooks.grads if stats else None)
+        return (gx, None, *_param_grads(gw, gb, need, ctx.bias_shapes))
 
 
 def ac_trunk_infer(x, weights, biases):
@@ -524,29 +502,27 @@ def ac_trunk_infer(x, weights, biases):
     activations as PX16 images, conv6 writing f32 for the pooling.  The caller checked ac_trunk_px_supported(..., need_grad=False)."""
     from Net import fused
     b = [t.reshape(-1) for t in biases]
-    a1 = fused.PX16.from_f32(fused.conv3x3_raw(x, weights[0], b[0], None, act=True))
+    a = fused.PX16.from_f32(fused.conv3x3_raw(x, weights[0], b[0], None, act=True))
     frag = fused._split_jobs(list(weights[1:6]), "tron_conv3x3_ws_split_weights", False)
-    a2 = fused.conv_ws_infer(a1, 32, frag[0], b[1])
-    a3 = fused.conv_ws_infer(a2, 32, frag[1], b[2], residual=a1)
-    del a1, a2
-    a4 = fused.conv_ws_infer(a3, 64, frag[2], b[3])
-    del a3
-    a5 = fused.conv_ws_infer(a4, 64, frag[3], b[4])
-    return fused.conv_ws_infer(a5, 64, frag[4], b[5], residual=a4, want_f32=True)
+    held = {}                                                       # activations a residual link still waits for: every other image
+    for k in range(1, 6):                                           # goes as soon as its layer has run (4 bytes per element)
+        _, cout, res = _TRUNK[k]
+        if k in _RESIDUAL_SOURCES:
+            held[k] = a
+        a = fused.conv_ws_infer(a, cout, frag[k - 1], b[k], residual=None if res is None else held.pop(res), want_f32=k == 5)
+    return a
 
 
 def ac_trunk_px_supported(x, weights, need_grad=True):
     """Can `_ACTrunkPX` (need_grad) / `ac_trunk_infer` run conv1 .. conv6 (weights: the six convolution weights) on the f32 planes x?"""
     from Net import fused
-    import os
     if os.environ.get("TRON_AC_TRUNK_PX", "1") == "0" or not fused.use_trunk_px:
         return False
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] > 0 and x.shape[-1] == x.shape[-2] and x.shape[-1] in (12, 26, 34)
             and x.shape[1] in (3, 4) and _aligned16(x) and torch.is_grad_enabled() == need_grad and fused.default_math == "f16x3"
             and bias_mish_supported(x)):                     # (the switch the tests use to get the module-by-module graph)
         return False
-    chans = [(w.shape[1], w.shape[0]) for w in weights]
-    return (chans == [(x.shape[1], 32), (32, 32), (32, 32), (32, 64), (64, 64), (64, 64)]
+    return ([(w.shape[1], w.shape[0]) for w in weights] == [(x.shape[1], _TRUNK[0][1])] + _TRUNK_CHANNELS
             and all(tuple(w.shape[2:]) == (3, 3) and w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() for w in weights))
 
 
@@ -564,24 +540,19 @@ class _BodyPX(torch.autograd.Function):
         from Net import fused
         L = nat.lib()
         w, b = wb[0::2], wb[1::2]
-        a6, saved = _trunk_px_forward(codes, plane4, w, b, False, pooled12=True)
         B, S = codes.shape[0], codes.shape[-1]
+        pool_fused = fused.use_pool_fused_train and S == 12 and B > 0            # conv6 and the pooling as one launch
+        a6, _, saved = _px_forward(codes, plane4, w, b, "pool12" if pool_fused else "px16")
         dev = codes.device
         st = nat.stream_ptr()
         with torch.cuda.device(dev):
             if S == 12:
-                if torch.is_tensor(a6):                                   # conv6 and the pooling were one launch
+                if pool_fused:
                     pooled = a6
                 else:
                     pooled = torch.empty(B, 64 * 36, dtype=torch.float32, device=dev)
                     nat.check(L.tron_pool12_px16(nat.ptr(a6.buf), nat.ptr(pooled), B, st), "tron_pool12_px16")
-                dense = torch.empty(64 * 9, 64 * 36, dtype=torch.float32, device=dev)
-                nat.check(L.tron_conv7_dense(nat.ptr(w[6]), nat.ptr(dense), 64, 64, 0, st), "tron_conv7_dense")
-                pre = fused.gemm_f16x3(pooled, dense, b[6].repeat_interleave(9))
-                if pre is None:
-                    pre = torch.addmm(b[6].repeat_interleave(9), pooled, dense.t())
-                y = torch.empty_like(pre)
-                nat.check(L.tron_mish_fwd(nat.ptr(pre), nat.ptr(y), pre.numel(), st), "tron_mish_fwd")
+                y, dense, pre = _conv7_dense_fwd(pooled, w[6], b[6])
                 extra = (pooled, dense, pre)
             else:
                 o = (S // 2 + 1) // 2
@@ -605,32 +576,14 @@ class _BodyPX(torch.autograd.Function):
         t = ctx.saved_tensors
         saved, w, extra = t[:12], t[12:19], t[19:]
         S = ctx.side
-        g = grad_out.contiguous()
-        if not _aligned16(g):
-            g = g.clone(memory_format=torch.contiguous_format)
+        g = _grad_in(grad_out)
         B = g.shape[0]
         dev = g.device
         need = ctx.needs_input_grad                                 # (codes, plane4, w1, b1, ..., w7, b7)
         st = nat.stream_ptr()
-        gw7 = gb7 = None
         with torch.cuda.device(dev):
             if S == 12:
-                pooled, dense, pre = extra
-                gp = torch.empty_like(pre)
-                nat.check(L.tron_mish_bwd(nat.ptr(pre), nat.ptr(g), nat.ptr(gp), pre.numel(), st), "tron_mish_bwd")
-                from Net.kfac import _pow2_scale
-                sc = _pow2_scale(gp) if fused.use_gemm else None
-                gpool = fused.gemm_f16x3(gp, dense, b_transposed=True, a_scale=sc)           # [B, 64 * 36]: the pooled planes' gradient
-                if gpool is None:
-                    gpool = gp @ dense
-                if need[14]:
-                    gdense = fused.gemm_f16x3(gp, pooled, a_transposed=True, b_transposed=True, a_scale=sc)
-                    if gdense is None:
-                        gdense = gp.t() @ pooled
-                    gw7 = torch.empty(64, 64, 7, 7, dtype=torch.float32, device=dev)
-                    nat.check(L.tron_conv7_dense(nat.ptr(gdense), nat.ptr(gw7), 64, 64, 1, st), "tron_conv7_dense")
-                if need[15]:
-                    gb7 = gp.view(B, 64, 9).sum((0, 2))
+                gpool, gw7, gb7 = _conv7_dense_bwd(g, *extra, True, need[14], need[15])      # (the pooled gradient: always)
                 channels_last = 0
             else:
                 keep, pre = extra
@@ -643,18 +596,14 @@ class _BodyPX(torch.autograd.Function):
                 channels_last = 1
             # pooling backward + conv6's activation backward + bias sums + the gradient image, one pass over the pooled gradient
             sc4 = torch.zeros(4, dtype=torch.float32, device=dev)
-            gp6 = fused.GradPX(B, 64, S, dev)
-            gb6 = torch.empty(64, dtype=torch.float32, device=dev)
+            top = [fused.GradPX(B, 64, S, dev), torch.empty(64, dtype=torch.float32, device=dev)]   # conv6's: gradient image, bias gradient
             gws = torch.empty(int(L.tron_px16_grad_workspace(B, 64)), dtype=torch.uint8, device=dev)
             nat.check(L.tron_absmax_pow2(nat.ptr(gpool), gpool.numel(), 15, nat.ptr(sc4), st), "tron_absmax_pow2")
-            nat.check(L.tron_px16_grad_from_pooled(nat.ptr(gpool), channels_last, nat.ptr(saved[11]), nat.ptr(sc4), B, 64, S, nat.ptr(gp6.buf),
-                                                   nat.ptr(gp6.info), nat.ptr(gb6), nat.ptr(gws), st), "tron_px16_grad_from_pooled")
+            nat.check(L.tron_px16_grad_from_pooled(nat.ptr(gpool), channels_last, nat.ptr(saved[11]), nat.ptr(sc4), B, 64, S, nat.ptr(top[0].buf),
+                                                   nat.ptr(top[0].info), nat.ptr(top[1]), nat.ptr(gws), st), "tron_px16_grad_from_pooled")
         del g, gpool
-        gw, gb = _trunk_px_backward(saved, w[:6], ctx.plane4, gp6, gb6, [need[2 + 2 * k] for k in range(6)])
-        grads = [None, None]
-        for k in range(6):
-            grads += [gw[k], gb[k] if need[3 + 2 * k] else None]
-        return tuple(grads + [gw7, gb7])
+        gw, gb, _ = _px_backward(saved, w[:6], ctx.plane4, top, need[2:14:2])
+        return (None, None, *_param_grads(gw, gb, need), gw7, gb7)
 
 
 def trunk_px_supported(net, x):
@@ -662,8 +611,7 @@ def trunk_px_supported(net, x):
     from Net import fused
     return (fused.use_trunk_px and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.int8 and x.dim() == 3 and x.numel() > 0
             and fused.default_math == "f16x3" and fused.ws_supported(net, x.shape[-1]) and x.shape[-2] == x.shape[-1]
-            and [(c.in_channels, c.out_channels) for c in (net.conv2, net.conv3, net.conv4, net.conv5, net.conv6)]
-            == [(32, 32), (32, 32), (32, 64), (64, 64), (64, 64)])
+            and [(c.in_channels, c.out_channels) for c in (net.conv2, net.conv3, net.conv4, net.conv5, net.conv6)] == _TRUNK_CHANNELS)
 
 
 def trunk_supported(net, x):
@@ -679,8 +627,7 @@ def trunk_supported(net, x):
     elif not (x.dtype == torch.float32 and x.dim() == 4 and x.shape[-2] == side and x.shape[1] == net.conv1.in_channels
               and net.conv1.in_channels in (3, 4) and _aligned16(x)):
         return False
-    chans = [(c.in_channels, c.out_channels) for c in convs[1:]]
-    return (chans == [(32, 32), (32, 32), (32, 64), (64, 64), (64, 64)] and net.conv1.out_channels == 32
+    return ([(c.in_channels, c.out_channels) for c in convs[1:]] == _TRUNK_CHANNELS and net.conv1.out_channels == _TRUNK[0][1]
             and all(c.bias is not None and fused.supported(c, side) for c in convs)
             and all(fused.dgrad_mish_supported(c.weight, side) for c in convs[1:]))
 
@@ -688,29 +635,23 @@ def trunk_supported(net, x):
 def body_px_supported(net, x):
     """Can `_BodyPX` run conv1 .. conv7 of `net` on the codes x?  `_TrunkPX`'s shapes, the reference's pooling and conv7 (64 -> 64,
     7x7 / 2 / 3: DQNNet.py:20-22) and mish as the activation."""
-    from Net import fused
     pool, conv = getattr(net, "pool", None), getattr(net, "conv7", None)
-    return (trunk_px_supported(net, x) and _use_pool_conv7_cl and isinstance(pool, torch.nn.AvgPool2d) and pool.kernel_size == 3
-            and pool.stride == 2 and pool.padding == 1 and pool.count_include_pad and not pool.ceil_mode and pool.divisor_override is None
-            and isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (7, 7) and conv.stride == (2, 2) and conv.padding == (3, 3)
-            and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is not None and conv.in_channels == 64 and conv.out_channels == 64
-            and conv.weight.is_contiguous() and conv.weight.dtype == torch.float32 and conv.weight.is_cuda
-            and _os.environ.get("TRON_BODY_PX", "1") != "0")
+    return (trunk_px_supported(net, x) and _use_pool_conv7_cl and _is_ref_pool(pool) and _is_ref_conv7(conv)
+            and conv.in_channels == 64 and conv.out_channels == 64
+            and conv.weight.is_cuda                          # (historical: the other conv7 predicates take the weight's device on trust)
+            and os.environ.get("TRON_BODY_PX", "1") != "0")
 
 
 def body_mish(net, codes, plane4=0.0):
     """mish(conv7(pool(trunk(codes)))) flattened [B, 64 * O * O] (DQNNet.py:33-55) as one node (`_BodyPX`)."""
-    wb = []
-    for c in (net.conv1, net.conv2, net.conv3, net.conv4, net.conv5, net.conv6, net.conv7):
-        wb += [c.weight, c.bias]
+    wb = _conv_params((net.conv1, net.conv2, net.conv3, net.conv4, net.conv5, net.conv6, net.conv7))
     return _BodyPX.apply(codes.contiguous(), float(plane4), *wb)
 
 
 def trunk_mish(net, x, plane4=0.0):
-    """mish-activated conv1..conv6 of a DQN `Net` (DQNNet.py:33-50) with autograd, as one node (`_TrunkHIP`)."""
-    wb = []
-    for c in (net.conv1, net.conv2, net.conv3, net.conv4, net.conv5, net.conv6):
-        wb += [c.weight, c.bias]
+    """mish-activated conv1..conv6 of a DQN `Net` (DQNNet.py:33-50) with autograd, as one node: `_TrunkPX` (the weight-stationary
+    chain) for the int8 codes it covers, `_TrunkHIP` (the f32 layer kernels) for f32 planes and everything else."""
+    wb = _conv_params((net.conv1, net.conv2, net.conv3, net.conv4, net.conv5, net.conv6))
     if trunk_px_supported(net, x):
         return _TrunkPX.apply(x.contiguous(), float(plane4), *wb)
     return _TrunkHIP.apply(x.contiguous(), float(plane4), *wb)
@@ -749,12 +690,8 @@ class _BiasMish(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from tron import _native as nat
         (pre,) = ctx.saved_tensors
-        g = grad_out.contiguous()
-        if not _aligned16(g):
-            g = g.clone(memory_format=torch.contiguous_format)
-        gp, gb = bias_mish_bwd(pre, g)
+        gp, gb = bias_mish_bwd(pre, _grad_in(grad_out))
         if ctx.grad_pre_hook is not None:
             ctx.grad_pre_hook(gp)
         return gp, gb.reshape(ctx.bias_shape), (gp if ctx.has_res else None), None
@@ -771,68 +708,81 @@ def bias_mish(y, bias, residual=None, grad_pre_hook=None):
     return _BiasMish.apply(y, bias, residual, grad_pre_hook)
 
 
+def _conv7_dense_fwd(pooled, weight, bias):
+    """mish(conv7(pooled)) for 6x6 pooled planes [B, Ci*36]: there the 7x7 / stride 2 / pad 3 convolution is the dense map
+    [Ci*36] -> [Co*9] (most taps fall on padding), one GEMM on the matrix csrc/tron_head.hip builds from the weight
+    (tron_conv7_dense).  Returns (the output [B, Co*9], the dense matrix, the pre-activation); the caller has set the device."""
+    from Net import fused
+    nat = fused.nat
+    L = nat.lib()
+    Co, C = weight.shape[0], weight.shape[1]
+    st = nat.stream_ptr()
+    dense = torch.empty(Co * 9, C * 36, dtype=torch.float32, device=pooled.device)
+    nat.check(L.tron_conv7_dense(nat.ptr(weight), nat.ptr(dense), Co, C, 0, st), "tron_conv7_dense")
+    pre = fused.gemm_f16x3(pooled, dense, bias.repeat_interleave(9))                # [B, Ci*36] x [Co*9, Ci*36]^T
+    if pre is None:
+        pre = torch.addmm(bias.repeat_interleave(9), pooled, dense.t())
+    out = torch.empty_like(pre)
+    nat.check(L.tron_mish_fwd(nat.ptr(pre), nat.ptr(out), pre.numel(), st), "tron_mish_fwd")
+    return out, dense, pre
+
+
+def _conv7_dense_bwd(g, pooled, dense, pre, want_pooled, want_weight, want_bias, unpool=None):
+    """The backward of `_conv7_dense_fwd`: two more GEMMs on the dense matrix, the weight's folded back into [Co, Ci, 7, 7].
+    Returns (the pooled planes' gradient [B, Ci*36] if want_pooled — with unpool = the planes' shape [B, Ci, 12, 12]: taken
+    through the pooling's backward, tron_pool12, to that shape —, weight gradient, bias gradient), None for what was not asked;
+    the caller has set the device."""
+    from Net import fused, kfac
+    nat = fused.nat
+    L = nat.lib()
+    B, Co, C = pre.shape[0], dense.shape[0] // 9, dense.shape[1] // 36
+    st = nat.stream_ptr()
+    gx = gw = gb = None
+    gp = torch.empty_like(pre)
+    nat.check(L.tron_mish_bwd(nat.ptr(pre), nat.ptr(g), nat.ptr(gp), pre.numel(), st), "tron_mish_bwd")
+    sc = kfac._pow2_scale(gp) if fused.use_gemm else None                    # the gradient's scale on its way into f16 (a device scalar)
+    if want_pooled:
+        gx = gpool = fused.gemm_f16x3(gp, dense, b_transposed=True, a_scale=sc)     # gp [B, Co*9] x dense [Co*9, Ci*36]
+        if gpool is None:
+            gx = gpool = gp @ dense
+        if unpool is not None:
+            gx = torch.empty(unpool, dtype=torch.float32, device=pre.device)
+            nat.check(L.tron_pool12(nat.ptr(gpool), nat.ptr(gx), B * C, 1, st), "tron_pool12")
+    if want_weight:
+        gdense = fused.gemm_f16x3(gp, pooled, a_transposed=True, b_transposed=True, a_scale=sc)   # gp^T [Co*9, B] x pooled [B, Ci*36]
+        if gdense is None:
+            gdense = gp.t() @ pooled
+        gw = torch.empty(Co, C, 7, 7, dtype=torch.float32, device=pre.device)
+        nat.check(L.tron_conv7_dense(nat.ptr(gdense), nat.ptr(gw), Co, C, 1, st), "tron_conv7_dense")
+    if want_bias:
+        gb = gp.view(B, Co, 9).sum((0, 2))
+    return gx, gw, gb
+
+
 class _PoolConv7(torch.autograd.Function):
-    """mish(conv7(avg_pool(x))) flattened, for 12x12 planes (Net/DQNNet.py:52-55): on the 6x6 pooled planes the 7x7 /
-    stride 2 / pad 3 convolution is the dense map [Ci*36] -> [Co*9] (most taps fall on padding), so forward, input
-    gradient and weight gradient are three plain f32 GEMMs on the matrix csrc/tron_head.hip builds from the weight
-    (tron_conv7_dense) and folds its gradient back into; pooling forward / backward are tron_pool12.  Replaces MIOpen's
-    conv7 kernels + their NCHW<->NHWC transposes + torch's avg_pool2d backward (1.1 ms -> 0.45 ms at 4 096 samples)."""
+    """mish(conv7(avg_pool(x))) flattened, for 12x12 planes (Net/DQNNet.py:52-55): conv7 on its dense form — forward, input
+    gradient and weight gradient are three plain f32 GEMMs (`_conv7_dense_fwd` / `_bwd`) —, pooling forward / backward are
+    tron_pool12.  Replaces MIOpen's conv7 kernels + their NCHW<->NHWC transposes + torch's avg_pool2d backward (1.1 ms ->
+    0.45 ms at 4 096 samples)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
         from tron import _native as nat
-        L = nat.lib()
         B, C = x.shape[0], x.shape[1]
-        Co = weight.shape[0]
-        st = nat.stream_ptr()
         with torch.cuda.device(x.device):
             pooled = torch.empty(B, C * 36, dtype=torch.float32, device=x.device)
-            nat.check(L.tron_pool12(nat.ptr(x), nat.ptr(pooled), B * C, 0, st), "tron_pool12")
-            dense = torch.empty(Co * 9, C * 36, dtype=torch.float32, device=x.device)
-            nat.check(L.tron_conv7_dense(nat.ptr(weight), nat.ptr(dense), Co, C, 0, st), "tron_conv7_dense")
-            from Net import fused
-            pre = fused.gemm_f16x3(pooled, dense, bias.repeat_interleave(9))            # [B, Ci*36] x [Co*9, Ci*36]^T
-            if pre is None:
-                pre = torch.addmm(bias.repeat_interleave(9), pooled, dense.t())
-            out = torch.empty_like(pre)
-            nat.check(L.tron_mish_fwd(nat.ptr(pre), nat.ptr(out), pre.numel(), st), "tron_mish_fwd")
+            nat.check(nat.lib().tron_pool12(nat.ptr(x), nat.ptr(pooled), B * C, 0, nat.stream_ptr()), "tron_pool12")
+            out, dense, pre = _conv7_dense_fwd(pooled, weight, bias)
         ctx.save_for_backward(pooled, dense, pre)
         ctx.shape = tuple(x.shape)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        from tron import _native as nat
-        L = nat.lib()
         pooled, dense, pre = ctx.saved_tensors
-        B, C = ctx.shape[0], ctx.shape[1]
-        Co = dense.shape[0] // 9
-        g = grad_out.contiguous()
-        if not _aligned16(g):
-            g = g.clone(memory_format=torch.contiguous_format)
-        st = nat.stream_ptr()
-        gx = gw = gb = None
-        with torch.cuda.device(pre.device):
-            gp = torch.empty_like(pre)
-            nat.check(L.tron_mish_bwd(nat.ptr(pre), nat.ptr(g), nat.ptr(gp), pre.numel(), st), "tron_mish_bwd")
-            from Net import fused
-            from Net.kfac import _pow2_scale
-            sc = _pow2_scale(gp) if fused.use_gemm else None                # the gradient's scale on its way into f16 (a device scalar)
-            if ctx.needs_input_grad[0]:
-                gpool = fused.gemm_f16x3(gp, dense, b_transposed=True, a_scale=sc)       # gp [B, Co*9] x dense [Co*9, Ci*36]
-                if gpool is None:
-                    gpool = gp @ dense
-                gx = torch.empty(ctx.shape, dtype=torch.float32, device=pre.device)
-                nat.check(L.tron_pool12(nat.ptr(gpool), nat.ptr(gx), B * C, 1, st), "tron_pool12")
-            if ctx.needs_input_grad[1]:
-                gdense = fused.gemm_f16x3(gp, pooled, a_transposed=True, b_transposed=True, a_scale=sc)   # gp^T [Co*9, B] x pooled [B, Ci*36]
-                if gdense is None:
-                    gdense = gp.t() @ pooled
-                gw = torch.empty(Co, C, 7, 7, dtype=torch.float32, device=pre.device)
-                nat.check(L.tron_conv7_dense(nat.ptr(gdense), nat.ptr(gw), Co, C, 1, st), "tron_conv7_dense")
-            if ctx.needs_input_grad[2]:
-                gb = gp.view(B, Co, 9).sum((0, 2))
-        return gx, gw, gb
+        g = _grad_in(grad_out)
+        with torch.cuda.device(pre.device):                              # (the pooled gradient only on its way to the planes')
+            return _conv7_dense_bwd(g, pooled, dense, pre, *ctx.needs_input_grad, unpool=ctx.shape)
 
 
 class _PoolConv7CL(torch.autograd.Function):
@@ -867,9 +817,7 @@ class _PoolConv7CL(torch.autograd.Function):
         L = nat.lib()
         saved, pre, weight = ctx.saved_tensors
         B, side = ctx.geometry
-        g = grad_out.contiguous()
-        if not _aligned16(g):
-            g = g.clone(memory_format=torch.contiguous_format)
+        g = _grad_in(grad_out)
         dev = pre.device
         gx = gw = gb = None
         with torch.cuda.device(dev):
@@ -913,9 +861,7 @@ class _Conv7HIP(torch.autograd.Function):
         L = nat.lib()
         saved, weight = ctx.saved_tensors
         B, ps = ctx.geometry
-        g = grad_out.contiguous()
-        if not _aligned16(g):
-            g = g.clone(memory_format=torch.contiguous_format)
+        g = _grad_in(grad_out)
         dev = g.device
         gx = gw = gb = None
         with torch.cuda.device(dev):
@@ -939,8 +885,7 @@ class Conv7(torch.nn.Conv2d):
     def forward(self, x):
         if (_use_pool_conv7_cl and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[-1] == x.shape[-2]
                 and x.shape[-1] in (13, 17) and 0 < x.shape[0] <= (1 << 20) and x.shape[1] == 64 and self.in_channels == 64
-                and self.out_channels == 64 and self.kernel_size == (7, 7) and self.stride == (2, 2) and self.padding == (3, 3)
-                and self.dilation == (1, 1) and self.groups == 1 and self.weight.dtype == torch.float32 and self.weight.is_contiguous()):
+                and self.out_channels == 64 and _is_ref_conv7(self, need_bias=False)):   # (KFACOptimizer splits the bias off: none left)
             from Net import fused
             if fused.default_math == "f16x3":
                 x = x.contiguous()
@@ -962,34 +907,33 @@ class _LinearHIP(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from tron import _native as nat
         x, weight = ctx.saved_tensors
         gy = gy.contiguous()
         gx = gy @ weight if ctx.needs_input_grad[0] else None
         gw = gb = None
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            B, O, I = x.shape[0], weight.shape[0], weight.shape[1]
-            L = nat.lib()
-            from Net import fused
-            if O * I >= _LIN_WGRAD_GEMM and fused.use_gemm:              # (as `_TailMLP`: large layers on the split-f16 GEMM)
-                from Net.kfac import _pow2_scale
-                gw = fused.gemm_f16x3(gy, x, a_transposed=True, b_transposed=True, a_scale=_pow2_scale(gy))
-                if gw is not None:
-                    return gx, gw, (gy.sum(0) if ctx.has_bias else None)
-            gw = torch.empty_like(weight)
-            gb = torch.empty(O, dtype=torch.float32, device=x.device) if ctx.has_bias else None
-            ws = torch.empty(max(16, int(L.tron_linear_wgrad_workspace(B, O, I))), dtype=torch.uint8, device=x.device)
             with torch.cuda.device(x.device):
-                nat.check(L.tron_linear_wgrad(nat.ptr(gy), nat.ptr(x), B, O, I, nat.ptr(gw), nat.ptr(gb), nat.ptr(ws), nat.stream_ptr()),
-                          "tron_linear_wgrad")
+                gw, gb = _linear_wgrad(gy, x, weight, ctx.has_bias)
         return gx, gw, gb
 
 
-import os as _os
-_use_linear_hip = _os.environ.get("TRON_LINEAR_HIP", "1") != "0"           # 0: the library's weight-gradient GEMMs (A/B measurements)
-# tron_linear_wgrad is plain f32 FMAs on 64 x 64 tiles: right for the head's small layers (<= 150 K outputs), 239 us for fc1 behind
-# 24x24 boards (256 x 3136 outputs over a batch of 4 096: 6.6 GFLOP) — from this many outputs on the weight gradient is tron_gemm_f16x3
-_LIN_WGRAD_GEMM = int(_os.environ.get("TRON_LIN_WGRAD_GEMM", str(1 << 19)))
+def _linear_wgrad(gy, x, weight, has_bias=True):
+    """(weight gradient, bias gradient or None) of a linear layer from the gradient at its output gy [B, O] and its input x [B, I]:
+    one launch pair of csrc/tron_dqn.hip (tron_linear_wgrad: the batch split over workgroups); from `_LIN_WGRAD_GEMM` outputs on
+    (fc1 behind 24x24 boards, 256 x 3136) the split-f16 GEMM, the bias sum apart.  The caller has set the device."""
+    from Net import fused, kfac
+    nat = fused.nat
+    B, (O, I) = x.shape[0], weight.shape
+    if O * I >= _LIN_WGRAD_GEMM and fused.use_gemm:
+        gw = fused.gemm_f16x3(gy, x, a_transposed=True, b_transposed=True, a_scale=kfac._pow2_scale(gy))
+        if gw is not None:
+            return gw, (gy.sum(0) if has_bias else None)
+    L = nat.lib()
+    gw = torch.empty_like(weight)
+    gb = torch.empty(O, dtype=torch.float32, device=x.device) if has_bias else None
+    ws = torch.empty(max(16, int(L.tron_linear_wgrad_workspace(B, O, I))), dtype=torch.uint8, device=x.device)
+    nat.check(L.tron_linear_wgrad(nat.ptr(gy), nat.ptr(x), B, O, I, nat.ptr(gw), nat.ptr(gb), nat.ptr(ws), nat.stream_ptr()), "tron_linear_wgrad")
+    return gw, gb
 
 
 def linear(layer, x):
@@ -1037,25 +981,11 @@ class _TailMLP(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gq):
         from tron import _native as nat
-        from Net import fused
         L = nat.lib()
         x, y1, d1, y2, d2, y3, a3, w1, w2, w3, w4, *masks = ctx.saved_tensors
         dev = x.device
         need = ctx.needs_input_grad                 # (x, p, training, w1, b1, ..., w4, b4)
-        B = x.shape[0]
         gq = gq.contiguous()
-
-        def wgrad(gy, inp, w):
-            O, I = w.shape
-            if O * I >= _LIN_WGRAD_GEMM and fused.use_gemm:    # fc1 behind 24x24 boards (256 x 3136): the split-f16 GEMM, the bias sum apart
-                from Net.kfac import _pow2_scale
-                gw = fused.gemm_f16x3(gy, inp, a_transposed=True, b_transposed=True, a_scale=_pow2_scale(gy))
-                if gw is not None:
-                    return gw, gy.sum(0)
-            gw, gb = torch.empty_like(w), torch.empty(O, dtype=torch.float32, device=dev)
-            ws = torch.empty(max(16, int(L.tron_linear_wgrad_workspace(B, O, I))), dtype=torch.uint8, device=dev)
-            nat.check(L.tron_linear_wgrad(nat.ptr(gy), nat.ptr(inp), B, O, I, nat.ptr(gw), nat.ptr(gb), nat.ptr(ws), nat.stream_ptr()), "tron_linear_wgrad")
-            return gw, gb
 
         def act_bwd(y, g):
             gy = torch.empty_like(y)
@@ -1063,15 +993,15 @@ class _TailMLP(torch.autograd.Function):
             return gy
         scale = 1.0 / (1.0 - ctx.p) if ctx.drop else 1.0
         with torch.cuda.device(dev):
-            gw4, gb4 = wgrad(gq, a3, w4)
+            gw4, gb4 = _linear_wgrad(gq, a3, w4)
             gy3 = act_bwd(y3, gq @ w4)
-            gw3, gb3 = wgrad(gy3, d2, w3)
+            gw3, gb3 = _linear_wgrad(gy3, d2, w3)
             g2 = gy3 @ w3
             gy2 = act_bwd(y2, torch._masked_scale(g2, masks[1], scale) if ctx.drop else g2)
-            gw2, gb2 = wgrad(gy2, d1, w2)
+            gw2, gb2 = _linear_wgrad(gy2, d1, w2)
             g1 = gy2 @ w2
             gy1 = act_bwd(y1, torch._masked_scale(g1, masks[0], scale) if ctx.drop else g1)
-            gw1, gb1 = wgrad(gy1, x, w1)
+            gw1, gb1 = _linear_wgrad(gy1, x, w1)
             gx = gy1 @ w1 if need[0] else None
         return gx, None, None, gw1, gb1, gw2, gb2, gw3, gb3, gw4, gb4
 
@@ -1115,20 +1045,30 @@ class _PoolS2(torch.autograd.Function):
     def backward(ctx, grad_y):
         from tron import _native as nat
         N, C, S = ctx.shape
-        g = grad_y.contiguous()
-        if not _aligned16(g):
-            g = g.clone(memory_format=torch.contiguous_format)
+        g = _grad_in(grad_y)
         gx = torch.empty(N, C, S, S, dtype=torch.float32, device=g.device)
         with torch.cuda.device(g.device):
             nat.check(nat.lib().tron_pool_s2_bwd(nat.ptr(g), nat.ptr(gx), N * C, S, nat.stream_ptr()), "tron_pool_s2_bwd")
         return gx
 
 
+def _is_ref_pool(pool):
+    """The reference's pooling: AvgPool2d(kernel_size=3, padding=1, stride=2) as DQNNet.py:20 builds it."""
+    return (isinstance(pool, torch.nn.AvgPool2d) and pool.kernel_size == 3 and pool.stride == 2 and pool.padding == 1
+            and pool.count_include_pad and not pool.ceil_mode and pool.divisor_override is None)
+
+
+def _is_ref_conv7(conv, need_bias=True):
+    """The reference's conv7 geometry (7x7 / stride 2 / pad 3: DQNNet.py:22) with a bias and a contiguous f32 weight; the channel
+    counts are the caller's to ask."""
+    return (isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (7, 7) and conv.stride == (2, 2) and conv.padding == (3, 3)
+            and conv.dilation == (1, 1) and conv.groups == 1 and (conv.bias is not None or not need_bias)
+            and conv.weight.is_contiguous() and conv.weight.dtype == torch.float32)
+
+
 def pool_s2_supported(pool, x):
     return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[-1] == x.shape[-2] and x.shape[-1] in (12, 26, 34)
-            and x.numel() > 0 and _aligned16(x) and isinstance(pool, torch.nn.AvgPool2d) and pool.kernel_size == 3
-            and pool.stride == 2 and pool.padding == 1 and pool.count_include_pad and not pool.ceil_mode
-            and pool.divisor_override is None)
+            and x.numel() > 0 and _aligned16(x) and _is_ref_pool(pool))
 
 
 def pool_s2(pool, x):
@@ -1138,19 +1078,13 @@ def pool_s2(pool, x):
 
 def pool_conv7_supported(pool, conv, x):
     return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[-1] == 12 and x.shape[-2] == 12 and x.shape[0] > 0
-            and _aligned16(x) and isinstance(pool, torch.nn.AvgPool2d) and pool.kernel_size == 3 and pool.stride == 2
-            and pool.padding == 1 and pool.count_include_pad and not pool.ceil_mode and pool.divisor_override is None
-            and isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (7, 7) and conv.stride == (2, 2)
-            and conv.padding == (3, 3) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is not None
-            and conv.in_channels == x.shape[1] and conv.weight.is_contiguous() and conv.weight.dtype == torch.float32)
+            and _aligned16(x) and _is_ref_pool(pool) and _is_ref_conv7(conv)
+            and conv.in_channels == x.shape[1])              # (historical: asks neither 64 output channels nor a CUDA weight, as `_BodyPX` does)
 
 
 def pool_conv7_mish(pool, conv, x):
     """mish(conv7(pool(x))) as [B, Co*3*3] (already flattened in NCHW order) — DQNNet.py:52-55."""
     return _PoolConv7.apply(x, conv.weight, conv.bias)
-
-
-_use_pool_conv7_cl = _os.environ.get("TRON_POOL_CONV7_HIP", "1") != "0"
 
 
 def pool_conv7_cl_supported(pool, conv, x):
@@ -1159,11 +1093,8 @@ def pool_conv7_cl_supported(pool, conv, x):
             and x.shape[-1] in (26, 34) and 0 < x.shape[0] <= (1 << 20) and x.shape[1] == 64 and x.is_contiguous() and _aligned16(x)):
         return False
     from Net import fused
-    return (fused.default_math == "f16x3" and isinstance(pool, torch.nn.AvgPool2d) and pool.kernel_size == 3 and pool.stride == 2
-            and pool.padding == 1 and pool.count_include_pad and not pool.ceil_mode and pool.divisor_override is None
-            and isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (7, 7) and conv.stride == (2, 2)
-            and conv.padding == (3, 3) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is not None
-            and conv.in_channels == 64 and conv.out_channels == 64 and conv.weight.is_contiguous() and conv.weight.dtype == torch.float32)
+    return (fused.default_math == "f16x3" and _is_ref_pool(pool) and _is_ref_conv7(conv)
+            and conv.in_channels == 64 and conv.out_channels == 64)
 
 
 def pool_conv7_cl_mish(pool, conv, x):

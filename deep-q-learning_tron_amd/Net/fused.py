@@ -206,24 +206,7 @@ def ws_supported(net, side):
 def ws_split_weights(convs):
     """The MFMA fragment images of several layers' weights in ONE launch (tron_conv3x3_ws_split_weights): a list of uint8
     workspace views to hand to conv_ws(..., wfrag=).  Built afresh by every forward pass — nothing is cached."""
-    import ctypes as C
-    L = nat.lib()
-    n = len(convs)
-    dev = convs[0].weight.device
-    sizes = [(int(L.tron_conv3x3_ws_workspace(c.in_channels, c.out_channels)) + 255) // 256 * 256 for c in convs]
-    buf = torch.empty(sum(sizes), dtype=torch.uint8, device=dev)
-    views, off = [], 0
-    for sz in sizes:
-        views.append(buf[off:off + sz])
-        off += sz
-    ws = [c.weight.detach() if c.weight.is_contiguous() else c.weight.detach().contiguous() for c in convs]
-    wp = (C.c_void_p * n)(*[w.data_ptr() for w in ws])
-    vp = (C.c_void_p * n)(*[v.data_ptr() for v in views])
-    ci = (C.c_int32 * n)(*[c.in_channels for c in convs])
-    co = (C.c_int32 * n)(*[c.out_channels for c in convs])
-    with torch.cuda.device(dev):
-        nat.check(L.tron_conv3x3_ws_split_weights(wp, ci, co, vp, n, nat.stream_ptr()), "tron_conv3x3_ws_split_weights")
-    return views
+    return _split_jobs([c.weight for c in convs], "tron_conv3x3_ws_split_weights", False)
 
 
 def conv1_px16(codes, conv, plane4=0.0):
@@ -242,23 +225,12 @@ def conv1_px16(codes, conv, plane4=0.0):
 
 
 def conv_ws(x, conv, wfrag, residual=None, act=True, want_px=True, want_f32=False, want_pre=False):
-    """act(conv3x3(x) + bias + residual) on PX16 images (tron_conv3x3_ws_fwd).  Returns the PX16 output and / or the f32
-    NCHW output / pre-activation, in that order, for what was asked."""
+    """act(conv3x3(x) + bias + residual) on PX16 images for an nn.Conv2d module: `conv_ws_infer` on its weight fragments and bias."""
     B, cin, S, _ = x.shape
     cout = conv.out_channels
     if cin != conv.in_channels or (residual is not None and residual.shape != (B, cout, S, S)):
         raise TypeError("conv_ws: channel / shape mismatch")
-    dev = x.buf.device
-    out = PX16(B, cout, S, dev) if want_px else None
-    o32 = torch.empty(B, cout, S, S, dtype=torch.float32, device=dev) if want_f32 else None
-    pre = torch.empty(B, cout, S, S, dtype=torch.float32, device=dev) if want_pre else None
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().tron_conv3x3_ws_fwd(nat.ptr(x.buf), nat.ptr(wfrag), nat.ptr(conv.bias.detach()),
-                                                nat.ptr(None if residual is None else residual.buf),
-                                                nat.ptr(None if out is None else out.buf), nat.ptr(o32), nat.ptr(pre),
-                                                B, cin, cout, S, int(act), nat.stream_ptr()), "tron_conv3x3_ws_fwd")
-    ret = [t for t, want in ((out, want_px), (o32, want_f32), (pre, want_pre)) if want]
-    return ret[0] if len(ret) == 1 else tuple(ret)
+    return conv_ws_infer(x, cout, wfrag, conv.bias, residual, want_f32, want_px, act, want_pre)
 
 
 use_pool_fused = _os.environ.get("TRON_POOL_FUSED", "1") != "0"      # 12x12: conv6 and the pooling as one launch (0: two) — gradient-free forwards
@@ -287,18 +259,24 @@ def conv_ws_pool12(x, conv, wfrag, residual):
     return out
 
 
-def conv_ws_infer(x, cout, wfrag, bias, residual=None, want_f32=False):
-    """mish(conv3x3(x) + bias + residual), gradient-free, from tensors instead of a module: x PX16 -> PX16, or (want_f32) the f32
-    NCHW tensor (tron_conv3x3_ws_fwd)."""
+def conv_ws_infer(x, cout, wfrag, bias, residual=None, want_f32=False, want_px=None, act=True, want_pre=False):
+    """act(conv3x3(x) + bias + residual), gradient-free, on PX16 images (tron_conv3x3_ws_fwd), from tensors instead of a module:
+    x PX16 -> PX16, or (want_f32) the f32 NCHW tensor.  want_px (default: not want_f32) / want_f32 / want_pre: returns the PX16
+    output and / or the f32 NCHW output / pre-activation, in that order, for what was asked."""
     B, cin, S, _ = x.shape
     dev = x.buf.device
-    out = None if want_f32 else PX16(B, cout, S, dev)
+    if want_px is None:
+        want_px = not want_f32
+    out = PX16(B, cout, S, dev) if want_px else None
     o32 = torch.empty(B, cout, S, S, dtype=torch.float32, device=dev) if want_f32 else None
+    pre = torch.empty(B, cout, S, S, dtype=torch.float32, device=dev) if want_pre else None
     with torch.cuda.device(dev):
-        nat.check(nat.lib().tron_conv3x3_ws_fwd(nat.ptr(x.buf), nat.ptr(wfrag), nat.ptr(bias.detach()), nat.ptr(None if residual is None else residual.buf),
-                                                nat.ptr(None if out is None else out.buf), nat.ptr(o32), None, B, cin, cout, S, 1, nat.stream_ptr()),
-                  "tron_conv3x3_ws_fwd")
-    return o32 if want_f32 else out
+        nat.check(nat.lib().tron_conv3x3_ws_fwd(nat.ptr(x.buf), nat.ptr(wfrag), nat.ptr(bias.detach()),
+                                                nat.ptr(None if residual is None else residual.buf),
+                                                nat.ptr(None if out is None else out.buf), nat.ptr(o32), nat.ptr(pre),
+                                                B, cin, cout, S, int(act), nat.stream_ptr()), "tron_conv3x3_ws_fwd")
+    ret = [t for t, want in ((out, want_px), (o32, want_f32), (pre, want_pre)) if want]
+    return ret[0] if len(ret) == 1 else tuple(ret)
 
 
 def trunk_px(net, codes, plane4=0.0, want="f32"):
@@ -335,9 +313,7 @@ class GradPX:
         self.info = torch.empty(68, dtype=torch.float32, device=device)          # (written by the producing kernels: {s, 1 / s} and the channels' maxima)
 
     def float(self):
-        px = PX16.__new__(PX16)
-        px.shape, px.buf = self.shape, self.buf
-        return px.float() * self.info[1]
+        return _px(self.shape, self.buf).float() * self.info[1]
 
 
 def _px(shape, buf):
