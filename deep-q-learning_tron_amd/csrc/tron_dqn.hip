@@ -278,7 +278,9 @@ struct AdamJobs {
     int n;
 };
 constexpr int ADAM_CHUNK = 1024;
-__global__ __launch_bounds__(256) void k_adam_soft(AdamJobs J, float beta1, float beta2, float eps, float tau)
+// om_beta1 / om_beta2 are 1 - beta rounded from double on the host, like the bias corrections: 1.0f - (float)0.999 is 1.3e-5 off 0.001,
+// 216 half-ulps of a fresh v (tests/adam_soft_support.py: the `one_minus_beta_in_f32` model).
+__global__ __launch_bounds__(256) void k_adam_soft(AdamJobs J, float om_beta1, float beta2, float om_beta2, float eps, float tau)
 {
     int k = 0;
     while (k + 1 < J.n && (int)blockIdx.x >= J.chunk0[k + 1]) ++k;       // (block-uniform: scalar loads from the kernel arguments)
@@ -295,8 +297,8 @@ __global__ __launch_bounds__(256) void k_adam_soft(AdamJobs J, float beta1, floa
             // torch/optim's single-tensor formulas in f32: m <- lerp(m, g, 1 - b1); v <- b2 v + (1 - b2) g g;
             // w <- w - (lr / (1 - b1^step)) m / (sqrt(v) / sqrt(1 - b2^step) + eps)
             const float gi = g[i];
-            const float mi = __fmaf_rn(1.0f - beta1, gi - m[i], m[i]);
-            const float vi = __fmaf_rn(beta2, v[i], (1.0f - beta2) * gi * gi);
+            const float mi = __fmaf_rn(om_beta1, gi - m[i], m[i]);
+            const float vi = __fmaf_rn(beta2, v[i], om_beta2 * gi * gi);
             m[i] = mi;
             v[i] = vi;
             w -= ss * (mi / (__fsqrt_rn(vi) / bc + eps));
@@ -312,15 +314,17 @@ extern "C" int tron_adam_soft_update(int32_t n, float *const *params, const floa
                                      double lr, double beta1, double beta2, double eps, double tau, void *stream)
 {
     if (n < 0 || (n && (!params || !grads || !exp_avg || !exp_avg_sq || !numel || !steps))) return TRON_ERR_BAD_ARG;
-    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && tau >= 0.0 && tau <= 1.0)) return TRON_ERR_BAD_ARG;
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && tau >= 0.0 && tau <= 1.0) || lr != lr) return TRON_ERR_BAD_ARG;
+    for (int k = 0; k < n; ++k) {                                        // every tensor before the first launch: a refused call writes nothing
+        if (!params[k] || numel[k] < 0 || numel[k] >= (1ll << 31) - ADAM_CHUNK) return TRON_ERR_BAD_ARG;
+        if (grads[k] && (!exp_avg[k] || !exp_avg_sq[k] || !(steps[k] >= 1.0))) return TRON_ERR_BAD_ARG;
+    }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     for (int k = 0; k < n;) {
         AdamJobs J{};
         int cnt = 0;
         J.chunk0[0] = 0;
         for (; k < n && cnt < TRON_ADAM_MAX_TENSORS; ++k) {
-            if (!params[k] || numel[k] < 0 || numel[k] >= (1ll << 31) - ADAM_CHUNK) return TRON_ERR_BAD_ARG;
-            if (grads[k] && (!exp_avg[k] || !exp_avg_sq[k] || !(steps[k] >= 1.0))) return TRON_ERR_BAD_ARG;
             if (numel[k] == 0 || (!grads[k] && !(targets && targets[k]))) continue;
             J.p[cnt] = params[k];
             J.g[cnt] = grads[k];
@@ -332,14 +336,13 @@ extern "C" int tron_adam_soft_update(int32_t n, float *const *params, const floa
                 J.step_size[cnt] = (float)(lr / (1.0 - pow(beta1, steps[k])));
                 J.bc2_sqrt[cnt] = (float)sqrt(1.0 - pow(beta2, steps[k]));
             }
-            const int64_t chunks = (numel[k] + ADAM_CHUNK - 1) / ADAM_CHUNK;
-            if ((int64_t)J.chunk0[cnt] + chunks >= (1ll << 31)) return TRON_ERR_UNSUPPORTED;
-            J.chunk0[cnt + 1] = J.chunk0[cnt] + (int)chunks;
+            J.chunk0[cnt + 1] = J.chunk0[cnt] + (int)((numel[k] + ADAM_CHUNK - 1) / ADAM_CHUNK);   // (< 2^21 each, 32 of them: < 2^26 blocks)
             ++cnt;
         }
         J.n = cnt;
         if (!cnt) continue;
-        hipLaunchKernelGGL(k_adam_soft, dim3((unsigned)J.chunk0[cnt]), dim3(256), 0, st, J, (float)beta1, (float)beta2, (float)eps, (float)tau);
+        hipLaunchKernelGGL(k_adam_soft, dim3((unsigned)J.chunk0[cnt]), dim3(256), 0, st, J, (float)(1.0 - beta1), (float)beta2,
+                           (float)(1.0 - beta2), (float)eps, (float)tau);
         if (hipGetLastError() != hipSuccess) return TRON_ERR_LAUNCH;
     }
     return TRON_OK;

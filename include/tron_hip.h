@@ -353,7 +353,9 @@ int64_t tron_linear_wgrad_workspace(int64_t batch, int32_t out_features, int32_t
  *   m <- m + (1 - beta1)(g - m);  v <- beta2 v + (1 - beta2) g g;
  *   w <- w - lr / (1 - beta1^steps[k]) * m / (sqrt(v) / sqrt(1 - beta2^steps[k]) + eps)      (steps[k] >= 1: the count INCLUDING this step)
  *   target <- tau w + (1 - tau) target                                                     (targets == NULL or targets[k] == NULL: skipped)
- * grads[k] == NULL: that tensor takes no Adam step (its soft update still runs).  The bias corrections are computed in double on the host. */
+ * grads[k] == NULL: that tensor takes no Adam step (its soft update still runs).  The bias corrections and 1 - beta1, 1 - beta2
+ * are computed in double on the host and rounded once.  A call that returns TRON_ERR_BAD_ARG has written nothing: every tensor is checked
+ * before the first launch. */
 #define TRON_ADAM_MAX_TENSORS 32
 int tron_adam_soft_update(int32_t n, float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
                           float *const *targets, const int64_t *numel, const double *steps, double lr, double beta1, double beta2,
