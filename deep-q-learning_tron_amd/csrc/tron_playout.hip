@@ -12,6 +12,8 @@
 //               four-way bank conflict in LDS; sixteen boards per instruction).  Reads are 16-byte aligned chunks put
 //               together with v_alignbyte, whatever a board's base address is (odd sides, sliced tensors); only a chunk
 //               that sticks out of the caller's buffer is read byte by byte.
+// tron_playout_values fans every board out over the 16 joint first moves and tallies the endings: k_playout_values and
+// k_values_pick below, made of the same board-in, start and step functions as k_playout.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -121,24 +123,20 @@ __device__ __forceinline__ int safe_move(const Board &bd, int S, int r, int c, u
     return cnt ? (int)((cand >> (2u * __umulhi(u, cnt))) & 3u) : 0;
 }
 
-__global__ __launch_bounds__(PO_LANES) void k_playout(const int8_t *__restrict__ codes, int64_t n, int S, int k_steps,
-                                                      const int8_t *__restrict__ actions, uint32_t seed, uint32_t stream,
-                                                      uint32_t call_lo, uint32_t call_hi, int32_t *__restrict__ out_steps,
-                                                      int8_t *__restrict__ out_winner, int8_t *__restrict__ out_codes)
+// ---- the phases both kernels are made of ---------------------------------------------------------------------------------
+// Boards in: `count` boards from board `first` on, through groups of GROUP lanes per board.  Lane (gb, sub) packs words
+// sub, sub + GROUP, ... of boards gb, gb + 64 / GROUP, ... to dst[w * stride + b] and the group merges the heads it saw
+// into info[b].  Every lane of the wave takes part, whatever `count` is.
+template <int GROUP>
+__device__ __forceinline__ void boards_in(const int8_t *__restrict__ codes, int64_t total, int G, int WORDS, int64_t first,
+                                          int count, uint32_t *dst, int stride, uint32_t *info)
 {
-    extern __shared__ uint32_t po_lds[];
-    const int lane = threadIdx.x, G = S * S, WORDS = (G + 15) >> 4, W = S - 2;
-    uint32_t *info = po_lds + WORDS * PO_LANES;                        // [64] one word per board, between the phases
-    const int64_t first = (int64_t)blockIdx.x * PO_LANES, idx = first + lane, total = n * (int64_t)G;
-    const int sub = lane % PO_GROUP, gb = lane / PO_GROUP;
-    const bool have = idx < n;
-
-    // ---- boards in: lane (gb, sub) packs words sub, sub + 4, ... of boards gb, gb + 16, ... and counts their heads
-    for (int b0 = 0; b0 < PO_LANES; b0 += PO_BOARDS) {
+    const int sub = (int)threadIdx.x % GROUP, gb = (int)threadIdx.x / GROUP;
+    for (int b0 = 0; b0 < count; b0 += PO_LANES / GROUP) {
         const int b = b0 + gb;
-        const bool have_b = first + b < n;
+        const bool have_b = b < count;
         uint32_t heads = 0u;
-        for (int w = sub; w < WORDS; w += PO_GROUP) {
+        for (int w = sub; w < WORDS; w += GROUP) {
             if (!have_b) continue;
             uint32_t x[4];
             load16(codes, total, (first + b) * (int64_t)G + 16 * w, x);
@@ -152,93 +150,128 @@ __global__ __launch_bounds__(PO_LANES) void k_playout(const int8_t *__restrict__
                 if (v == 10) heads = head_seen(heads, 0, 16 * w + i);
                 if (v == -10) heads = head_seen(heads, 1, 16 * w + i);
             }
-            po_lds[w * PO_LANES + b] = word;
+            dst[w * stride + b] = word;
         }
-        heads = heads_merged(heads, (uint32_t)__shfl_xor((int)heads, 1));
-        heads = heads_merged(heads, (uint32_t)__shfl_xor((int)heads, 2));
+#pragma unroll
+        for (int m = 1; m < GROUP; m <<= 1) heads = heads_merged(heads, (uint32_t)__shfl_xor((int)heads, m));
         if (sub == 0) info[b] = heads;
     }
-    __syncthreads();
+}
 
-    // ---- playable: exactly one +10 and one -10, both strictly inside the border
-    const Board bd{po_lds + lane};
-    const uint32_t heads = info[lane];
+// One playout as its lane carries it: the heads in board coordinates, the alive bits, how it ended (-1: not yet).
+struct Playout {
     int r[2], c[2];
+    uint32_t alive;
+    int winner, steps;
+    bool live;
+};
+// Playable: exactly one +10 and one -10, both strictly inside the border; a playout that is not never goes live.
+__device__ __forceinline__ Playout playout_start(uint32_t heads, int S, bool have)
+{
+    Playout po;
     bool playable = have;
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
         const uint32_t f = (heads >> (16 * p)) & 0xFFFFu;
         const int at = (int)(f >> 2), pr = at / S, pc = at - pr * S;
-        playable = playable && (f & 3u) == 1u && pr >= 1 && pc >= 1 && pr <= W && pc <= W;
-        r[p] = pr - 1;
-        c[p] = pc - 1;
+        playable = playable && (f & 3u) == 1u && pr >= 1 && pc >= 1 && pr <= S - 2 && pc <= S - 2;
+        po.r[p] = pr - 1;
+        po.c[p] = pc - 1;
     }
+    po.alive = META_ALIVE0 | META_ALIVE1;
+    po.winner = -1;
+    po.steps = 0;
+    po.live = playable;
+    return po;
+}
+// Step t of the live playout `index`: `now` holds the two players' tape bytes (player 2's in bits 8..15).
+__device__ __forceinline__ void playout_step(const Board &bd, int S, Playout &po, uint32_t now, uint32_t index, int t,
+                                             uint32_t call_lo, uint32_t call_hi, uint32_t seed, uint32_t stream)
+{
+    int a[2] = {(int)(int8_t)now, (int)(int8_t)(now >> 8)};
+    if ((a[0] | a[1]) < 0) {                                           // a negative byte: one Philox block serves both players
+        uint32_t u[4];
+        philox4x32_10(index, (uint32_t)t, call_lo, call_hi, seed, stream, u);
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+            if (a[p] < 0) a[p] = safe_move(bd, S, po.r[p], po.c[p], u[p]);
+    }
+    // Game.step: both move, then each is judged on the cell it entered, player 2 after player 1's head is down
+    int old[2], f[2];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        int dr, dc;
+        action_delta(a[p] & 3, dr, dc);
+        old[p] = cell_index(S, po.r[p], po.c[p]);
+        po.r[p] += dr;
+        po.c[p] += dc;
+        f[p] = cell_index(S, po.r[p], po.c[p]);
+    }
+    uint32_t *w0 = bd.words + (f[0] >> 4) * PO_LANES, *w1 = bd.words + (f[1] >> 4) * PO_LANES;
+    const uint32_t s0 = 2u * (uint32_t)(f[0] & 15), s1 = 2u * (uint32_t)(f[1] & 15);
+    uint32_t x0 = *w0, x1 = *w1;
+    uint32_t tf[2] = {(x0 >> s0) & 3u, (x1 >> s1) & 3u};
+    plain_targets(old, f, tf, PO_P1, PO_P2, PO_P1_HEAD);
+#pragma unroll
+    for (int p = 0; p < 2; ++p) po.alive = collide(po.alive, p, S - 2, po.r[p], po.c[p], tf[p] == PO_EMPTY);
+    // the new heads' cells take their owners' trails (what they are once the next step begins); a cell a player died
+    // on is a head's cell of the last position, which the head byte covers
+    x0 |= PO_P1 << s0;
+    if (w1 == w0) x1 = x0;
+    x1 |= PO_P2 << s1;
+    *w0 = x0;
+    *w1 = x1;
+    po.steps = t + 1;
+    int won = 0;
+    if (settle(po.alive, po.r, po.c, won)) {
+        po.winner = won;
+        po.live = false;
+    }
+}
+
+__global__ __launch_bounds__(PO_LANES) void k_playout(const int8_t *__restrict__ codes, int64_t n, int S, int k_steps,
+                                                      const int8_t *__restrict__ actions, uint32_t seed, uint32_t stream,
+                                                      uint32_t call_lo, uint32_t call_hi, int32_t *__restrict__ out_steps,
+                                                      int8_t *__restrict__ out_winner, int8_t *__restrict__ out_codes)
+{
+    extern __shared__ uint32_t po_lds[];
+    const int lane = threadIdx.x, G = S * S, WORDS = (G + 15) >> 4;
+    uint32_t *info = po_lds + WORDS * PO_LANES;                        // [64] one word per board, between the phases
+    const int64_t first = (int64_t)blockIdx.x * PO_LANES, idx = first + lane, total = n * (int64_t)G;
+    const int sub = lane % PO_GROUP, gb = lane / PO_GROUP;
+    const bool have = idx < n;
+
+    boards_in<PO_GROUP>(codes, total, G, WORDS, first, (int)min((int64_t)PO_LANES, n - first), po_lds, PO_LANES, info);
+    __syncthreads();
+    const Board bd{po_lds + lane};
+    Playout po = playout_start(have ? info[lane] : 0u, S, have);
+    const bool playable = po.live;
 
     // ---- the steps.  A lane that is finished or rejected idles; the wave leaves when its last lane is done
-    uint32_t alive = META_ALIVE0 | META_ALIVE1;
-    int winner = -1, steps = 0;
-    bool live = playable;
     const int8_t *tape = actions ? actions + 2 * idx : nullptr;        // row t: tape + t * 2n
     auto tape_row = [&](int t) {
         uint16_t v;
         __builtin_memcpy(&v, tape + (int64_t)t * 2 * n, 2);
         return (uint32_t)v;
     };
-    uint32_t ahead = (tape && live && k_steps > 0) ? tape_row(0) : 0xFFFFu;
+    uint32_t ahead = (tape && po.live && k_steps > 0) ? tape_row(0) : 0xFFFFu;
     for (int t = 0; t < k_steps; ++t) {
-        if (!__ballot(live)) break;
+        if (!__ballot(po.live)) break;
         const uint32_t now = ahead;
-        if (tape && live && t + 1 < k_steps) ahead = tape_row(t + 1);  // one step ahead of its use
-        if (!live) continue;
-        int a[2] = {(int)(int8_t)now, (int)(int8_t)(now >> 8)};
-        if ((a[0] | a[1]) < 0) {                                       // a negative byte: one Philox block serves both players
-            uint32_t u[4];
-            philox4x32_10((uint32_t)idx, (uint32_t)t, call_lo, call_hi, seed, stream, u);
-#pragma unroll
-            for (int p = 0; p < 2; ++p)
-                if (a[p] < 0) a[p] = safe_move(bd, S, r[p], c[p], u[p]);
-        }
-        // Game.step: both move, then each is judged on the cell it entered, player 2 after player 1's head is down
-        int old[2], f[2];
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            int dr, dc;
-            action_delta(a[p] & 3, dr, dc);
-            old[p] = cell_index(S, r[p], c[p]);
-            r[p] += dr;
-            c[p] += dc;
-            f[p] = cell_index(S, r[p], c[p]);
-        }
-        uint32_t *w0 = bd.words + (f[0] >> 4) * PO_LANES, *w1 = bd.words + (f[1] >> 4) * PO_LANES;
-        const uint32_t s0 = 2u * (uint32_t)(f[0] & 15), s1 = 2u * (uint32_t)(f[1] & 15);
-        uint32_t x0 = *w0, x1 = *w1;
-        uint32_t tf[2] = {(x0 >> s0) & 3u, (x1 >> s1) & 3u};
-        plain_targets(old, f, tf, PO_P1, PO_P2, PO_P1_HEAD);
-#pragma unroll
-        for (int p = 0; p < 2; ++p) alive = collide(alive, p, W, r[p], c[p], tf[p] == PO_EMPTY);
-        // the new heads' cells take their owners' trails (what they are once the next step begins); a cell a player died
-        // on is a head's cell of the last position, which the head byte covers
-        x0 |= PO_P1 << s0;
-        if (w1 == w0) x1 = x0;
-        x1 |= PO_P2 << s1;
-        *w0 = x0;
-        *w1 = x1;
-        steps = t + 1;
-        int won = 0;
-        if (settle(alive, r, c, won)) {
-            winner = won;
-            live = false;
-        }
+        if (tape && po.live && t + 1 < k_steps) ahead = tape_row(t + 1);   // one step ahead of its use
+        if (!po.live) continue;
+        playout_step(bd, S, po, now, (uint32_t)idx, t, call_lo, call_hi, seed, stream);
     }
     if (have) {
-        if (out_steps) out_steps[idx] = playable ? steps : 0;
-        if (out_winner) out_winner[idx] = (int8_t)(playable ? winner : -2);
+        if (out_steps) out_steps[idx] = playable ? po.steps : 0;
+        if (out_winner) out_winner[idx] = (int8_t)(playable ? po.winner : -2);
     }
     if (!out_codes) return;
 
     // ---- boards out: the last position's cells from LDS with the two head bytes on top, player 2's last (game.py:205-214);
     // a rejected board, and every board of a call of no steps, is its input copied
-    info[lane] = (playable && k_steps > 0) ? (uint32_t)cell_index(S, r[0], c[0]) | ((uint32_t)cell_index(S, r[1], c[1]) << 11) : PO_COPY;
+    info[lane] = (playable && k_steps > 0) ? (uint32_t)cell_index(S, po.r[0], po.c[0]) | ((uint32_t)cell_index(S, po.r[1], po.c[1]) << 11)
+                                           : PO_COPY;
     __syncthreads();
     constexpr uint32_t CODE_OF = pack4(1, -2, -3, -1);                 // PO_EMPTY, PO_P1, PO_P2, PO_WALL as player 1 sees them
     for (int b0 = 0; b0 < PO_LANES; b0 += PO_BOARDS) {
@@ -272,6 +305,108 @@ __global__ __launch_bounds__(PO_LANES) void k_playout(const int8_t *__restrict__
     }
 }
 
+// ---- Monte-Carlo move values (tron_playout_values) --------------------------------------------------------------------------
+//   k_playout_values  k_playout's lanes and step loop over launch indices q = ((board * 16 + a1 * 4 + a2) * copies + j):
+//               the board and the first move come from q, no tape and no copied board exist.  A wave's 64 consecutive
+//               indices meet at most PV_SLOTS boards (16 * copies >= 16 indices per board: 5 at the most).  Each is read
+//               from global memory once, by a group of 16 lanes, classified once into a staging table [word][slot], and
+//               copied from there into the column of every lane that plays it (a read of at most 5 addresses on 5
+//               different banks, a write to the lane's own bank).  The endings are summed in LDS, [slot][move][4 classes
+//               and the steps], and each non-zero sum goes out as one global integer add: sums of integers, so the order
+//               of arrival changes nothing.
+//   k_values_pick     one lane per board, after the tallies: the maximin of m = wins of 1 - wins of 2 for either player.
+constexpr int PV_GROUP = 16;                       // lanes that share a board while k_playout_values loads it
+constexpr int PV_SLOTS = 8;                        // room for the boards of one wave (two rounds of 64 / PV_GROUP)
+constexpr int PV_ROW = 5;                          // one (board, first move): draws, wins of 1, wins of 2, unfinished, steps
+constexpr int PV_TALLY = PV_SLOTS * 16 * PV_ROW;
+
+__global__ __launch_bounds__(PO_LANES) void k_playout_values(const int8_t *__restrict__ codes, int64_t n, int S, int k_steps,
+                                                             uint32_t copies, uint32_t seed, uint32_t stream, uint32_t call_lo,
+                                                             uint32_t call_hi, int32_t *__restrict__ out_counts,
+                                                             int32_t *__restrict__ out_steps)
+{
+    extern __shared__ uint32_t po_lds[];
+    const int lane = threadIdx.x, G = S * S, WORDS = (G + 15) >> 4;
+    uint32_t *info = po_lds + WORDS * PO_LANES;                        // [PV_SLOTS] the heads of the wave's boards
+    uint32_t *stage = info + PO_LANES;                                 // [WORDS][PV_SLOTS] the wave's boards, packed
+    int *tally = reinterpret_cast<int *>(stage + WORDS * PV_SLOTS);    // [PV_SLOTS][16][PV_ROW]
+    const uint32_t per = 16u * copies, nq = (uint32_t)n * per;          // n * 16 * copies < 2^31 (checked by the entry)
+    const uint32_t first = blockIdx.x * (uint32_t)PO_LANES, q = first + (uint32_t)lane;
+    const uint32_t b_lo = first / per, b_hi = min(first + (uint32_t)(PO_LANES - 1), nq - 1u) / per;
+    const int nb = (int)(b_hi - b_lo) + 1;                             // <= 63 / 16 + 2 = 5
+    const bool have = q < nq;
+    const int lb = have ? (int)(q / per - b_lo) : 0, move = (int)((q / copies) & 15u);
+
+    for (int e = lane; e < PV_TALLY; e += PO_LANES) tally[e] = 0;
+    boards_in<PV_GROUP>(codes, n * (int64_t)G, G, WORDS, (int64_t)b_lo, nb, stage, PV_SLOTS, info);
+    __syncthreads();
+    const Board bd{po_lds + lane};
+    if (have)
+        for (int w = 0; w < WORDS; ++w) bd.words[w * PO_LANES] = stage[w * PV_SLOTS + lb];
+    Playout po = playout_start(info[lb], S, have);
+    const bool playable = po.live;
+
+    // ---- the steps: the first from the index, every later one a safe draw for both
+    for (int t = 0; t < k_steps; ++t) {
+        if (!__ballot(po.live)) break;
+        if (!po.live) continue;
+        playout_step(bd, S, po, t ? 0xFFFFu : (uint32_t)(move >> 2) | ((uint32_t)(move & 3) << 8), q, t, call_lo, call_hi, seed, stream);
+    }
+
+    // ---- the tallies: winner -1, 0, 1, 2 is class 3, 0, 1, 2
+    if (playable) {
+        int *row = tally + (lb * 16 + move) * PV_ROW;
+        atomicAdd(row + (po.winner & 3), 1);
+        if (po.steps) atomicAdd(row + 4, po.steps);
+    }
+    __syncthreads();
+    for (int e = lane; e < nb * 16 * PV_ROW; e += PO_LANES) {
+        const int v = tally[e];
+        if (!v) continue;
+        const int64_t at = (int64_t)b_lo * 16 + e / PV_ROW;            // (board, first move)
+        const int c = e % PV_ROW;
+        if (c < 4) {
+            if (out_counts) atomicAdd(out_counts + at * 4 + c, v);
+        } else if (out_steps) {
+            atomicAdd(out_steps + at, v);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_values_pick(const int32_t *__restrict__ counts, int64_t n, int8_t *__restrict__ out_actions)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int32_t *c = counts + i * 64;
+    int m[4][4];
+#pragma unroll
+    for (int a1 = 0; a1 < 4; ++a1)
+#pragma unroll
+        for (int a2 = 0; a2 < 4; ++a2) m[a1][a2] = c[(a1 * 4 + a2) * 4 + 1] - c[(a1 * 4 + a2) * 4 + 2];
+    if (c[0] + c[1] + c[2] + c[3] == 0) {                              // a playable board's rows sum to copies >= 1
+        out_actions[2 * i] = out_actions[2 * i + 1] = (int8_t)-1;
+        return;
+    }
+    int best[2] = {0, 0}, best_v[2] = {0, 0};
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        int v[2] = {m[a][0], -m[0][a]};
+#pragma unroll
+        for (int o = 1; o < 4; ++o) {
+            v[0] = min(v[0], m[a][o]);
+            v[1] = min(v[1], -m[o][a]);
+        }
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+            if (a == 0 || v[p] > best_v[p]) {
+                best[p] = a;
+                best_v[p] = v[p];
+            }
+    }
+    out_actions[2 * i] = (int8_t)best[0];
+    out_actions[2 * i + 1] = (int8_t)best[1];
+}
+
 }  // namespace
 
 extern "C" int tron_playout_codes(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, const int8_t *actions,
@@ -287,4 +422,37 @@ extern "C" int tron_playout_codes(const int8_t *codes, int64_t n, int32_t side, 
                        reinterpret_cast<hipStream_t>(stream), codes, n, side, k_steps, actions, seed, stream_id, (uint32_t)call,
                        (uint32_t)(call >> 32), out_steps, out_winner, out_codes);
     return hipGetLastError() == hipSuccess ? TRON_OK : TRON_ERR_LAUNCH;
+}
+
+extern "C" int tron_playout_values(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, int32_t copies, uint32_t seed,
+                                   uint32_t stream_id, uint64_t call, int32_t *out_counts, int32_t *out_steps,
+                                   int8_t *out_actions, void *stream)
+{
+    constexpr int64_t LIMIT = (int64_t)1 << 31;                        // the Philox index and the sums are 32 bits
+    if (n < 0 || k_steps < 0 || copies < 1 || (!codes && n > 0)) return TRON_ERR_BAD_ARG;
+    if (n >= LIMIT || n * 16 >= LIMIT || n * 16 * copies >= LIMIT || (int64_t)copies * k_steps >= LIMIT) return TRON_ERR_BAD_ARG;
+    if (side < 6 || side > 34) return TRON_ERR_UNSUPPORTED;
+    if (n == 0) return TRON_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // the actions are read off the counts: without a buffer of the caller's they are tallied in one that lives for this call
+    int32_t *counts = out_counts;
+    const size_t counts_bytes = (size_t)n * 64 * sizeof(int32_t);
+    if (!counts && out_actions && hipMallocAsync(reinterpret_cast<void **>(&counts), counts_bytes, st) != hipSuccess) {
+        (void)hipGetLastError();
+        return TRON_ERR_LAUNCH;
+    }
+    bool ok = (!counts || hipMemsetAsync(counts, 0, counts_bytes, st) == hipSuccess) &&
+              (!out_steps || hipMemsetAsync(out_steps, 0, (size_t)n * 16 * sizeof(int32_t), st) == hipSuccess);
+    if (ok && (counts || out_steps)) {
+        const int words = (side * side + 15) >> 4;
+        const size_t smem = ((size_t)(words + 1) * PO_LANES + (size_t)words * PV_SLOTS + PV_TALLY) * sizeof(uint32_t);   // 23 840 bytes at side 34
+        const int64_t nq = n * 16 * copies;
+        hipLaunchKernelGGL(k_playout_values, dim3((unsigned)((nq + PO_LANES - 1) / PO_LANES)), dim3(PO_LANES), smem, st, codes, n,
+                           side, k_steps, (uint32_t)copies, seed, stream_id, (uint32_t)call, (uint32_t)(call >> 32), counts, out_steps);
+        if (out_actions)
+            hipLaunchKernelGGL(k_values_pick, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, counts, n, out_actions);
+    }
+    ok = hipGetLastError() == hipSuccess && ok;
+    if (counts != out_counts) ok = hipFreeAsync(counts, st) == hipSuccess && ok;
+    return ok ? TRON_OK : TRON_ERR_LAUNCH;
 }

@@ -26,8 +26,12 @@ def rating(model, model2=None, n_games=10000, slides=None, width=10, gamemode="i
            max_steps=None, verbose=True):
     """Returns a list of dicts {slide, p1_win, p2_win, draw, p1_rate} (play.py:76-98).
     model2="minimax" seats MinimaxPlayer(2, "voronoi") as player 2 — the "minimax rating" that
-    ACKTR.py:408-421 logs (there it is played net against net)."""
+    ACKTR.py:408-421 logs (there it is played net against net).  model2="montecarlo" seats the flat Monte-Carlo
+    opponent (VecTron.montecarlo_actions: 64 random playouts per game and step, call = the step number) as player 2; its
+    playouts follow mode None's rule, so it sits only in gamemode None / "none"."""
     model2 = model2 or model
+    if model2 == "montecarlo" and gamemode not in (None, "none"):
+        raise ValueError('model2="montecarlo" plays mode None\'s rule: gamemode must be None or "none"')
     slides = [0.03 * i for i in range(13)] if slides is None else list(slides)     # play.py:74,98
     n = n_games * len(slides)
     S = width + 2
@@ -41,10 +45,13 @@ def rating(model, model2=None, n_games=10000, slides=None, width=10, gamemode="i
     env1 = torch.stack([degree, st["weight"][:, 0].to(torch.float32)], 1)
     env2 = -((degree - 30) * 0.6) / 100           # [n]: main_loop hands player 2 torch.tensor([get_rate()]) per game
     prob_plane = ((-slide_t * 100) * (10 / 6) + 30).to(torch.float32).view(n, 1, 1, 1).expand(n, 1, S, S)
-    for _ in range(max_steps or width * width):
+    for t in range(max_steps or width * width):
         planes = pop_up_planes(obs.reshape(2 * n, S, S)).view(n, 2, 3, S, S)
         a1 = model_actions(model, planes[:, 0], prob_plane, env1)
-        a2 = env.minimax_actions(2) if isinstance(model2, str) else model_actions(model2, planes[:, 1], prob_plane, env2)
+        if model2 == "montecarlo":
+            a2 = env.montecarlo_actions(2, call=t)
+        else:
+            a2 = env.minimax_actions(2) if isinstance(model2, str) else model_actions(model2, planes[:, 1], prob_plane, env2)
         obs, _, done, _ = env.step(torch.stack([a1, a2], 1), autoreset=False)
         if bool(done.all()):
             break

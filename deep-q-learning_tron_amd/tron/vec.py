@@ -290,12 +290,36 @@ class VecTron:
             raise ValueError("playout plays mode None's rule; the sliding modes have no playout")
         if int(copies) < 1:
             raise ValueError("copies is at least 1")
+        return playout_codes(self._p1_codes().repeat_interleave(int(copies), dim=0), actions, k_steps, seed=self.seed,
+                             stream_id=self.rank, call=call, want_codes=want_codes)
+
+    def _p1_codes(self):
+        """int8 [N, S, S] player 1's codes of the boards as they stand: the attached buffer's plane, or a fresh encode."""
         if self.obs_is_state:
-            p1 = self.obs[:, 0]
-        else:
-            p1 = self.encode("codes", out=self._alloc_obs(nat.OBS_CODES_I8))[:, 0]
-        return playout_codes(p1.repeat_interleave(int(copies), dim=0), actions, k_steps, seed=self.seed, stream_id=self.rank,
-                             call=call, want_codes=want_codes)
+            return self.obs[:, 0]
+        return self.encode("codes", out=self._alloc_obs(nat.OBS_CODES_I8))[:, 0]
+
+    def playout_values(self, k_steps, copies=1, call=0, want_actions=True):
+        """playout_values on every env's current board (no board is copied): (counts int32 [N, 4, 4, 4], steps int32
+        [N, 4, 4], actions int8 [N, 2] | None), the draws keyed by this env's seed and rank.  The env itself is left
+        exactly as it was.  Mode None only; a finished env's row is what playout_values makes of its image."""
+        if self.mode not in (None, "none"):
+            raise ValueError("playout_values plays mode None's rule; the sliding modes have no playout")
+        return playout_values(self._p1_codes(), k_steps, copies, seed=self.seed, stream_id=self.rank, call=call,
+                              want_actions=want_actions)
+
+    def montecarlo_actions(self, player, k_steps=None, copies=4, call=0, out=None):
+        """The flat Monte-Carlo opponent, minimax_actions' counterpart: int8 [N], `player`'s (1|2) maximin move over the
+        tallies of playout_values(k_steps, copies, call) — 16 * copies random playouts of at most k_steps (default W * W)
+        steps per env.  Pass the step number as `call` so that every step draws its own playouts."""
+        if int(player) not in (1, 2):
+            raise ValueError("player is 1 or 2")
+        k_steps = self.W * self.W if k_steps is None else k_steps
+        actions = self.playout_values(k_steps, copies, call)[2][:, int(player) - 1]
+        if out is None:
+            return actions.contiguous()
+        out.copy_(actions)
+        return out
 
     # -- read-back ---------------------------------------------------------
     def grid(self):
@@ -390,6 +414,39 @@ def playout_codes(codes, actions=None, k_steps=None, seed=0x5EED, stream_id=0, c
                                                int(call) & 0xFFFFFFFFFFFFFFFF, nat.ptr(steps), nat.ptr(winner),
                                                nat.ptr(final), nat.stream_ptr()), "tron_playout_codes")
     return steps, winner, final
+
+
+def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, want_actions=True):
+    """Monte-Carlo move values of a stack of observation-code boards int8 [n, S, S] (tron_playout_values): every board is
+    played 16 * copies times, `copies` playouts behind each joint first move (a1, a2), every later move a safe draw.
+    Playout (i, a1, a2, j) is what playout_codes does at launch index q = ((i * 16 + a1 * 4 + a2) * copies + j) with board
+    i there and (a1, a2) in the tape's first row, under the same (seed, stream_id, call); no copied board and no tape is
+    made.  Returns (counts int32 [n, 4, 4, 4], steps int32 [n, 4, 4], actions int8 [n, 2] or None): counts[i, a1, a2] =
+    how many of those playouts ended as a draw, a win of player 1, a win of player 2, or not within k_steps (all zero for
+    a rejected board); steps = the sum of their lengths; actions[i, p] = player p + 1's maximin move on wins of 1 minus
+    wins of 2 (the first of equal moves in UP, RIGHT, DOWN, LEFT order; -1 for a rejected board)."""
+    c = codes.contiguous()
+    if c.dtype != torch.int8 or c.dim() != 3 or c.shape[1] != c.shape[2]:
+        raise ValueError(f"playout_values takes int8 boards [n, S, S], got {c.dtype} {tuple(c.shape)}")
+    n, side = int(c.shape[0]), int(c.shape[-1])
+    k_steps, copies = int(k_steps), int(copies)
+    if k_steps < 0:
+        raise ValueError("k_steps is at least 0")
+    if copies < 1:
+        raise ValueError("copies is at least 1")
+    if n * 16 * copies >= 2 ** 31:
+        raise ValueError(f"{n} boards x 16 moves x {copies} copies do not fit the 32-bit playout index")
+    if copies * k_steps >= 2 ** 31:
+        raise ValueError(f"{copies} copies x {k_steps} steps do not fit a 32-bit sum of steps")
+    cp = nat.ptr(c)                                                    # a host tensor is refused here
+    counts = torch.empty(n, 4, 4, 4, dtype=torch.int32, device=c.device)
+    steps = torch.empty(n, 4, 4, dtype=torch.int32, device=c.device)
+    actions = torch.empty(n, 2, dtype=torch.int8, device=c.device) if want_actions else None
+    with torch.cuda.device(c.device):
+        nat.check(nat.lib().tron_playout_values(cp, n, side, k_steps, copies, seed & 0xFFFFFFFF, stream_id & 0xFFFFFFFF,
+                                                int(call) & 0xFFFFFFFFFFFFFFFF, nat.ptr(counts), nat.ptr(steps),
+                                                nat.ptr(actions), nat.stream_ptr()), "tron_playout_values")
+    return counts, steps, actions
 
 
 def pop_up_planes(codes):

@@ -424,6 +424,34 @@ int tron_playout_codes(const int8_t *codes, int64_t n, int32_t side, int32_t k_s
                        int8_t  *out_winner,              /* i8[n]             or NULL */
                        int8_t  *out_codes,               /* i8[n][side][side] or NULL; may not alias codes */
                        void *stream);
+/* Monte-Carlo move values: every board fanned out over the 16 joint first moves, `copies` playouts each, and tallied.
+ * DEFINED THROUGH tron_playout_codes: playout (i, a1, a2, j), 0 <= a1, a2 < 4, 0 <= j < copies, has launch index
+ *     q = ((i * 16 + a1 * 4 + a2) * copies + j)
+ * and is exactly what tron_playout_codes does at index q of a launch of n * 16 * copies boards whose board q is codes[i],
+ * under a tape whose row 0 is (a1, a2) at q and whose rows 1 .. k_steps - 1 are negative (safe draws), with the same
+ * (seed, stream_id, call): Philox counter (q, step, call low, call high), words 0 and 1 for the two players.  No such
+ * launch, tape or copied board exists: the board and the first move are taken from the index.
+ * out_counts  i32[n][4][4][4] or NULL: [i][a1][a2][c] = how many of the `copies` playouts ended as c: 0 draw, 1 player 1
+ *             won, 2 player 2 won, 3 not finished within k_steps (out_winner -1).  A playable board's 16 rows each sum to
+ *             `copies`; a REJECTED board (tron_playout_codes' condition) gets all zeros.
+ * out_steps   i32[n][4][4] or NULL: the sum of those playouts' out_steps; 0 for a rejected board.
+ * out_actions i8[n][2] or NULL: [i][p] = the maximin move of player p (0 = player 1) on the integer payoff
+ *             m[a1][a2] = counts[..][1] - counts[..][2], negated for player 2: the value of an own move is the minimum over
+ *             the opponent's four moves, and the action is the first move in the order UP, RIGHT, DOWN, LEFT of the
+ *             greatest value.  -1 for both players of a rejected board.  Integer arithmetic only: the result does not
+ *             depend on the order in which the playouts were summed.
+ * k_steps == 0: every playable board gets counts[..][3] = copies, steps 0 and actions (0, 0).
+ * TRON_ERR_BAD_ARG: codes == NULL with n > 0, n < 0, k_steps < 0, copies < 1, n * 16 * copies >= 2^31 (the Philox index
+ * is 32 bits), copies * k_steps >= 2^31 (a sum of steps is 32 bits); TRON_ERR_UNSUPPORTED: side outside 6..34.  n == 0
+ * launches nothing.  Any subset of the outputs may be NULL (actions without counts are tallied in a stream-ordered
+ * allocation that lives for the call).  The outputs are zeroed on `stream`, then added to; nothing outside [0, n) of an
+ * output is written, and codes is only read.                                                                          */
+int tron_playout_values(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, int32_t copies,
+                        uint32_t seed, uint32_t stream_id, uint64_t call,
+                        int32_t *out_counts,              /* i32[n][4][4][4] or NULL */
+                        int32_t *out_steps,               /* i32[n][4][4]    or NULL */
+                        int8_t  *out_actions,             /* i8[n][2]        or NULL */
+                        void *stream);
 
 /* ---- K-FAC helper of the ACKTR path (Net/kfac.py:28-38 `_extract_patches`; its TODO at kfac.py:9-12
  * asks for this kernel) -------------------------------------------------------------------------- */
