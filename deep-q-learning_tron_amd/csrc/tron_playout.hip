@@ -14,6 +14,27 @@
 //               that sticks out of the caller's buffer is read byte by byte.
 // tron_playout_values fans every board out over the 16 joint first moves and tallies the endings: k_playout_values and
 // k_values_pick below, made of the same board-in, start and step functions as k_playout.
+//
+// tron_playout_slide_codes / tron_playout_slide_values play the sliding rule of "ice" and "temper" (one slide rate per
+// player and board): k_playout_slide and k_playout_values_slide are the two kernel bodies above instantiated with
+// playout_step_slide in the place of playout_step — same lanes, same LDS column, same phases before and behind the steps;
+// the mode-None kernels are the instantiations without it and compile to what they were.
+//   the sliding step   can look at four cells: each player's target n[p] and the cell behind it, sl[p], where a slide
+//               lands.  All four addresses follow from the heads and the moves alone (sl[p] = n[p] when the target is
+//               off the interior, so no address leaves the image), so all four are read in ONE round trip, before
+//               anything is decided, as lane_move does for the env (tron_env.hip).  What a later read of the reference
+//               would see of an earlier write of the same step — player 1's slide tile on player 2's target or landing,
+//               player 2's slide tile on player 1's new cell, player 1's head on player 2's — is a comparison of cell
+//               indices in registers.  A drawn move's four neighbours are a round trip of their own before that, as in
+//               the mode-None step: two round trips per drawn step in either rule.
+//               The up to four cells a step fills (two slide tiles, two trails under the new heads) go out as ds_or
+//               without return, in program order: no read-modify-write, so words that coincide need no care.  A slide
+//               tile is only ever laid on an EMPTY cell, so the OR is the cell's value; a trail ORed onto a cell that
+//               was not EMPTY belongs to a player that died there, the playout ends, and the head byte covers the cell.
+//   the decision       is (double)u <= rate as the reference writes it, on the lane's two float64 rates (four VGPRs): one
+//               conversion and one compare per player and step, exact for every float and every double (NaN, negative
+//               and >= 1 rates included) with no threshold to derive.  u comes from the caller's tape, or from words 2
+//               and 3 of the step's Philox block by the env's conversion; without a tape the block is drawn every step.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -229,10 +250,80 @@ __device__ __forceinline__ void playout_step(const Board &bd, int S, Playout &po
     }
 }
 
-__global__ __launch_bounds__(PO_LANES) void k_playout(const int8_t *__restrict__ codes, int64_t n, int S, int k_steps,
-                                                      const int8_t *__restrict__ actions, uint32_t seed, uint32_t stream,
-                                                      uint32_t call_lo, uint32_t call_hi, int32_t *__restrict__ out_steps,
-                                                      int8_t *__restrict__ out_winner, int8_t *__restrict__ out_codes)
+// The same step under the sliding rule (orc_step's order; game.py:158-214): player p's target n[p] is consumed when it is
+// strictly inside the border and EMPTY as the board stands then, and with (double)u[p] <= rate[p] it takes p's trail and
+// the head lands one cell further, on sl[p].  `taped`: u[] holds the caller's uniforms; else words 2 and 3 of the block.
+__device__ __forceinline__ void playout_step_slide(const Board &bd, int S, Playout &po, uint32_t now, const double rate[2],
+                                                   bool taped, float u0, float u1, uint32_t index, int t, uint32_t call_lo,
+                                                   uint32_t call_hi, uint32_t seed, uint32_t stream)
+{
+    int a[2] = {(int)(int8_t)now, (int)(int8_t)(now >> 8)};
+    float u[2] = {u0, u1};
+    if (!taped || (a[0] | a[1]) < 0) {                                 // one Philox block serves both players' move and slide
+        uint32_t x[4];
+        philox4x32_10(index, (uint32_t)t, call_lo, call_hi, seed, stream, x);
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+            if (a[p] < 0) a[p] = safe_move(bd, S, po.r[p], po.c[p], x[p]);
+        if (!taped) {                                                  // the env's conversion (tron_env.hip)
+            u[0] = (float)(x[2] >> 8) * (1.0f / 16777216.0f);
+            u[1] = (float)(x[3] >> 8) * (1.0f / 16777216.0f);
+        }
+    }
+    // the four cells, read in one round trip: as the board stood before the step (the heads' cells hold trails)
+    int dr[2], dc[2], n[2], sl[2];
+    bool inb[2], en[2], es[2];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        action_delta(a[p] & 3, dr[p], dc[p]);
+        inb[p] = on_board(S - 2, po.r[p] + dr[p], po.c[p] + dc[p]);
+        n[p] = cell_index(S, po.r[p] + dr[p], po.c[p] + dc[p]);
+        sl[p] = inb[p] ? n[p] + dr[p] * S + dc[p] : n[p];
+    }
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        en[p] = bd.cell(n[p]) == PO_EMPTY;
+        es[p] = bd.cell(sl[p]) == PO_EMPTY;
+    }
+    // both move, player 2 on the board that holds player 1's slide tile of this step
+    bool slid[2] = {false, false}, ef[2];
+    int f[2];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const bool empty_now = en[p] && !(p == 1 && slid[0] && n[1] == n[0]);
+        slid[p] = inb[p] && empty_now && (double)u[p] <= rate[p];
+        f[p] = slid[p] ? sl[p] : n[p];
+        ef[p] = slid[p] ? es[p] : empty_now;
+        po.r[p] += slid[p] ? 2 * dr[p] : dr[p];
+        po.c[p] += slid[p] ? 2 * dc[p] : dc[p];
+    }
+    // each is judged on the cell it entered, after both slide tiles, player 2 after player 1's head is down
+    const bool ok[2] = {ef[0] && !(slid[1] && f[0] == n[1]), ef[1] && !(slid[0] && f[1] == n[0]) && f[1] != f[0]};
+#pragma unroll
+    for (int p = 0; p < 2; ++p) po.alive = collide(po.alive, p, S - 2, po.r[p], po.c[p], ok[p]);
+    // the slide tiles and the new heads' cells take their owners' trails (see the file header)
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const uint32_t trail = p == 0 ? PO_P1 : PO_P2;
+        if (slid[p]) atomicOr(bd.words + (n[p] >> 4) * PO_LANES, trail << (2u * (uint32_t)(n[p] & 15)));
+        atomicOr(bd.words + (f[p] >> 4) * PO_LANES, trail << (2u * (uint32_t)(f[p] & 15)));
+    }
+    po.steps = t + 1;
+    int won = 0;
+    if (settle(po.alive, po.r, po.c, won)) {
+        po.winner = won;
+        po.live = false;
+    }
+}
+
+// SLIDE: the sliding rule under `rates` f64[n][2] and `uniforms` f32[k_steps][n][2] or nullptr (k_playout_slide); without it
+// the two are not looked at (k_playout).
+template <bool SLIDE>
+__global__ __launch_bounds__(PO_LANES) void k_playout_t(const int8_t *__restrict__ codes, int64_t n, int S, int k_steps,
+                                                        const int8_t *__restrict__ actions, uint32_t seed, uint32_t stream,
+                                                        uint32_t call_lo, uint32_t call_hi, int32_t *__restrict__ out_steps,
+                                                        int8_t *__restrict__ out_winner, int8_t *__restrict__ out_codes,
+                                                        const double *__restrict__ rates, const float *__restrict__ uniforms)
 {
     extern __shared__ uint32_t po_lds[];
     const int lane = threadIdx.x, G = S * S, WORDS = (G + 15) >> 4;
@@ -255,12 +346,29 @@ __global__ __launch_bounds__(PO_LANES) void k_playout(const int8_t *__restrict__
         return (uint32_t)v;
     };
     uint32_t ahead = (tape && po.live && k_steps > 0) ? tape_row(0) : 0xFFFFu;
-    for (int t = 0; t < k_steps; ++t) {
-        if (!__ballot(po.live)) break;
-        const uint32_t now = ahead;
-        if (tape && po.live && t + 1 < k_steps) ahead = tape_row(t + 1);   // one step ahead of its use
-        if (!po.live) continue;
-        playout_step(bd, S, po, now, (uint32_t)idx, t, call_lo, call_hi, seed, stream);
+    if constexpr (!SLIDE) {
+        for (int t = 0; t < k_steps; ++t) {
+            if (!__ballot(po.live)) break;
+            const uint32_t now = ahead;
+            if (tape && po.live && t + 1 < k_steps) ahead = tape_row(t + 1);   // one step ahead of its use
+            if (!po.live) continue;
+            playout_step(bd, S, po, now, (uint32_t)idx, t, call_lo, call_hi, seed, stream);
+        }
+    } else {
+        const double rate[2] = {have ? rates[2 * idx] : -1.0, have ? rates[2 * idx + 1] : -1.0};
+        const float *utape = uniforms ? uniforms + 2 * idx : nullptr;  // row t: utape + t * 2n, read as the action tape is
+        auto utape_row = [&](int t) { return make_float2(utape[(int64_t)t * 2 * n], utape[(int64_t)t * 2 * n + 1]); };
+        float2 uahead = (utape && po.live && k_steps > 0) ? utape_row(0) : make_float2(0.0f, 0.0f);
+        for (int t = 0; t < k_steps; ++t) {
+            if (!__ballot(po.live)) break;
+            const uint32_t now = ahead;
+            const float2 unow = uahead;
+            if (tape && po.live && t + 1 < k_steps) ahead = tape_row(t + 1);
+            if (utape && po.live && t + 1 < k_steps) uahead = utape_row(t + 1);
+            if (!po.live) continue;
+            playout_step_slide(bd, S, po, now, rate, utape != nullptr, unow.x, unow.y, (uint32_t)idx, t, call_lo, call_hi, seed,
+                               stream);
+        }
     }
     if (have) {
         if (out_steps) out_steps[idx] = playable ? po.steps : 0;
@@ -305,6 +413,8 @@ __global__ __launch_bounds__(PO_LANES) void k_playout(const int8_t *__restrict__
     }
 }
 
+constexpr auto k_playout = k_playout_t<false>, k_playout_slide = k_playout_t<true>;
+
 // ---- Monte-Carlo move values (tron_playout_values) --------------------------------------------------------------------------
 //   k_playout_values  k_playout's lanes and step loop over launch indices q = ((board * 16 + a1 * 4 + a2) * copies + j):
 //               the board and the first move come from q, no tape and no copied board exist.  A wave's 64 consecutive
@@ -320,10 +430,14 @@ constexpr int PV_SLOTS = 8;                        // room for the boards of one
 constexpr int PV_ROW = 5;                          // one (board, first move): draws, wins of 1, wins of 2, unfinished, steps
 constexpr int PV_TALLY = PV_SLOTS * 16 * PV_ROW;
 
-__global__ __launch_bounds__(PO_LANES) void k_playout_values(const int8_t *__restrict__ codes, int64_t n, int S, int k_steps,
-                                                             uint32_t copies, uint32_t seed, uint32_t stream, uint32_t call_lo,
-                                                             uint32_t call_hi, int32_t *__restrict__ out_counts,
-                                                             int32_t *__restrict__ out_steps)
+// SLIDE: the sliding rule, board i's row of `rates` f64[n][2] for all its playouts (k_playout_values_slide).
+template <bool SLIDE>
+__global__ __launch_bounds__(PO_LANES) void k_playout_values_t(const int8_t *__restrict__ codes, int64_t n, int S, int k_steps,
+                                                               uint32_t copies, uint32_t seed, uint32_t stream,
+                                                               uint32_t call_lo, uint32_t call_hi,
+                                                               int32_t *__restrict__ out_counts,
+                                                               int32_t *__restrict__ out_steps,
+                                                               const double *__restrict__ rates)
 {
     extern __shared__ uint32_t po_lds[];
     const int lane = threadIdx.x, G = S * S, WORDS = (G + 15) >> 4;
@@ -347,10 +461,19 @@ __global__ __launch_bounds__(PO_LANES) void k_playout_values(const int8_t *__res
     const bool playable = po.live;
 
     // ---- the steps: the first from the index, every later one a safe draw for both
+    double rate[2] = {-1.0, -1.0};
+    if constexpr (SLIDE) {
+        if (have) {
+            rate[0] = rates[2 * (int64_t)(q / per)];
+            rate[1] = rates[2 * (int64_t)(q / per) + 1];
+        }
+    }
     for (int t = 0; t < k_steps; ++t) {
         if (!__ballot(po.live)) break;
         if (!po.live) continue;
-        playout_step(bd, S, po, t ? 0xFFFFu : (uint32_t)(move >> 2) | ((uint32_t)(move & 3) << 8), q, t, call_lo, call_hi, seed, stream);
+        const uint32_t now = t ? 0xFFFFu : (uint32_t)(move >> 2) | ((uint32_t)(move & 3) << 8);
+        if constexpr (SLIDE) playout_step_slide(bd, S, po, now, rate, false, 0.0f, 0.0f, q, t, call_lo, call_hi, seed, stream);
+        else playout_step(bd, S, po, now, q, t, call_lo, call_hi, seed, stream);
     }
 
     // ---- the tallies: winner -1, 0, 1, 2 is class 3, 0, 1, 2
@@ -372,6 +495,8 @@ __global__ __launch_bounds__(PO_LANES) void k_playout_values(const int8_t *__res
         }
     }
 }
+
+constexpr auto k_playout_values = k_playout_values_t<false>, k_playout_values_slide = k_playout_values_t<true>;
 
 __global__ __launch_bounds__(256) void k_values_pick(const int32_t *__restrict__ counts, int64_t n, int8_t *__restrict__ out_actions)
 {
@@ -409,24 +534,47 @@ __global__ __launch_bounds__(256) void k_values_pick(const int32_t *__restrict__
 
 }  // namespace
 
-extern "C" int tron_playout_codes(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, const int8_t *actions,
-                                  uint32_t seed, uint32_t stream_id, uint64_t call, int32_t *out_steps, int8_t *out_winner,
-                                  int8_t *out_codes, void *stream)
+// The two entries of each pair differ in the kernel alone: rates == nullptr launches the mode-None kernel.
+static int launch_playout(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, const int8_t *actions, const double *rates,
+                          const float *uniforms, uint32_t seed, uint32_t stream_id, uint64_t call, int32_t *out_steps,
+                          int8_t *out_winner, int8_t *out_codes, void *stream)
 {
     if (n < 0 || n > 0x7FFFFFFF || k_steps < 0 || (!codes && n > 0) || (out_codes && out_codes == codes)) return TRON_ERR_BAD_ARG;
     if (side < 6 || side > 34) return TRON_ERR_UNSUPPORTED;
     if (n == 0) return TRON_OK;
     const int words = (side * side + 15) >> 4;
     const size_t smem = (size_t)(words + 1) * PO_LANES * sizeof(uint32_t);     // 18 944 bytes at side 34: no LDS opt-in
-    hipLaunchKernelGGL(k_playout, dim3((unsigned)((n + PO_LANES - 1) / PO_LANES)), dim3(PO_LANES), smem,
-                       reinterpret_cast<hipStream_t>(stream), codes, n, side, k_steps, actions, seed, stream_id, (uint32_t)call,
-                       (uint32_t)(call >> 32), out_steps, out_winner, out_codes);
+    const dim3 grid((unsigned)((n + PO_LANES - 1) / PO_LANES));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (rates)
+        hipLaunchKernelGGL(k_playout_slide, grid, dim3(PO_LANES), smem, st, codes, n, side, k_steps, actions, seed, stream_id,
+                           (uint32_t)call, (uint32_t)(call >> 32), out_steps, out_winner, out_codes, rates, uniforms);
+    else
+        hipLaunchKernelGGL(k_playout, grid, dim3(PO_LANES), smem, st, codes, n, side, k_steps, actions, seed, stream_id,
+                           (uint32_t)call, (uint32_t)(call >> 32), out_steps, out_winner, out_codes, nullptr, nullptr);
     return hipGetLastError() == hipSuccess ? TRON_OK : TRON_ERR_LAUNCH;
 }
 
-extern "C" int tron_playout_values(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, int32_t copies, uint32_t seed,
-                                   uint32_t stream_id, uint64_t call, int32_t *out_counts, int32_t *out_steps,
-                                   int8_t *out_actions, void *stream)
+extern "C" int tron_playout_codes(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, const int8_t *actions,
+                                  uint32_t seed, uint32_t stream_id, uint64_t call, int32_t *out_steps, int8_t *out_winner,
+                                  int8_t *out_codes, void *stream)
+{
+    return launch_playout(codes, n, side, k_steps, actions, nullptr, nullptr, seed, stream_id, call, out_steps, out_winner,
+                          out_codes, stream);
+}
+
+extern "C" int tron_playout_slide_codes(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, const int8_t *actions,
+                                        const double *rates, const float *uniforms, uint32_t seed, uint32_t stream_id,
+                                        uint64_t call, int32_t *out_steps, int8_t *out_winner, int8_t *out_codes, void *stream)
+{
+    if (!rates && n > 0) return TRON_ERR_BAD_ARG;
+    return launch_playout(codes, n, side, k_steps, actions, rates, uniforms, seed, stream_id, call, out_steps, out_winner,
+                          out_codes, stream);
+}
+
+static int launch_values(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, int32_t copies, const double *rates,
+                         uint32_t seed, uint32_t stream_id, uint64_t call, int32_t *out_counts, int32_t *out_steps,
+                         int8_t *out_actions, void *stream)
 {
     constexpr int64_t LIMIT = (int64_t)1 << 31;                        // the Philox index and the sums are 32 bits
     if (n < 0 || k_steps < 0 || copies < 1 || (!codes && n > 0)) return TRON_ERR_BAD_ARG;
@@ -447,12 +595,32 @@ extern "C" int tron_playout_values(const int8_t *codes, int64_t n, int32_t side,
         const int words = (side * side + 15) >> 4;
         const size_t smem = ((size_t)(words + 1) * PO_LANES + (size_t)words * PV_SLOTS + PV_TALLY) * sizeof(uint32_t);   // 23 840 bytes at side 34
         const int64_t nq = n * 16 * copies;
-        hipLaunchKernelGGL(k_playout_values, dim3((unsigned)((nq + PO_LANES - 1) / PO_LANES)), dim3(PO_LANES), smem, st, codes, n,
-                           side, k_steps, (uint32_t)copies, seed, stream_id, (uint32_t)call, (uint32_t)(call >> 32), counts, out_steps);
+        const dim3 grid((unsigned)((nq + PO_LANES - 1) / PO_LANES));
+        if (rates)
+            hipLaunchKernelGGL(k_playout_values_slide, grid, dim3(PO_LANES), smem, st, codes, n, side, k_steps, (uint32_t)copies,
+                               seed, stream_id, (uint32_t)call, (uint32_t)(call >> 32), counts, out_steps, rates);
+        else
+            hipLaunchKernelGGL(k_playout_values, grid, dim3(PO_LANES), smem, st, codes, n, side, k_steps, (uint32_t)copies, seed,
+                               stream_id, (uint32_t)call, (uint32_t)(call >> 32), counts, out_steps, nullptr);
         if (out_actions)
             hipLaunchKernelGGL(k_values_pick, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, counts, n, out_actions);
     }
     ok = hipGetLastError() == hipSuccess && ok;
     if (counts != out_counts) ok = hipFreeAsync(counts, st) == hipSuccess && ok;
     return ok ? TRON_OK : TRON_ERR_LAUNCH;
+}
+
+extern "C" int tron_playout_values(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, int32_t copies, uint32_t seed,
+                                   uint32_t stream_id, uint64_t call, int32_t *out_counts, int32_t *out_steps,
+                                   int8_t *out_actions, void *stream)
+{
+    return launch_values(codes, n, side, k_steps, copies, nullptr, seed, stream_id, call, out_counts, out_steps, out_actions, stream);
+}
+
+extern "C" int tron_playout_slide_values(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, int32_t copies,
+                                         const double *rates, uint32_t seed, uint32_t stream_id, uint64_t call,
+                                         int32_t *out_counts, int32_t *out_steps, int8_t *out_actions, void *stream)
+{
+    if (!rates && n > 0) return TRON_ERR_BAD_ARG;
+    return launch_values(codes, n, side, k_steps, copies, rates, seed, stream_id, call, out_counts, out_steps, out_actions, stream);
 }

@@ -28,7 +28,9 @@ def rating(model, model2=None, n_games=10000, slides=None, width=10, gamemode="i
     model2="minimax" seats MinimaxPlayer(2, "voronoi") as player 2 — the "minimax rating" that
     ACKTR.py:408-421 logs (there it is played net against net).  model2="montecarlo" seats the flat Monte-Carlo
     opponent (VecTron.montecarlo_actions: 64 random playouts per game and step, call = the step number) as player 2; its
-    playouts follow mode None's rule, so it sits only in gamemode None / "none"."""
+    playouts follow mode None's rule, so it sits only in gamemode None / "none".  model2="montecarlo-slide" seats the same
+    opponent with rates=True — its playouts follow the env's own rule under every game's own slide rates — in any
+    gamemode, the default ice sweep included."""
     model2 = model2 or model
     if model2 == "montecarlo" and gamemode not in (None, "none"):
         raise ValueError('model2="montecarlo" plays mode None\'s rule: gamemode must be None or "none"')
@@ -50,6 +52,8 @@ def rating(model, model2=None, n_games=10000, slides=None, width=10, gamemode="i
         a1 = model_actions(model, planes[:, 0], prob_plane, env1)
         if model2 == "montecarlo":
             a2 = env.montecarlo_actions(2, call=t)
+        elif model2 == "montecarlo-slide":
+            a2 = env.montecarlo_actions(2, call=t, rates=True)
         else:
             a2 = env.minimax_actions(2) if isinstance(model2, str) else model_actions(model2, planes[:, 1], prob_plane, env2)
         obs, _, done, _ = env.step(torch.stack([a1, a2], 1), autoreset=False)

@@ -280,18 +280,54 @@ class VecTron:
                       "tron_minimax_actions")
         return (out, values, expanded) if want_values else out
 
-    def playout(self, actions=None, k_steps=None, copies=1, call=0, want_codes=False):
+    def playout(self, actions=None, k_steps=None, copies=1, call=0, want_codes=False, rates=None, uniforms=None):
         """playout_codes on every env's current board, `copies` times each: playout i * copies + j is env i, and the tape
         (if any) is int8 [K, N * copies, 2].  The boards are the player-1 codes — the attached buffer's plane, or a fresh
         encode("codes") — and the draws are keyed by this env's seed and rank; the env itself is left exactly as it was.
-        Mode None only.  Returns (steps, winner, final_codes | None) as playout_codes does; a finished env's row is what
-        playout_codes makes of its image."""
-        if self.mode not in (None, "none"):
-            raise ValueError("playout plays mode None's rule; the sliding modes have no playout")
+        rates=None plays mode None's rule and is for mode None only; rates=True plays the sliding rule under
+        slide_rates(), a float64 [N, 2] tensor under the caller's rates (either in any mode; `uniforms`, float32
+        [K, N * copies, 2], replaces the drawn slide uniforms).  Returns (steps, winner, final_codes | None) as
+        playout_codes does; a finished env's row is what playout_codes makes of its image."""
+        rates = self._playout_rates(rates, "playout")
         if int(copies) < 1:
             raise ValueError("copies is at least 1")
+        if rates is not None:
+            rates = rates.repeat_interleave(int(copies), dim=0)
         return playout_codes(self._p1_codes().repeat_interleave(int(copies), dim=0), actions, k_steps, seed=self.seed,
-                             stream_id=self.rank, call=call, want_codes=want_codes)
+                             stream_id=self.rank, call=call, want_codes=want_codes, rates=rates, uniforms=uniforms)
+
+    def slide_rates(self):
+        """float64 [N, 2] on the device: the rate each player's `random.random() <= rate` meets in this env's mode
+        (game.py:169) — ice: the env's slide for both players; temper: get_rate(degree, weight[p]) in game.py:100-102's
+        operation order, in float64; mode None: -1.0 (never).  What playout / playout_values / montecarlo_actions take as
+        rates=True."""
+        if self.mode in (None, "none"):
+            return torch.full((self.N, 2), -1.0, dtype=torch.float64, device=self.device)
+        st = self.state()
+        if self.mode == "ice":
+            return st["slide"].view(self.N, 1).expand(self.N, 2).contiguous()
+        # every operand a device tensor: a division by a host scalar would be a multiplication by its reciprocal
+        f64 = dict(dtype=torch.float64, device=self.device)
+        hundred, k = torch.full((), 100.0, **f64), torch.full((), 0.6, **f64)
+        a = (st["degree"].to(torch.float64) - 30.0) * k
+        b = (-a) / hundred
+        c = (70.0 - st["weight"].to(torch.float64)) / hundred
+        return (b.view(self.N, 1) - c).contiguous()
+
+    def _playout_rates(self, rates, what):
+        """The rates argument of playout / playout_values: None (mode None only), True -> slide_rates(), or a tensor."""
+        if rates is None:
+            if self.mode not in (None, "none"):
+                raise ValueError(f"{what} without rates plays mode None's rule; in a sliding mode pass rates=True "
+                                 "(this env's slide_rates()) or a float64 [N, 2] tensor")
+            return None
+        if rates is True:
+            return self.slide_rates()
+        if not torch.is_tensor(rates):
+            raise TypeError("rates is None, True or a float64 tensor [N, 2]")
+        if tuple(rates.shape) != (self.N, 2):
+            raise ValueError(f"expected rates of shape ({self.N}, 2), got {tuple(rates.shape)}")
+        return rates
 
     def _p1_codes(self):
         """int8 [N, S, S] player 1's codes of the boards as they stand: the attached buffer's plane, or a fresh encode."""
@@ -299,23 +335,24 @@ class VecTron:
             return self.obs[:, 0]
         return self.encode("codes", out=self._alloc_obs(nat.OBS_CODES_I8))[:, 0]
 
-    def playout_values(self, k_steps, copies=1, call=0, want_actions=True):
+    def playout_values(self, k_steps, copies=1, call=0, want_actions=True, rates=None):
         """playout_values on every env's current board (no board is copied): (counts int32 [N, 4, 4, 4], steps int32
         [N, 4, 4], actions int8 [N, 2] | None), the draws keyed by this env's seed and rank.  The env itself is left
-        exactly as it was.  Mode None only; a finished env's row is what playout_values makes of its image."""
-        if self.mode not in (None, "none"):
-            raise ValueError("playout_values plays mode None's rule; the sliding modes have no playout")
+        exactly as it was.  rates as in playout: None is mode None's rule and mode None only, True this env's
+        slide_rates(), a tensor the caller's.  A finished env's row is what playout_values makes of its image."""
+        rates = self._playout_rates(rates, "playout_values")
         return playout_values(self._p1_codes(), k_steps, copies, seed=self.seed, stream_id=self.rank, call=call,
-                              want_actions=want_actions)
+                              want_actions=want_actions, rates=rates)
 
-    def montecarlo_actions(self, player, k_steps=None, copies=4, call=0, out=None):
+    def montecarlo_actions(self, player, k_steps=None, copies=4, call=0, out=None, rates=None):
         """The flat Monte-Carlo opponent, minimax_actions' counterpart: int8 [N], `player`'s (1|2) maximin move over the
-        tallies of playout_values(k_steps, copies, call) — 16 * copies random playouts of at most k_steps (default W * W)
-        steps per env.  Pass the step number as `call` so that every step draws its own playouts."""
+        tallies of playout_values(k_steps, copies, call, rates=rates) — 16 * copies random playouts of at most k_steps
+        (default W * W) steps per env.  Pass the step number as `call` so that every step draws its own playouts, and
+        rates=True in a sliding mode."""
         if int(player) not in (1, 2):
             raise ValueError("player is 1 or 2")
         k_steps = self.W * self.W if k_steps is None else k_steps
-        actions = self.playout_values(k_steps, copies, call)[2][:, int(player) - 1]
+        actions = self.playout_values(k_steps, copies, call, rates=rates)[2][:, int(player) - 1]
         if out is None:
             return actions.contiguous()
         out.copy_(actions)
@@ -379,7 +416,23 @@ def minimax_codes(codes, draws=None, mode="voronoi", depth=2):
     return act, values, expanded
 
 
-def playout_codes(codes, actions=None, k_steps=None, seed=0x5EED, stream_id=0, call=0, want_codes=False):
+def _slide_rates(rates, n, device, what):
+    """The checked rates argument of playout_codes / playout_values: float64 [n, 2], contiguous, on the boards' device."""
+    if not torch.is_tensor(rates):
+        raise TypeError(f"{what}: rates is None or a float64 tensor [n, 2]")
+    if rates.dtype != torch.float64:
+        raise TypeError(f"{what}: rates are float64, got {rates.dtype}")
+    if tuple(rates.shape) != (n, 2):
+        raise ValueError(f"{what}: expected rates of shape ({n}, 2), got {tuple(rates.shape)}")
+    if rates.device != device:
+        raise ValueError(f"{what}: rates must be on {device}, got {rates.device}")
+    if not rates.is_contiguous():
+        raise ValueError(f"{what}: rates must be contiguous")
+    return rates
+
+
+def playout_codes(codes, actions=None, k_steps=None, seed=0x5EED, stream_id=0, call=0, want_codes=False, rates=None,
+                  uniforms=None):
     """Plays a stack of observation-code boards int8 [n, S, S] (player 1's view: encode_codes(.., 1), a VecTron's
     obs[:, 0]) forward up to k_steps steps of mode None's Game.step, without restart (tron_playout_codes).  Returns
     (steps int32 [n], winner int8 [n], final_codes int8 [n, S, S] or None): steps played, 0 draw / 1 / 2 / -1 not
@@ -387,7 +440,10 @@ def playout_codes(codes, actions=None, k_steps=None, seed=0x5EED, stream_id=0, c
     observation of the last position reached.  actions: int8 tape [K, n, 2], step-major; a byte 0..127 is an action (its
     low two bits), a negative byte draws a safe move for that player in that step; None draws every move.  k_steps
     defaults to the tape's length.  The draws are Philox keyed by (seed, stream_id) at counter (playout, step, call):
-    pass another `call` for another set of playouts of the same boards; a fork is a repeat_interleave of the codes."""
+    pass another `call` for another set of playouts of the same boards; a fork is a repeat_interleave of the codes.
+    rates: float64 [n, 2] on the boards' device plays the sliding rule of "ice" / "temper" instead
+    (tron_playout_slide_codes): player p of board i slides when (double)u <= rates[i, p], u from words 2 and 3 of the
+    step's Philox block, or from `uniforms`, a float32 tape [K, n, 2]; a slide tile shows as its owner's body."""
     c = codes.contiguous()
     if c.dtype != torch.int8 or c.dim() != 3 or c.shape[1] != c.shape[2]:
         raise ValueError(f"playout_codes takes int8 boards [n, S, S], got {c.dtype} {tuple(c.shape)}")
@@ -401,22 +457,46 @@ def playout_codes(codes, actions=None, k_steps=None, seed=0x5EED, stream_id=0, c
             k_steps = int(a.shape[0])
         elif int(k_steps) > int(a.shape[0]):
             raise ValueError(f"k_steps {k_steps} is more than the tape's {int(a.shape[0])} rows")
-    elif k_steps is None:
+    if uniforms is not None:
+        if rates is None:
+            raise ValueError("uniforms belong to the sliding rule: pass rates with them")
+        if not torch.is_tensor(uniforms):
+            raise TypeError("uniforms is None or a float32 tensor [K, n, 2]")
+        if uniforms.dtype != torch.float32:
+            raise TypeError(f"the uniforms are float32, got {uniforms.dtype}")
+        if uniforms.dim() != 3 or tuple(uniforms.shape[1:]) != (n, 2):
+            raise ValueError(f"expected a float32 uniforms tape of shape (K, {n}, 2), got {tuple(uniforms.shape)}")
+        if uniforms.device != c.device:
+            raise ValueError(f"the uniforms must be on {c.device}, got {uniforms.device}")
+        if not uniforms.is_contiguous():
+            raise ValueError("the uniforms must be contiguous")
+        if k_steps is None:
+            k_steps = int(uniforms.shape[0])
+        elif int(k_steps) > int(uniforms.shape[0]):
+            raise ValueError(f"k_steps {k_steps} is more than the uniforms tape's {int(uniforms.shape[0])} rows")
+    if k_steps is None:
         raise ValueError("playout_codes needs k_steps when there is no tape")
+    if rates is not None:
+        rates = _slide_rates(rates, n, c.device, "playout_codes")
     cp, ap = nat.ptr(c), nat.ptr(a)                                   # host tensors are refused here
     if a is not None and a.device != c.device:
         raise ValueError(f"the tape must be on {c.device}, got {a.device}")
     steps = torch.empty(n, dtype=torch.int32, device=c.device)
     winner = torch.empty(n, dtype=torch.int8, device=c.device)
     final = torch.empty_like(c) if want_codes else None
+    key = (seed & 0xFFFFFFFF, stream_id & 0xFFFFFFFF, int(call) & 0xFFFFFFFFFFFFFFFF)
     with torch.cuda.device(c.device):
-        nat.check(nat.lib().tron_playout_codes(cp, n, side, int(k_steps), ap, seed & 0xFFFFFFFF, stream_id & 0xFFFFFFFF,
-                                               int(call) & 0xFFFFFFFFFFFFFFFF, nat.ptr(steps), nat.ptr(winner),
-                                               nat.ptr(final), nat.stream_ptr()), "tron_playout_codes")
+        if rates is None:
+            nat.check(nat.lib().tron_playout_codes(cp, n, side, int(k_steps), ap, *key, nat.ptr(steps), nat.ptr(winner),
+                                                   nat.ptr(final), nat.stream_ptr()), "tron_playout_codes")
+        else:
+            nat.check(nat.lib().tron_playout_slide_codes(cp, n, side, int(k_steps), ap, nat.ptr(rates), nat.ptr(uniforms), *key,
+                                                         nat.ptr(steps), nat.ptr(winner), nat.ptr(final), nat.stream_ptr()),
+                      "tron_playout_slide_codes")
     return steps, winner, final
 
 
-def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, want_actions=True):
+def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, want_actions=True, rates=None):
     """Monte-Carlo move values of a stack of observation-code boards int8 [n, S, S] (tron_playout_values): every board is
     played 16 * copies times, `copies` playouts behind each joint first move (a1, a2), every later move a safe draw.
     Playout (i, a1, a2, j) is what playout_codes does at launch index q = ((i * 16 + a1 * 4 + a2) * copies + j) with board
@@ -424,7 +504,9 @@ def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, w
     made.  Returns (counts int32 [n, 4, 4, 4], steps int32 [n, 4, 4], actions int8 [n, 2] or None): counts[i, a1, a2] =
     how many of those playouts ended as a draw, a win of player 1, a win of player 2, or not within k_steps (all zero for
     a rejected board); steps = the sum of their lengths; actions[i, p] = player p + 1's maximin move on wins of 1 minus
-    wins of 2 (the first of equal moves in UP, RIGHT, DOWN, LEFT order; -1 for a rejected board)."""
+    wins of 2 (the first of equal moves in UP, RIGHT, DOWN, LEFT order; -1 for a rejected board).
+    rates: float64 [n, 2] on the boards' device plays the sliding rule (tron_playout_slide_values): board i's row serves
+    all its playouts, which are playout_codes(rates=...)'s at the same index, with drawn uniforms."""
     c = codes.contiguous()
     if c.dtype != torch.int8 or c.dim() != 3 or c.shape[1] != c.shape[2]:
         raise ValueError(f"playout_values takes int8 boards [n, S, S], got {c.dtype} {tuple(c.shape)}")
@@ -438,14 +520,21 @@ def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, w
         raise ValueError(f"{n} boards x 16 moves x {copies} copies do not fit the 32-bit playout index")
     if copies * k_steps >= 2 ** 31:
         raise ValueError(f"{copies} copies x {k_steps} steps do not fit a 32-bit sum of steps")
+    if rates is not None:
+        rates = _slide_rates(rates, n, c.device, "playout_values")
     cp = nat.ptr(c)                                                    # a host tensor is refused here
     counts = torch.empty(n, 4, 4, 4, dtype=torch.int32, device=c.device)
     steps = torch.empty(n, 4, 4, dtype=torch.int32, device=c.device)
     actions = torch.empty(n, 2, dtype=torch.int8, device=c.device) if want_actions else None
+    key = (seed & 0xFFFFFFFF, stream_id & 0xFFFFFFFF, int(call) & 0xFFFFFFFFFFFFFFFF)
     with torch.cuda.device(c.device):
-        nat.check(nat.lib().tron_playout_values(cp, n, side, k_steps, copies, seed & 0xFFFFFFFF, stream_id & 0xFFFFFFFF,
-                                                int(call) & 0xFFFFFFFFFFFFFFFF, nat.ptr(counts), nat.ptr(steps),
-                                                nat.ptr(actions), nat.stream_ptr()), "tron_playout_values")
+        if rates is None:
+            nat.check(nat.lib().tron_playout_values(cp, n, side, k_steps, copies, *key, nat.ptr(counts), nat.ptr(steps),
+                                                    nat.ptr(actions), nat.stream_ptr()), "tron_playout_values")
+        else:
+            nat.check(nat.lib().tron_playout_slide_values(cp, n, side, k_steps, copies, nat.ptr(rates), *key, nat.ptr(counts),
+                                                          nat.ptr(steps), nat.ptr(actions), nat.stream_ptr()),
+                      "tron_playout_slide_values")
     return counts, steps, actions
 
 

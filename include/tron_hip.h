@@ -452,6 +452,52 @@ int tron_playout_values(const int8_t *codes, int64_t n, int32_t side, int32_t k_
                         int32_t *out_steps,               /* i32[n][4][4]    or NULL */
                         int8_t  *out_actions,             /* i8[n][2]        or NULL */
                         void *stream);
+/* The same two under the SLIDING rule of the "ice" and "temper" modes (game.py:158-178), with one slide rate per player
+ * and board.  Everything not named here — codes, the playable / REJECTED condition, actions, the safe move (the
+ * directions whose target is empty before the step; the cell behind the target is not looked at), out_steps,
+ * out_winner, out_counts, out_actions, the errors, n == 0, k_steps == 0, the side range 6..34 and the output
+ * discipline — is tron_playout_codes' / tron_playout_values'.  A slide tile shows as its owner's body in the codes
+ * (map.py:67-81), so a board image still holds all the rule reads and the calls stay pure functions of their arguments.
+ * One step of a live playout, in the reference's order (both heads' cells hold their owners' trails):
+ *   1. for p = 0, then p = 1: the target t is the head plus the move.  If t is strictly inside the border and EMPTY on
+ *      the board as it stands NOW — for p = 1 after player 1's slide tile of this step, before any new head — the player
+ *      consumes its uniform u: with (double)u <= rates[i][p] cell t takes p's trail (the slide tile) and the head goes
+ *      one cell further in the same direction; otherwise the head is t.  A head thus moves at most one cell past an
+ *      interior cell and never leaves the side x side image.
+ *   2. for p = 0, then p = 1: the player dies if its head is off the interior or its cell is not EMPTY (both slide
+ *      tiles are down by now); then the head is written, so player 2 sees player 1's head.  done / winner as ever.
+ * rates     f64[n][2], required: [i][p] is what player p's uniform meets.  The decision is exactly (double)u <= rate
+ *           for every float u and every double rate: a NaN rate never slides, a negative one never slides under a drawn
+ *           u (which is >= 0), a rate >= 1 always does.  ice: the env's slide for both players; temper: get_rate(degree,
+ *           weight[p]) (game.py:100-102).  With both rates of every board negative and no uniforms tape every output
+ *           equals tron_playout_codes' / tron_playout_values' bit for bit.
+ * uniforms  f32[k_steps][n][2], step-major, or NULL.  With a tape u is its float (read whether or not it is consumed;
+ *           rows after a playout's end are not used).  With NULL u = (word[2 + p] >> 8) * 2^-24 — the env's conversion —
+ *           of the Philox block whose words 0 and 1 are the safe draws: counter (playout index, step, call low, call
+ *           high), key (seed, stream_id).  u is a function of those alone, consumed or not.
+ * out_codes a slide tile as its owner's body; the head bytes are written last, player 2's on top, on a wall or a trail
+ *           cell included (a head that slid onto the border shows there).
+ * tron_playout_slide_values is DEFINED THROUGH tron_playout_slide_codes exactly as tron_playout_values is through
+ * tron_playout_codes: playout (i, a1, a2, j) is index q = ((i * 16 + a1 * 4 + a2) * copies + j) of a launch whose board
+ * q is codes[i] and whose rates row q is rates[i], under the constructed tape and NO uniforms tape: board i's row serves
+ * all its 16 * copies playouts.
+ * TRON_ERR_BAD_ARG additionally: rates == NULL with n > 0.  rates and uniforms are only read.                          */
+int tron_playout_slide_codes(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps,
+                             const int8_t *actions,      /* i8[k_steps][n][2] step-major, or NULL */
+                             const double *rates,        /* f64[n][2], required */
+                             const float  *uniforms,     /* f32[k_steps][n][2] step-major, or NULL = Philox */
+                             uint32_t seed, uint32_t stream_id, uint64_t call,
+                             int32_t *out_steps,         /* i32[n]            or NULL */
+                             int8_t  *out_winner,        /* i8[n]             or NULL */
+                             int8_t  *out_codes,         /* i8[n][side][side] or NULL; may not alias codes */
+                             void *stream);
+int tron_playout_slide_values(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, int32_t copies,
+                              const double *rates,       /* f64[n][2]: board i's row serves all its 16 * copies playouts */
+                              uint32_t seed, uint32_t stream_id, uint64_t call,
+                              int32_t *out_counts,       /* i32[n][4][4][4] or NULL */
+                              int32_t *out_steps,        /* i32[n][4][4]    or NULL */
+                              int8_t  *out_actions,      /* i8[n][2]        or NULL */
+                              void *stream);
 
 /* ---- K-FAC helper of the ACKTR path (Net/kfac.py:28-38 `_extract_patches`; its TODO at kfac.py:9-12
  * asks for this kernel) -------------------------------------------------------------------------- */
