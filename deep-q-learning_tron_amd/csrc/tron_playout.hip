@@ -35,6 +35,26 @@
 //               conversion and one compare per player and step, exact for every float and every double (NaN, negative
 //               and >= 1 rates included) with no threshold to derive.  u comes from the caller's tape, or from words 2
 //               and 3 of the step's Philox block by the env's conversion; without a tape the block is drawn every step.
+//
+// tron_playout_weighted_codes / tron_playout_weighted_values replace the uniform safe draw by one that weighs every safe
+// move by its room (include/tron_hip.h): the four kernel bodies above instantiated once more with WEIGHTED, in which
+// playout_step and playout_step_slide — still the only copies of the rule — take a drawn move from safe_move_weighted
+// instead of safe_move.  The instantiations without it compile to what they were; the four weights are one uint32 kernel
+// argument, wave-uniform, in an SGPR.
+//   the weighted draw  looks at the twelve cells within two steps of the head: the
+//               four targets, the four diagonals (each a neighbour of two targets) and the four cells two steps on in a
+//               straight line (a neighbour of one).  The head is strictly inside the border (playout_start; a player
+//               that left the interior has died and the playout is over), so the targets and the diagonals lie in the
+//               side x side image whatever the board holds.  The cell two steps on lies in it exactly when its target is
+//               strictly inside the border, which is register arithmetic on the head's coordinates (on_board), not a
+//               property of the board: where it is not, the target's own address is read in its place and the result
+//               is discarded.  So every address is inside the lane's own column for any board a caller can pass — a
+//               border cell that reads EMPTY included — and, as none depends on a cell's value, all twelve reads are
+//               ONE round trip in the place of safe_move's four: two round trips per drawn step, as before.  A lane's
+//               cells live in its own bank, so nothing conflicts.
+//               The pick is branch-free: w[a] = byte k(a) of the weights for a safe move and 0 otherwise; if they sum to
+//               0 every safe move weighs 1 (the uniform rule is the same running-sum pick); the move is the number of
+//               running sums that mulhi(u, sum) has reached.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -143,6 +163,48 @@ __device__ __forceinline__ int safe_move(const Board &bd, int S, int r, int c, u
     }
     return cnt ? (int)((cand >> (2u * __umulhi(u, cnt))) & 3u) : 0;
 }
+// The weighted safe move (file header): the same candidates, candidate a weighing byte k(a) of `weights`; the first one
+// whose running sum of weights exceeds mulhi(u, sum).  Candidates that all weigh nothing weigh one each, which is
+// safe_move's pick written as a running sum; UP when there is none.
+__device__ __forceinline__ int safe_move_weighted(const Board &bd, int S, int r, int c, uint32_t u, uint32_t weights)
+{
+    const int at = cell_index(S, r, c);
+    // the twelve cells around the head, one round trip: the four targets, the four diagonals (two targets' neighbour
+    // each) and the four cells two steps on, which lie in the image when their target is strictly inside the border
+    bool e[4], diag[4], far[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        int dr, dc, er, ec;
+        action_delta(a, dr, dc);
+        action_delta((a + 1) & 3, er, ec);
+        const int t = at + dr * S + dc;
+        const bool inside = on_board(S - 2, r + dr, c + dc);
+        e[a] = bd.cell(t) == PO_EMPTY;
+        diag[a] = bd.cell(t + er * S + ec) == PO_EMPTY;                // between directions a and a + 1
+        far[a] = (bd.cell(inside ? t + dr * S + dc : t) == PO_EMPTY) && inside;
+    }
+    uint32_t w[4], cnt = 0u, total = 0u;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const uint32_t k = (uint32_t)diag[(a + 3) & 3] + (uint32_t)diag[a] + (uint32_t)far[a];
+        w[a] = e[a] ? (weights >> (8u * k)) & 0xFFu : 0u;
+        cnt += (uint32_t)e[a];
+        total += w[a];
+    }
+    if (total == 0u) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) w[a] = (uint32_t)e[a];
+        total = cnt;
+    }
+    const uint32_t x = __umulhi(u, total), s0 = w[0], s1 = s0 + w[1], s2 = s1 + w[2];
+    return total ? (int)(x >= s0) + (int)(x >= s1) + (int)(x >= s2) : 0;
+}
+template <bool WEIGHTED>
+__device__ __forceinline__ int drawn_move(const Board &bd, int S, int r, int c, uint32_t u, uint32_t weights)
+{
+    if constexpr (WEIGHTED) return safe_move_weighted(bd, S, r, c, u, weights);
+    else return safe_move(bd, S, r, c, u);
+}
 
 // ---- the phases both kernels are made of ---------------------------------------------------------------------------------
 // Boards in: `count` boards from board `first` on, through groups of GROUP lanes per board.  Lane (gb, sub) packs words
@@ -206,8 +268,11 @@ __device__ __forceinline__ Playout playout_start(uint32_t heads, int S, bool hav
     return po;
 }
 // Step t of the live playout `index`: `now` holds the two players' tape bytes (player 2's in bits 8..15).
+// WEIGHTED (here and in the sliding step): a drawn move is safe_move_weighted under `weights`, else safe_move.
+template <bool WEIGHTED>
 __device__ __forceinline__ void playout_step(const Board &bd, int S, Playout &po, uint32_t now, uint32_t index, int t,
-                                             uint32_t call_lo, uint32_t call_hi, uint32_t seed, uint32_t stream)
+                                             uint32_t call_lo, uint32_t call_hi, uint32_t seed, uint32_t stream,
+                                             uint32_t weights)
 {
     int a[2] = {(int)(int8_t)now, (int)(int8_t)(now >> 8)};
     if ((a[0] | a[1]) < 0) {                                           // a negative byte: one Philox block serves both players
@@ -215,7 +280,7 @@ __device__ __forceinline__ void playout_step(const Board &bd, int S, Playout &po
         philox4x32_10(index, (uint32_t)t, call_lo, call_hi, seed, stream, u);
 #pragma unroll
         for (int p = 0; p < 2; ++p)
-            if (a[p] < 0) a[p] = safe_move(bd, S, po.r[p], po.c[p], u[p]);
+            if (a[p] < 0) a[p] = drawn_move<WEIGHTED>(bd, S, po.r[p], po.c[p], u[p], weights);
     }
     // Game.step: both move, then each is judged on the cell it entered, player 2 after player 1's head is down
     int old[2], f[2];
@@ -253,9 +318,10 @@ __device__ __forceinline__ void playout_step(const Board &bd, int S, Playout &po
 // The same step under the sliding rule (orc_step's order; game.py:158-214): player p's target n[p] is consumed when it is
 // strictly inside the border and EMPTY as the board stands then, and with (double)u[p] <= rate[p] it takes p's trail and
 // the head lands one cell further, on sl[p].  `taped`: u[] holds the caller's uniforms; else words 2 and 3 of the block.
+template <bool WEIGHTED>
 __device__ __forceinline__ void playout_step_slide(const Board &bd, int S, Playout &po, uint32_t now, const double rate[2],
                                                    bool taped, float u0, float u1, uint32_t index, int t, uint32_t call_lo,
-                                                   uint32_t call_hi, uint32_t seed, uint32_t stream)
+                                                   uint32_t call_hi, uint32_t seed, uint32_t stream, uint32_t weights)
 {
     int a[2] = {(int)(int8_t)now, (int)(int8_t)(now >> 8)};
     float u[2] = {u0, u1};
@@ -264,7 +330,7 @@ __device__ __forceinline__ void playout_step_slide(const Board &bd, int S, Playo
         philox4x32_10(index, (uint32_t)t, call_lo, call_hi, seed, stream, x);
 #pragma unroll
         for (int p = 0; p < 2; ++p)
-            if (a[p] < 0) a[p] = safe_move(bd, S, po.r[p], po.c[p], x[p]);
+            if (a[p] < 0) a[p] = drawn_move<WEIGHTED>(bd, S, po.r[p], po.c[p], x[p], weights);
         if (!taped) {                                                  // the env's conversion (tron_env.hip)
             u[0] = (float)(x[2] >> 8) * (1.0f / 16777216.0f);
             u[1] = (float)(x[3] >> 8) * (1.0f / 16777216.0f);
@@ -317,13 +383,15 @@ __device__ __forceinline__ void playout_step_slide(const Board &bd, int S, Playo
 }
 
 // SLIDE: the sliding rule under `rates` f64[n][2] and `uniforms` f32[k_steps][n][2] or nullptr (k_playout_slide); without it
-// the two are not looked at (k_playout).
-template <bool SLIDE>
+// the two are not looked at (k_playout).  WEIGHTED: drawn moves are weighted by `weights`, byte k the weight of room k
+// (k_playout_weighted, k_playout_slide_weighted); without it `weights` is not looked at.
+template <bool SLIDE, bool WEIGHTED>
 __global__ __launch_bounds__(PO_LANES) void k_playout_t(const int8_t *__restrict__ codes, int64_t n, int S, int k_steps,
                                                         const int8_t *__restrict__ actions, uint32_t seed, uint32_t stream,
                                                         uint32_t call_lo, uint32_t call_hi, int32_t *__restrict__ out_steps,
                                                         int8_t *__restrict__ out_winner, int8_t *__restrict__ out_codes,
-                                                        const double *__restrict__ rates, const float *__restrict__ uniforms)
+                                                        const double *__restrict__ rates, const float *__restrict__ uniforms,
+                                                        uint32_t weights)
 {
     extern __shared__ uint32_t po_lds[];
     const int lane = threadIdx.x, G = S * S, WORDS = (G + 15) >> 4;
@@ -352,7 +420,7 @@ __global__ __launch_bounds__(PO_LANES) void k_playout_t(const int8_t *__restrict
             const uint32_t now = ahead;
             if (tape && po.live && t + 1 < k_steps) ahead = tape_row(t + 1);   // one step ahead of its use
             if (!po.live) continue;
-            playout_step(bd, S, po, now, (uint32_t)idx, t, call_lo, call_hi, seed, stream);
+            playout_step<WEIGHTED>(bd, S, po, now, (uint32_t)idx, t, call_lo, call_hi, seed, stream, weights);
         }
     } else {
         const double rate[2] = {have ? rates[2 * idx] : -1.0, have ? rates[2 * idx + 1] : -1.0};
@@ -366,8 +434,8 @@ __global__ __launch_bounds__(PO_LANES) void k_playout_t(const int8_t *__restrict
             if (tape && po.live && t + 1 < k_steps) ahead = tape_row(t + 1);
             if (utape && po.live && t + 1 < k_steps) uahead = utape_row(t + 1);
             if (!po.live) continue;
-            playout_step_slide(bd, S, po, now, rate, utape != nullptr, unow.x, unow.y, (uint32_t)idx, t, call_lo, call_hi, seed,
-                               stream);
+            playout_step_slide<WEIGHTED>(bd, S, po, now, rate, utape != nullptr, unow.x, unow.y, (uint32_t)idx, t, call_lo,
+                                         call_hi, seed, stream, weights);
         }
     }
     if (have) {
@@ -413,7 +481,8 @@ __global__ __launch_bounds__(PO_LANES) void k_playout_t(const int8_t *__restrict
     }
 }
 
-constexpr auto k_playout = k_playout_t<false>, k_playout_slide = k_playout_t<true>;
+constexpr auto k_playout = k_playout_t<false, false>, k_playout_slide = k_playout_t<true, false>;
+constexpr auto k_playout_weighted = k_playout_t<false, true>, k_playout_slide_weighted = k_playout_t<true, true>;
 
 // ---- Monte-Carlo move values (tron_playout_values) --------------------------------------------------------------------------
 //   k_playout_values  k_playout's lanes and step loop over launch indices q = ((board * 16 + a1 * 4 + a2) * copies + j):
@@ -430,14 +499,15 @@ constexpr int PV_SLOTS = 8;                        // room for the boards of one
 constexpr int PV_ROW = 5;                          // one (board, first move): draws, wins of 1, wins of 2, unfinished, steps
 constexpr int PV_TALLY = PV_SLOTS * 16 * PV_ROW;
 
-// SLIDE: the sliding rule, board i's row of `rates` f64[n][2] for all its playouts (k_playout_values_slide).
-template <bool SLIDE>
+// SLIDE: the sliding rule, board i's row of `rates` f64[n][2] for all its playouts (k_playout_values_slide).  WEIGHTED: as
+// in k_playout_t (k_playout_values_weighted, k_playout_values_slide_weighted).
+template <bool SLIDE, bool WEIGHTED>
 __global__ __launch_bounds__(PO_LANES) void k_playout_values_t(const int8_t *__restrict__ codes, int64_t n, int S, int k_steps,
                                                                uint32_t copies, uint32_t seed, uint32_t stream,
                                                                uint32_t call_lo, uint32_t call_hi,
                                                                int32_t *__restrict__ out_counts,
                                                                int32_t *__restrict__ out_steps,
-                                                               const double *__restrict__ rates)
+                                                               const double *__restrict__ rates, uint32_t weights)
 {
     extern __shared__ uint32_t po_lds[];
     const int lane = threadIdx.x, G = S * S, WORDS = (G + 15) >> 4;
@@ -472,8 +542,10 @@ __global__ __launch_bounds__(PO_LANES) void k_playout_values_t(const int8_t *__r
         if (!__ballot(po.live)) break;
         if (!po.live) continue;
         const uint32_t now = t ? 0xFFFFu : (uint32_t)(move >> 2) | ((uint32_t)(move & 3) << 8);
-        if constexpr (SLIDE) playout_step_slide(bd, S, po, now, rate, false, 0.0f, 0.0f, q, t, call_lo, call_hi, seed, stream);
-        else playout_step(bd, S, po, now, q, t, call_lo, call_hi, seed, stream);
+        if constexpr (SLIDE)
+            playout_step_slide<WEIGHTED>(bd, S, po, now, rate, false, 0.0f, 0.0f, q, t, call_lo, call_hi, seed, stream, weights);
+        else
+            playout_step<WEIGHTED>(bd, S, po, now, q, t, call_lo, call_hi, seed, stream, weights);
     }
 
     // ---- the tallies: winner -1, 0, 1, 2 is class 3, 0, 1, 2
@@ -496,7 +568,9 @@ __global__ __launch_bounds__(PO_LANES) void k_playout_values_t(const int8_t *__r
     }
 }
 
-constexpr auto k_playout_values = k_playout_values_t<false>, k_playout_values_slide = k_playout_values_t<true>;
+constexpr auto k_playout_values = k_playout_values_t<false, false>, k_playout_values_slide = k_playout_values_t<true, false>;
+constexpr auto k_playout_values_weighted = k_playout_values_t<false, true>,
+               k_playout_values_slide_weighted = k_playout_values_t<true, true>;
 
 __global__ __launch_bounds__(256) void k_values_pick(const int32_t *__restrict__ counts, int64_t n, int8_t *__restrict__ out_actions)
 {
@@ -534,10 +608,11 @@ __global__ __launch_bounds__(256) void k_values_pick(const int32_t *__restrict__
 
 }  // namespace
 
-// The two entries of each pair differ in the kernel alone: rates == nullptr launches the mode-None kernel.
+// The entries differ in the kernel alone: rates == nullptr launches a mode-None kernel, weights == nullptr one of the
+// uniform draw (whose `weights` argument is not looked at).
 static int launch_playout(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, const int8_t *actions, const double *rates,
-                          const float *uniforms, uint32_t seed, uint32_t stream_id, uint64_t call, int32_t *out_steps,
-                          int8_t *out_winner, int8_t *out_codes, void *stream)
+                          const float *uniforms, const uint32_t *weights, uint32_t seed, uint32_t stream_id, uint64_t call,
+                          int32_t *out_steps, int8_t *out_winner, int8_t *out_codes, void *stream)
 {
     if (n < 0 || n > 0x7FFFFFFF || k_steps < 0 || (!codes && n > 0) || (out_codes && out_codes == codes)) return TRON_ERR_BAD_ARG;
     if (side < 6 || side > 34) return TRON_ERR_UNSUPPORTED;
@@ -546,12 +621,10 @@ static int launch_playout(const int8_t *codes, int64_t n, int32_t side, int32_t 
     const size_t smem = (size_t)(words + 1) * PO_LANES * sizeof(uint32_t);     // 18 944 bytes at side 34: no LDS opt-in
     const dim3 grid((unsigned)((n + PO_LANES - 1) / PO_LANES));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (rates)
-        hipLaunchKernelGGL(k_playout_slide, grid, dim3(PO_LANES), smem, st, codes, n, side, k_steps, actions, seed, stream_id,
-                           (uint32_t)call, (uint32_t)(call >> 32), out_steps, out_winner, out_codes, rates, uniforms);
-    else
-        hipLaunchKernelGGL(k_playout, grid, dim3(PO_LANES), smem, st, codes, n, side, k_steps, actions, seed, stream_id,
-                           (uint32_t)call, (uint32_t)(call >> 32), out_steps, out_winner, out_codes, nullptr, nullptr);
+    const auto kernel = weights ? (rates ? k_playout_slide_weighted : k_playout_weighted) : (rates ? k_playout_slide : k_playout);
+    hipLaunchKernelGGL(kernel, grid, dim3(PO_LANES), smem, st, codes, n, side, k_steps, actions, seed, stream_id, (uint32_t)call,
+                       (uint32_t)(call >> 32), out_steps, out_winner, out_codes, rates, rates ? uniforms : nullptr,
+                       weights ? *weights : 0u);
     return hipGetLastError() == hipSuccess ? TRON_OK : TRON_ERR_LAUNCH;
 }
 
@@ -559,8 +632,8 @@ extern "C" int tron_playout_codes(const int8_t *codes, int64_t n, int32_t side, 
                                   uint32_t seed, uint32_t stream_id, uint64_t call, int32_t *out_steps, int8_t *out_winner,
                                   int8_t *out_codes, void *stream)
 {
-    return launch_playout(codes, n, side, k_steps, actions, nullptr, nullptr, seed, stream_id, call, out_steps, out_winner,
-                          out_codes, stream);
+    return launch_playout(codes, n, side, k_steps, actions, nullptr, nullptr, nullptr, seed, stream_id, call, out_steps,
+                          out_winner, out_codes, stream);
 }
 
 extern "C" int tron_playout_slide_codes(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, const int8_t *actions,
@@ -568,13 +641,23 @@ extern "C" int tron_playout_slide_codes(const int8_t *codes, int64_t n, int32_t 
                                         uint64_t call, int32_t *out_steps, int8_t *out_winner, int8_t *out_codes, void *stream)
 {
     if (!rates && n > 0) return TRON_ERR_BAD_ARG;
-    return launch_playout(codes, n, side, k_steps, actions, rates, uniforms, seed, stream_id, call, out_steps, out_winner,
-                          out_codes, stream);
+    return launch_playout(codes, n, side, k_steps, actions, rates, uniforms, nullptr, seed, stream_id, call, out_steps,
+                          out_winner, out_codes, stream);
+}
+
+extern "C" int tron_playout_weighted_codes(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, const int8_t *actions,
+                                           const double *rates, const float *uniforms, uint32_t weights, uint32_t seed,
+                                           uint32_t stream_id, uint64_t call, int32_t *out_steps, int8_t *out_winner,
+                                           int8_t *out_codes, void *stream)
+{
+    if (uniforms && !rates) return TRON_ERR_BAD_ARG;
+    return launch_playout(codes, n, side, k_steps, actions, rates, uniforms, &weights, seed, stream_id, call, out_steps,
+                          out_winner, out_codes, stream);
 }
 
 static int launch_values(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, int32_t copies, const double *rates,
-                         uint32_t seed, uint32_t stream_id, uint64_t call, int32_t *out_counts, int32_t *out_steps,
-                         int8_t *out_actions, void *stream)
+                         const uint32_t *weights, uint32_t seed, uint32_t stream_id, uint64_t call, int32_t *out_counts,
+                         int32_t *out_steps, int8_t *out_actions, void *stream)
 {
     constexpr int64_t LIMIT = (int64_t)1 << 31;                        // the Philox index and the sums are 32 bits
     if (n < 0 || k_steps < 0 || copies < 1 || (!codes && n > 0)) return TRON_ERR_BAD_ARG;
@@ -596,12 +679,10 @@ static int launch_values(const int8_t *codes, int64_t n, int32_t side, int32_t k
         const size_t smem = ((size_t)(words + 1) * PO_LANES + (size_t)words * PV_SLOTS + PV_TALLY) * sizeof(uint32_t);   // 23 840 bytes at side 34
         const int64_t nq = n * 16 * copies;
         const dim3 grid((unsigned)((nq + PO_LANES - 1) / PO_LANES));
-        if (rates)
-            hipLaunchKernelGGL(k_playout_values_slide, grid, dim3(PO_LANES), smem, st, codes, n, side, k_steps, (uint32_t)copies,
-                               seed, stream_id, (uint32_t)call, (uint32_t)(call >> 32), counts, out_steps, rates);
-        else
-            hipLaunchKernelGGL(k_playout_values, grid, dim3(PO_LANES), smem, st, codes, n, side, k_steps, (uint32_t)copies, seed,
-                               stream_id, (uint32_t)call, (uint32_t)(call >> 32), counts, out_steps, nullptr);
+        const auto kernel = weights ? (rates ? k_playout_values_slide_weighted : k_playout_values_weighted)
+                                    : (rates ? k_playout_values_slide : k_playout_values);
+        hipLaunchKernelGGL(kernel, grid, dim3(PO_LANES), smem, st, codes, n, side, k_steps, (uint32_t)copies, seed, stream_id,
+                           (uint32_t)call, (uint32_t)(call >> 32), counts, out_steps, rates, weights ? *weights : 0u);
         if (out_actions)
             hipLaunchKernelGGL(k_values_pick, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, counts, n, out_actions);
     }
@@ -614,7 +695,8 @@ extern "C" int tron_playout_values(const int8_t *codes, int64_t n, int32_t side,
                                    uint32_t stream_id, uint64_t call, int32_t *out_counts, int32_t *out_steps,
                                    int8_t *out_actions, void *stream)
 {
-    return launch_values(codes, n, side, k_steps, copies, nullptr, seed, stream_id, call, out_counts, out_steps, out_actions, stream);
+    return launch_values(codes, n, side, k_steps, copies, nullptr, nullptr, seed, stream_id, call, out_counts, out_steps, out_actions,
+                         stream);
 }
 
 extern "C" int tron_playout_slide_values(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, int32_t copies,
@@ -622,5 +704,15 @@ extern "C" int tron_playout_slide_values(const int8_t *codes, int64_t n, int32_t
                                          int32_t *out_counts, int32_t *out_steps, int8_t *out_actions, void *stream)
 {
     if (!rates && n > 0) return TRON_ERR_BAD_ARG;
-    return launch_values(codes, n, side, k_steps, copies, rates, seed, stream_id, call, out_counts, out_steps, out_actions, stream);
+    return launch_values(codes, n, side, k_steps, copies, rates, nullptr, seed, stream_id, call, out_counts, out_steps, out_actions,
+                         stream);
+}
+
+extern "C" int tron_playout_weighted_values(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, int32_t copies,
+                                            const double *rates, uint32_t weights, uint32_t seed, uint32_t stream_id,
+                                            uint64_t call, int32_t *out_counts, int32_t *out_steps, int8_t *out_actions,
+                                            void *stream)
+{
+    return launch_values(codes, n, side, k_steps, copies, rates, &weights, seed, stream_id, call, out_counts, out_steps,
+                         out_actions, stream);
 }

@@ -6,6 +6,7 @@ state lives in HBM behind a `tron_handle` (include/tron_hip.h); this class only
 owns the output tensors and launches kernels on torch's current stream.
 """
 import ctypes as C
+import numbers
 
 import torch
 
@@ -280,21 +281,24 @@ class VecTron:
                       "tron_minimax_actions")
         return (out, values, expanded) if want_values else out
 
-    def playout(self, actions=None, k_steps=None, copies=1, call=0, want_codes=False, rates=None, uniforms=None):
+    def playout(self, actions=None, k_steps=None, copies=1, call=0, want_codes=False, rates=None, uniforms=None,
+                weights=None):
         """playout_codes on every env's current board, `copies` times each: playout i * copies + j is env i, and the tape
         (if any) is int8 [K, N * copies, 2].  The boards are the player-1 codes — the attached buffer's plane, or a fresh
         encode("codes") — and the draws are keyed by this env's seed and rank; the env itself is left exactly as it was.
         rates=None plays mode None's rule and is for mode None only; rates=True plays the sliding rule under
         slide_rates(), a float64 [N, 2] tensor under the caller's rates (either in any mode; `uniforms`, float32
-        [K, N * copies, 2], replaces the drawn slide uniforms).  Returns (steps, winner, final_codes | None) as
-        playout_codes does; a finished env's row is what playout_codes makes of its image."""
+        [K, N * copies, 2], replaces the drawn slide uniforms).  weights: four ints 0..255 (HUG_WEIGHTS) weigh the drawn
+        moves by their room as playout_codes does; None is the uniform draw.  Returns (steps, winner, final_codes | None)
+        as playout_codes does; a finished env's row is what playout_codes makes of its image."""
         rates = self._playout_rates(rates, "playout")
         if int(copies) < 1:
             raise ValueError("copies is at least 1")
         if rates is not None:
             rates = rates.repeat_interleave(int(copies), dim=0)
         return playout_codes(self._p1_codes().repeat_interleave(int(copies), dim=0), actions, k_steps, seed=self.seed,
-                             stream_id=self.rank, call=call, want_codes=want_codes, rates=rates, uniforms=uniforms)
+                             stream_id=self.rank, call=call, want_codes=want_codes, rates=rates, uniforms=uniforms,
+                             weights=weights)
 
     def slide_rates(self):
         """float64 [N, 2] on the device: the rate each player's `random.random() <= rate` meets in this env's mode
@@ -335,24 +339,25 @@ class VecTron:
             return self.obs[:, 0]
         return self.encode("codes", out=self._alloc_obs(nat.OBS_CODES_I8))[:, 0]
 
-    def playout_values(self, k_steps, copies=1, call=0, want_actions=True, rates=None):
+    def playout_values(self, k_steps, copies=1, call=0, want_actions=True, rates=None, weights=None):
         """playout_values on every env's current board (no board is copied): (counts int32 [N, 4, 4, 4], steps int32
         [N, 4, 4], actions int8 [N, 2] | None), the draws keyed by this env's seed and rank.  The env itself is left
         exactly as it was.  rates as in playout: None is mode None's rule and mode None only, True this env's
-        slide_rates(), a tensor the caller's.  A finished env's row is what playout_values makes of its image."""
+        slide_rates(), a tensor the caller's; weights as in playout.  A finished env's row is what playout_values makes of its
+        image."""
         rates = self._playout_rates(rates, "playout_values")
         return playout_values(self._p1_codes(), k_steps, copies, seed=self.seed, stream_id=self.rank, call=call,
-                              want_actions=want_actions, rates=rates)
+                              want_actions=want_actions, rates=rates, weights=weights)
 
-    def montecarlo_actions(self, player, k_steps=None, copies=4, call=0, out=None, rates=None):
+    def montecarlo_actions(self, player, k_steps=None, copies=4, call=0, out=None, rates=None, weights=None):
         """The flat Monte-Carlo opponent, minimax_actions' counterpart: int8 [N], `player`'s (1|2) maximin move over the
-        tallies of playout_values(k_steps, copies, call, rates=rates) — 16 * copies random playouts of at most k_steps
-        (default W * W) steps per env.  Pass the step number as `call` so that every step draws its own playouts, and
-        rates=True in a sliding mode."""
+        tallies of playout_values(k_steps, copies, call, rates=rates, weights=weights) — 16 * copies random playouts of at
+        most k_steps (default W * W) steps per env.  Pass the step number as `call` so that every step draws its own
+        playouts, rates=True in a sliding mode, and weights (HUG_WEIGHTS) for playouts that prefer room."""
         if int(player) not in (1, 2):
             raise ValueError("player is 1 or 2")
         k_steps = self.W * self.W if k_steps is None else k_steps
-        actions = self.playout_values(k_steps, copies, call, rates=rates)[2][:, int(player) - 1]
+        actions = self.playout_values(k_steps, copies, call, rates=rates, weights=weights)[2][:, int(player) - 1]
         if out is None:
             return actions.contiguous()
         out.copy_(actions)
@@ -431,8 +436,26 @@ def _slide_rates(rates, n, device, what):
     return rates
 
 
+HUG_WEIGHTS = (0, 4, 2, 1)                                              # measured: profiles/r27_playout_policy_match.txt
+
+
+def _packed_weights(weights, what):
+    """The checked weights argument of playout_codes / playout_values as the entries take it: byte k is w[k]."""
+    try:
+        w = list(weights)
+    except TypeError:
+        raise TypeError(f"{what}: weights is None or a sequence of four ints 0..255") from None
+    if len(w) != 4:
+        raise ValueError(f"{what}: weights are four, one per room 0..3, got {len(w)}")
+    if not all(isinstance(x, numbers.Integral) and not isinstance(x, bool) for x in w):
+        raise TypeError(f"{what}: weights are ints, got {[type(x).__name__ for x in w]}")
+    if not all(0 <= x <= 255 for x in w):
+        raise ValueError(f"{what}: weights are 0..255, got {[int(x) for x in w]}")
+    return sum(int(x) << (8 * k) for k, x in enumerate(w))
+
+
 def playout_codes(codes, actions=None, k_steps=None, seed=0x5EED, stream_id=0, call=0, want_codes=False, rates=None,
-                  uniforms=None):
+                  uniforms=None, weights=None):
     """Plays a stack of observation-code boards int8 [n, S, S] (player 1's view: encode_codes(.., 1), a VecTron's
     obs[:, 0]) forward up to k_steps steps of mode None's Game.step, without restart (tron_playout_codes).  Returns
     (steps int32 [n], winner int8 [n], final_codes int8 [n, S, S] or None): steps played, 0 draw / 1 / 2 / -1 not
@@ -443,11 +466,17 @@ def playout_codes(codes, actions=None, k_steps=None, seed=0x5EED, stream_id=0, c
     pass another `call` for another set of playouts of the same boards; a fork is a repeat_interleave of the codes.
     rates: float64 [n, 2] on the boards' device plays the sliding rule of "ice" / "temper" instead
     (tron_playout_slide_codes): player p of board i slides when (double)u <= rates[i, p], u from words 2 and 3 of the
-    step's Philox block, or from `uniforms`, a float32 tape [K, n, 2]; a slide tile shows as its owner's body."""
+    step's Philox block, or from `uniforms`, a float32 tape [K, n, 2]; a slide tile shows as its owner's body.
+    weights: four ints 0..255 weigh every drawn move by its room under either rule (tron_playout_weighted_codes):
+    weights[k] is the weight of a safe move whose target has k EMPTY cells among its three neighbours other than the
+    mover's head, and the move is the first safe one whose running sum of weights exceeds mulhi(u, sum) at the word u the
+    uniform draw uses; safe moves that all weigh 0 are drawn uniformly.  Four equal weights are the uniform draw bit
+    for bit; HUG_WEIGHTS is a preset that prefers tight cells.  None calls the entries without weights."""
     c = codes.contiguous()
     if c.dtype != torch.int8 or c.dim() != 3 or c.shape[1] != c.shape[2]:
         raise ValueError(f"playout_codes takes int8 boards [n, S, S], got {c.dtype} {tuple(c.shape)}")
     n, side = int(c.shape[0]), int(c.shape[-1])
+    packed = None if weights is None else _packed_weights(weights, "playout_codes")
     a = None
     if actions is not None:
         if actions.dtype != torch.int8 or actions.dim() != 3 or tuple(actions.shape[1:]) != (n, 2):
@@ -486,7 +515,11 @@ def playout_codes(codes, actions=None, k_steps=None, seed=0x5EED, stream_id=0, c
     final = torch.empty_like(c) if want_codes else None
     key = (seed & 0xFFFFFFFF, stream_id & 0xFFFFFFFF, int(call) & 0xFFFFFFFFFFFFFFFF)
     with torch.cuda.device(c.device):
-        if rates is None:
+        if packed is not None:
+            nat.check(nat.lib().tron_playout_weighted_codes(cp, n, side, int(k_steps), ap, nat.ptr(rates), nat.ptr(uniforms), packed,
+                                                            *key, nat.ptr(steps), nat.ptr(winner), nat.ptr(final),
+                                                            nat.stream_ptr()), "tron_playout_weighted_codes")
+        elif rates is None:
             nat.check(nat.lib().tron_playout_codes(cp, n, side, int(k_steps), ap, *key, nat.ptr(steps), nat.ptr(winner),
                                                    nat.ptr(final), nat.stream_ptr()), "tron_playout_codes")
         else:
@@ -496,7 +529,7 @@ def playout_codes(codes, actions=None, k_steps=None, seed=0x5EED, stream_id=0, c
     return steps, winner, final
 
 
-def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, want_actions=True, rates=None):
+def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, want_actions=True, rates=None, weights=None):
     """Monte-Carlo move values of a stack of observation-code boards int8 [n, S, S] (tron_playout_values): every board is
     played 16 * copies times, `copies` playouts behind each joint first move (a1, a2), every later move a safe draw.
     Playout (i, a1, a2, j) is what playout_codes does at launch index q = ((i * 16 + a1 * 4 + a2) * copies + j) with board
@@ -506,11 +539,14 @@ def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, w
     a rejected board); steps = the sum of their lengths; actions[i, p] = player p + 1's maximin move on wins of 1 minus
     wins of 2 (the first of equal moves in UP, RIGHT, DOWN, LEFT order; -1 for a rejected board).
     rates: float64 [n, 2] on the boards' device plays the sliding rule (tron_playout_slide_values): board i's row serves
-    all its playouts, which are playout_codes(rates=...)'s at the same index, with drawn uniforms."""
+    all its playouts, which are playout_codes(rates=...)'s at the same index, with drawn uniforms.
+    weights: four ints 0..255 as in playout_codes (tron_playout_weighted_values): every move behind the first is
+    playout_codes(weights=...)'s at the same index, under either rule."""
     c = codes.contiguous()
     if c.dtype != torch.int8 or c.dim() != 3 or c.shape[1] != c.shape[2]:
         raise ValueError(f"playout_values takes int8 boards [n, S, S], got {c.dtype} {tuple(c.shape)}")
     n, side = int(c.shape[0]), int(c.shape[-1])
+    packed = None if weights is None else _packed_weights(weights, "playout_values")
     k_steps, copies = int(k_steps), int(copies)
     if k_steps < 0:
         raise ValueError("k_steps is at least 0")
@@ -528,7 +564,11 @@ def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, w
     actions = torch.empty(n, 2, dtype=torch.int8, device=c.device) if want_actions else None
     key = (seed & 0xFFFFFFFF, stream_id & 0xFFFFFFFF, int(call) & 0xFFFFFFFFFFFFFFFF)
     with torch.cuda.device(c.device):
-        if rates is None:
+        if packed is not None:
+            nat.check(nat.lib().tron_playout_weighted_values(cp, n, side, k_steps, copies, nat.ptr(rates), packed, *key,
+                                                             nat.ptr(counts), nat.ptr(steps), nat.ptr(actions), nat.stream_ptr()),
+                      "tron_playout_weighted_values")
+        elif rates is None:
             nat.check(nat.lib().tron_playout_values(cp, n, side, k_steps, copies, *key, nat.ptr(counts), nat.ptr(steps),
                                                     nat.ptr(actions), nat.stream_ptr()), "tron_playout_values")
         else:

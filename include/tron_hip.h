@@ -498,6 +498,45 @@ int tron_playout_slide_values(const int8_t *codes, int64_t n, int32_t side, int3
                               int32_t *out_steps,        /* i32[n][4][4]    or NULL */
                               int8_t  *out_actions,      /* i8[n][2]        or NULL */
                               void *stream);
+/* The same four with a WEIGHTED safe draw: every drawn move (a negative tape byte, no tape, every move of a values
+ * playout behind the first) prefers targets by the room around them.  Everything not named here is the entry's above
+ * that the arguments select: rates == NULL plays tron_playout_codes' / tron_playout_values' rule, anything else
+ * tron_playout_slide_codes' / tron_playout_slide_values' (where `uniforms`, words 2 and 3 of the block and the
+ * (double)u <= rate decision are untouched).
+ * weights   four weights 0..255 packed into one word: byte k (bits 8k..8k+7) is w[k], the weight of a target of room k.
+ * The room k(a) of a move a whose target n is EMPTY on the board as it stands (the heads' cells hold trails, as the
+ * safe move sees it): the number of EMPTY cells among the three neighbours of n other than the mover's head, 0..3.
+ * A neighbour outside the side x side image (n on the border ring: never on a board the env made) is not EMPTY.  The
+ * opponent's move of the same step is not anticipated, and under the sliding rule the room is still that of the plain
+ * target n, not of the landing cell.
+ * The draw of one player and step, u = word p of the step's Philox block (the word the uniform draw uses):
+ *   1. the candidates are the moves in UP, RIGHT, DOWN, LEFT order whose target is EMPTY, cnt of them; none: UP.
+ *   2. T = the sum of w[k(a)] over the candidates.  T > 0: x = mulhi(u, T), and the move is the first candidate, in
+ *      that order, whose running sum of weights exceeds x (a candidate of weight 0 is never taken).  T == 0: the move
+ *      is candidates[mulhi(u, cnt)], the uniform rule.
+ * Hence four equal weights — (1,1,1,1), (255,255,255,255), (0,0,0,0) — give every output of the entry above bit for
+ * bit, and a single non-zero weight makes the move independent of u wherever exactly one candidate has that room.
+ * tron_playout_weighted_values is DEFINED THROUGH tron_playout_weighted_codes as the two pairs above: playout
+ * (i, a1, a2, j) is index q = ((i * 16 + a1 * 4 + a2) * copies + j) of a launch with the same key, rates row and weights.
+ * TRON_ERR_BAD_ARG additionally: uniforms without rates.                                                              */
+int tron_playout_weighted_codes(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps,
+                                const int8_t *actions,   /* i8[k_steps][n][2] step-major, or NULL */
+                                const double *rates,     /* f64[n][2], or NULL = mode None's rule */
+                                const float  *uniforms,  /* f32[k_steps][n][2] step-major, or NULL = Philox; needs rates */
+                                uint32_t weights,        /* w[0] | w[1] << 8 | w[2] << 16 | w[3] << 24 */
+                                uint32_t seed, uint32_t stream_id, uint64_t call,
+                                int32_t *out_steps,      /* i32[n]            or NULL */
+                                int8_t  *out_winner,     /* i8[n]             or NULL */
+                                int8_t  *out_codes,      /* i8[n][side][side] or NULL; may not alias codes */
+                                void *stream);
+int tron_playout_weighted_values(const int8_t *codes, int64_t n, int32_t side, int32_t k_steps, int32_t copies,
+                                 const double *rates,    /* f64[n][2], or NULL = mode None's rule */
+                                 uint32_t weights,       /* as above */
+                                 uint32_t seed, uint32_t stream_id, uint64_t call,
+                                 int32_t *out_counts,    /* i32[n][4][4][4] or NULL */
+                                 int32_t *out_steps,     /* i32[n][4][4]    or NULL */
+                                 int8_t  *out_actions,   /* i8[n][2]        or NULL */
+                                 void *stream);
 
 /* ---- K-FAC helper of the ACKTR path (Net/kfac.py:28-38 `_extract_patches`; its TODO at kfac.py:9-12
  * asks for this kernel) -------------------------------------------------------------------------- */
