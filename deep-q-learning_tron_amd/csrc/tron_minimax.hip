@@ -25,6 +25,7 @@
 
 #include "../../include/tron_hip.h"
 #include "tron_device.hpp"
+#include "tron_flood.hpp"
 #include "tron_minimax.hpp"
 
 namespace {
@@ -34,40 +35,8 @@ using namespace tron;
 constexpr int MM_BLOCK = 256;
 constexpr int MM_WAVES = MM_BLOCK / 64;
 
-// whole-wave shifts by one lane on the DPP path (no LDS crossbar round trip): wave_shr:1 hands lane
-// r the value of lane r-1, wave_shl:1 that of lane r+1; the lane with no source keeps `old` = 0
-__device__ __forceinline__ uint32_t dpp_from_above(uint32_t v)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, false);
-}
-__device__ __forceinline__ uint32_t dpp_from_below(uint32_t v)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xF, 0xF, false);
-}
-template <typename M>
-__device__ __forceinline__ M from_row_above(M v)                     // lane r <- lane r-1
-{
-    if constexpr (sizeof(M) == 8)
-        return (M)(((uint64_t)dpp_from_above((uint32_t)(v >> 32)) << 32) | dpp_from_above((uint32_t)v));
-    else
-        return (M)dpp_from_above((uint32_t)v);
-}
-template <typename M>
-__device__ __forceinline__ M from_row_below(M v)                     // lane r <- lane r+1
-{
-    if constexpr (sizeof(M) == 8)
-        return (M)(((uint64_t)dpp_from_below((uint32_t)(v >> 32)) << 32) | dpp_from_below((uint32_t)v));
-    else
-        return (M)dpp_from_below((uint32_t)v);
-}
-// sums / minima over the GROUP consecutive lanes that hold one board (every lane gets the result)
-template <int GROUP>
-__device__ __forceinline__ int group_sum(int v)
-{
-#pragma unroll
-    for (int o = GROUP / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
+// the DPP row shifts, group_sum and popc: tron_flood.hpp (shared with tron_territory.hip)
+// minima over the GROUP consecutive lanes that hold one board (every lane gets the result)
 template <int GROUP>
 __device__ __forceinline__ uint32_t group_min_u32(uint32_t v)
 {
@@ -77,12 +46,6 @@ __device__ __forceinline__ uint32_t group_min_u32(uint32_t v)
         v = w < v ? w : v;
     }
     return v;
-}
-template <typename M>
-__device__ __forceinline__ int popc(M v)
-{
-    if constexpr (sizeof(M) == 8) return __popcll((unsigned long long)v);
-    else return __popc((uint32_t)v);
 }
 template <typename M>
 __device__ __forceinline__ int ctz(M v)          // v != 0

@@ -716,3 +716,13 @@ extern "C" int tron_playout_weighted_values(const int8_t *codes, int64_t n, int3
     return launch_values(codes, n, side, k_steps, copies, rates, &weights, seed, stream_id, call, out_counts, out_steps,
                          out_actions, stream);
 }
+
+// k_values_pick alone, on counts the caller tallied itself (tron.vec.playout_values(judge=...)).
+extern "C" int tron_values_pick(const int32_t *counts, int64_t n, int8_t *out_actions, void *stream)
+{
+    if (n < 0 || n > 0x7FFFFFFF || ((!counts || !out_actions) && n > 0)) return TRON_ERR_BAD_ARG;
+    if (n == 0) return TRON_OK;
+    hipLaunchKernelGGL(k_values_pick, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), counts,
+                       n, out_actions);
+    return hipGetLastError() == hipSuccess ? TRON_OK : TRON_ERR_LAUNCH;
+}

@@ -1,0 +1,217 @@
+// tron_territory.hip — who reaches which cell first (tron_territory_codes, include/tron_hip.h): for every board of a stack
+// of observation-code images, both players' breadth-first floods over the open cells, counted and, if asked for, written
+// out as an owner plane.  A pure function of its arguments: no handle, nothing to invalidate.
+//
+//   k_territory   the layout voronoi() in tron_minimax.hip proves out: one lane per board ROW, the row a bit mask (bit c =
+//               column c), GROUP lanes per board and 64 / GROUP boards per wave.  Both floods advance level by level —
+//               left / right are shifts within the mask, up / down one DPP wave shift each (tron_flood.hpp) — and every
+//               newly reached cell is classified on the spot into one of three masks: reached by player 1 first, by
+//               player 2 first, by both at the same level.  The loop leaves on __ballot of the frontiers, so a wave runs
+//               as many levels as its deepest board needs.
+//   the leak    a wave shift carries a row into the neighbouring board's lanes.  What stops it is the OPEN mask, not the
+//               data: a board's row 0 and row S - 1 (and every lane behind row S - 1) have an open mask of 0 and columns 0
+//               and S - 1 are cleared in every row, whatever bytes the caller's border ring holds.  A frontier is always
+//               a subset of the open mask (the heads' start bits are strictly inside too: a board whose head is not is
+//               rejected and floods nothing), so a board's first and last lane never hold a frontier bit and the
+//               neighbouring board is handed zeros.
+//   boards in   as the playouts bring them in (tron_playout.hip's load16, copied here: that file is left as it is): 16-byte
+//               aligned chunks put together with v_alignbyte whatever a board's base address is; a chunk that sticks out
+//               of the caller's buffer is read byte by byte inside it.  A chunk becomes 16 bits in each of three bit
+//               planes in LDS (open, +10, -10), and a row lane takes its S bits out of three consecutive words.
+//   owner out   the row lanes expand their masks to bytes in an LDS tile; the tile goes out in 16-byte chunks, one 16-byte
+//               store where the address allows it.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/tron_hip.h"
+#include "tron_flood.hpp"
+
+namespace {
+
+using namespace tron;
+
+constexpr int TT_BLOCK = 256;
+constexpr int TT_WAVES = TT_BLOCK / 64;
+
+// The 16 bytes at offset `at` (16-byte aligned as an address) of base[0, total); bytes outside the buffer read as 0 and are
+// not loaded.
+__device__ __forceinline__ uint4 chunk16(const int8_t *__restrict__ base, int64_t total, int64_t at)
+{
+    if (at >= 0 && at + 16 <= total) return *reinterpret_cast<const uint4 *>(base + at);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        if (at + i >= 0 && at + i < total) w[i >> 2] |= (uint32_t)(uint8_t)base[at + i] << (8 * (i & 3));
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+// The 16 bytes at offset f of base[0, total) from the two aligned chunks that hold them.
+__device__ __forceinline__ void load16(const int8_t *__restrict__ base, int64_t total, int64_t f, uint32_t out[4])
+{
+    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(base + f) & 15u);
+    const uint4 c0 = chunk16(base, total, f - mis), c1 = mis ? chunk16(base, total, f - mis + 16) : make_uint4(0u, 0u, 0u, 0u);
+    uint32_t t[9] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, 0u};
+    if (mis & 8u) {
+#pragma unroll
+        for (int j = 0; j < 7; ++j) t[j] = t[j + 2];
+    }
+    if (mis & 4u) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) t[j] = t[j + 1];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) out[j] = __builtin_amdgcn_alignbyte(t[j + 1], t[j], mis & 3u);
+}
+// The first nvalid of 16 bytes to p: one 16-byte store where p allows it, dwords where it allows those, else bytes.
+__device__ __forceinline__ void store16(int8_t *p, int nvalid, const uint32_t x[4])
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    if (nvalid == 16 && (a & 15u) == 0u) {
+        *reinterpret_cast<uint4 *>(p) = make_uint4(x[0], x[1], x[2], x[3]);
+        return;
+    }
+    const bool dwords = (a & 3u) == 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (dwords && 4 * j + 4 <= nvalid) {
+            reinterpret_cast<uint32_t *>(p)[j] = x[j];
+        } else {
+#pragma unroll
+            for (int i = 4 * j; i < 4 * j + 4; ++i)
+                if (i < nvalid) p[i] = (int8_t)(x[j] >> (8 * (i & 3)));
+        }
+    }
+}
+
+// Bits [start, start + S) of a bit plane (bit i of the board = bit i & 31 of word i >> 5), S <= 34: three words cover them
+// wherever they start; the plane has two words of slack behind its last cell.
+template <typename M>
+__device__ __forceinline__ M row_bits(const uint32_t *plane, int start, int S)
+{
+    const int k = start >> 5, off = start & 31;
+    uint64_t v = (((uint64_t)plane[k + 1] << 32) | plane[k]) >> off;
+    if (off) v |= (uint64_t)plane[k + 2] << (64 - off);
+    return (M)(v & ((1ull << S) - 1ull));
+}
+
+// LDS of one board: the owner tile (S * S bytes in whole 16-byte chunks), then the three bit planes of `plane_words` words.
+__host__ __device__ inline int plane_words(int G) { return ((G + 31) >> 5) + 2; }
+__host__ __device__ inline int board_lds(int G) { return ((((G + 15) >> 4) << 4) + 12 * plane_words(G) + 15) & ~15; }
+
+// GROUP lanes per board (one lane per row), 64 / GROUP boards per wave, TT_WAVES waves per block.
+template <typename M, int GROUP>
+__global__ __launch_bounds__(TT_BLOCK) void k_territory(const int8_t *__restrict__ codes, int64_t n, int S,
+                                                       int32_t *__restrict__ out_counts, int8_t *__restrict__ out_owner)
+{
+    extern __shared__ uint4 tt_lds[];
+    constexpr int BPW = 64 / GROUP;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int grp = lane / GROUP, row = lane % GROUP, slot = wave * BPW + grp;
+    const int64_t board = (int64_t)blockIdx.x * (TT_WAVES * BPW) + slot;
+    const int G = S * S, CHUNKS = (G + 15) >> 4, PW = plane_words(G);
+    int8_t *tile = reinterpret_cast<int8_t *>(tt_lds) + (size_t)slot * (size_t)board_lds(G);
+    uint32_t *planes = reinterpret_cast<uint32_t *>(tile + CHUNKS * 16);      // [3][PW]: open, +10, -10
+    uint16_t *halves = reinterpret_cast<uint16_t *>(planes);
+    const bool have = board < n;
+    const int64_t total = n * (int64_t)G, base = board * (int64_t)G;
+
+    // ---- the board in: chunk w of the board is 16 bits of each plane
+    if (have) {
+        for (int w = row; w < CHUNKS; w += GROUP) {
+            uint32_t x[4];
+            load16(codes, total, base + 16 * w, x);
+            uint32_t open = 0u, h1 = 0u, h2 = 0u;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int v = (int)(int8_t)(x[i >> 2] >> (8 * (i & 3)));      // bytes behind the board's end belong to no row
+                open |= (uint32_t)(v == 1) << i;
+                h1 |= (uint32_t)(v == 10) << i;
+                h2 |= (uint32_t)(v == -10) << i;
+            }
+            halves[w] = (uint16_t)open;
+            halves[2 * PW + w] = (uint16_t)h1;
+            halves[4 * PW + w] = (uint16_t)h2;
+        }
+    }
+    __syncthreads();
+
+    // ---- my row as masks.  `inner` is the row's cells strictly inside the border: nothing outside it is ever open
+    const M inner = (row >= 1 && row <= S - 2) ? (M)((((M)1 << (S - 2)) - (M)1) << 1) : (M)0;
+    M E = 0, H1 = 0, H2 = 0;
+    if (have && row < S) {
+        E = row_bits<M>(planes, row * S, S) & inner;
+        H1 = row_bits<M>(planes + PW, row * S, S);
+        H2 = row_bits<M>(planes + 2 * PW, row * S, S);
+    }
+    // playable: exactly one +10 and one -10 on the whole image, both strictly inside the border
+    const int all = group_sum<GROUP>(popc<M>(H1) | (popc<M>(H2) << 16));
+    const int in = group_sum<GROUP>(popc<M>(H1 & inner) | (popc<M>(H2 & inner) << 16));
+    const bool playable = have && all == 0x00010001 && in == 0x00010001;
+
+    // ---- both floods, level by level; a rejected or absent board has no frontier and takes no part
+    M f1 = playable ? (M)(H1 & inner) : (M)0, f2 = playable ? (M)(H2 & inner) : (M)0;
+    M vis1 = f1, vis2 = f2, own1 = 0, own2 = 0, tied = 0;
+    while (__ballot((f1 | f2) != 0)) {
+        const M e1 = (M)((f1 << 1) | (f1 >> 1) | from_row_above<M>(f1) | from_row_below<M>(f1));
+        const M e2 = (M)((f2 << 1) | (f2 >> 1) | from_row_above<M>(f2) | from_row_below<M>(f2));
+        const M n1 = e1 & E & ~vis1, n2 = e2 & E & ~vis2;
+        own1 |= n1 & ~vis2 & ~n2;
+        own2 |= n2 & ~vis1 & ~n1;
+        tied |= n1 & n2;
+        vis1 |= n1;
+        vis2 |= n2;
+        f1 = n1;
+        f2 = n2;
+    }
+
+    // ---- the six counts, two to a sum (a board has at most 32 * 32 open cells)
+    if (out_counts) {
+        const int s01 = group_sum<GROUP>(popc<M>(own1) | (popc<M>(own2) << 16));
+        const int s23 = group_sum<GROUP>(popc<M>(tied) | (popc<M>((M)(E & ~vis1 & ~vis2)) << 16));
+        const int s45 = group_sum<GROUP>(popc<M>((M)(E & vis1)) | (popc<M>((M)(E & vis2)) << 16));
+        if (have && row < 6) {
+            const int s = row < 2 ? s01 : row < 4 ? s23 : s45;
+            out_counts[board * 6 + row] = playable ? ((row & 1) ? (s >> 16) : (s & 0xFFFF)) : -1;
+        }
+    }
+    if (!out_owner) return;
+
+    // ---- the owner plane: rows to bytes in the tile, the tile out in 16-byte chunks
+    if (have && row < S) {
+        int8_t *tr = tile + row * S;
+        for (int c = 0; c < S; ++c)
+            tr[c] = (int8_t)(((own1 >> c) & 1) | (((own2 >> c) & 1) << 1) | (((tied >> c) & 1) * 3));
+    }
+    __syncthreads();
+    if (have) {
+        for (int w = row; w < CHUNKS; w += GROUP) {
+            const uint4 q = *reinterpret_cast<const uint4 *>(tile + 16 * w);
+            const uint32_t x[4] = {q.x, q.y, q.z, q.w};
+            store16(out_owner + base + 16 * w, min(16, G - 16 * w), x);
+        }
+    }
+}
+
+template <typename M, int GROUP>
+void launch_territory(const int8_t *codes, int64_t n, int S, int32_t *out_counts, int8_t *out_owner, hipStream_t st)
+{
+    constexpr int per_block = TT_WAVES * (64 / GROUP);
+    const size_t smem = (size_t)per_block * (size_t)board_lds(S * S);          // 6 592 bytes at side 34, 11 520 at side 32
+    const dim3 grid((unsigned)((n + per_block - 1) / per_block));
+    hipLaunchKernelGGL((k_territory<M, GROUP>), grid, dim3(TT_BLOCK), smem, st, codes, n, S, out_counts, out_owner);
+}
+
+}  // namespace
+
+extern "C" int tron_territory_codes(const int8_t *codes, int64_t n, int32_t side, int32_t *out_counts, int8_t *out_owner,
+                                    void *stream)
+{
+    if (n < 0 || n > 0x7FFFFFFF || (!codes && n > 0) || (out_owner && out_owner == codes)) return TRON_ERR_BAD_ARG;
+    if (side < 6 || side > 34) return TRON_ERR_UNSUPPORTED;
+    if (n == 0 || (!out_counts && !out_owner)) return TRON_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (side <= 8) launch_territory<uint32_t, 8>(codes, n, side, out_counts, out_owner, st);
+    else if (side <= 16) launch_territory<uint32_t, 16>(codes, n, side, out_counts, out_owner, st);
+    else if (side <= 32) launch_territory<uint32_t, 32>(codes, n, side, out_counts, out_owner, st);
+    else launch_territory<uint64_t, 64>(codes, n, side, out_counts, out_owner, st);
+    return hipGetLastError() == hipSuccess ? TRON_OK : TRON_ERR_LAUNCH;
+}

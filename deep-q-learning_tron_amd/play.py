@@ -23,7 +23,7 @@ def model_actions(model, planes, prob_plane, env_vec):
 
 
 def rating(model, model2=None, n_games=10000, slides=None, width=10, gamemode="ice", fair=True, seed=0x5EED,
-           max_steps=None, verbose=True, mc_weights=None):
+           max_steps=None, verbose=True, mc_weights=None, mc_judge=None, mc_steps=None):
     """Returns a list of dicts {slide, p1_win, p2_win, draw, p1_rate} (play.py:76-98).
     model2="minimax" seats MinimaxPlayer(2, "voronoi") as player 2 — the "minimax rating" that
     ACKTR.py:408-421 logs (there it is played net against net).  model2="montecarlo" seats the flat Monte-Carlo
@@ -31,7 +31,9 @@ def rating(model, model2=None, n_games=10000, slides=None, width=10, gamemode="i
     playouts follow mode None's rule, so it sits only in gamemode None / "none".  model2="montecarlo-slide" seats the same
     opponent with rates=True — its playouts follow the env's own rule under every game's own slide rates — in any
     gamemode, the default ice sweep included.  mc_weights: the weights= of either Monte-Carlo seat's playouts (four ints
-    0..255, tron.vec.HUG_WEIGHTS: drawn moves weighed by their room); None is the uniform draw."""
+    0..255, tron.vec.HUG_WEIGHTS: drawn moves weighed by their room); None is the uniform draw.  mc_steps: the k_steps of
+    those playouts (None: width * width); mc_judge="territory" judges the playouts that mc_steps cuts off by territory
+    (VecTron.montecarlo_actions' judge=)."""
     model2 = model2 or model
     if model2 == "montecarlo" and gamemode not in (None, "none"):
         raise ValueError('model2="montecarlo" plays mode None\'s rule: gamemode must be None or "none"')
@@ -52,9 +54,9 @@ def rating(model, model2=None, n_games=10000, slides=None, width=10, gamemode="i
         planes = pop_up_planes(obs.reshape(2 * n, S, S)).view(n, 2, 3, S, S)
         a1 = model_actions(model, planes[:, 0], prob_plane, env1)
         if model2 == "montecarlo":
-            a2 = env.montecarlo_actions(2, call=t, weights=mc_weights)
+            a2 = env.montecarlo_actions(2, k_steps=mc_steps, call=t, weights=mc_weights, judge=mc_judge)
         elif model2 == "montecarlo-slide":
-            a2 = env.montecarlo_actions(2, call=t, rates=True, weights=mc_weights)
+            a2 = env.montecarlo_actions(2, k_steps=mc_steps, call=t, rates=True, weights=mc_weights, judge=mc_judge)
         else:
             a2 = env.minimax_actions(2) if isinstance(model2, str) else model_actions(model2, planes[:, 1], prob_plane, env2)
         obs, _, done, _ = env.step(torch.stack([a1, a2], 1), autoreset=False)

@@ -282,7 +282,7 @@ class VecTron:
         return (out, values, expanded) if want_values else out
 
     def playout(self, actions=None, k_steps=None, copies=1, call=0, want_codes=False, rates=None, uniforms=None,
-                weights=None):
+                weights=None, judge=None):
         """playout_codes on every env's current board, `copies` times each: playout i * copies + j is env i, and the tape
         (if any) is int8 [K, N * copies, 2].  The boards are the player-1 codes — the attached buffer's plane, or a fresh
         encode("codes") — and the draws are keyed by this env's seed and rank; the env itself is left exactly as it was.
@@ -290,7 +290,8 @@ class VecTron:
         slide_rates(), a float64 [N, 2] tensor under the caller's rates (either in any mode; `uniforms`, float32
         [K, N * copies, 2], replaces the drawn slide uniforms).  weights: four ints 0..255 (HUG_WEIGHTS) weigh the drawn
         moves by their room as playout_codes does; None is the uniform draw.  Returns (steps, winner, final_codes | None)
-        as playout_codes does; a finished env's row is what playout_codes makes of its image."""
+        as playout_codes does; a finished env's row is what playout_codes makes of its image.  judge="territory": an
+        unfinished playout's winner is territory_winner's verdict on its last position, as in playout_codes."""
         rates = self._playout_rates(rates, "playout")
         if int(copies) < 1:
             raise ValueError("copies is at least 1")
@@ -298,7 +299,13 @@ class VecTron:
             rates = rates.repeat_interleave(int(copies), dim=0)
         return playout_codes(self._p1_codes().repeat_interleave(int(copies), dim=0), actions, k_steps, seed=self.seed,
                              stream_id=self.rank, call=call, want_codes=want_codes, rates=rates, uniforms=uniforms,
-                             weights=weights)
+                             weights=weights, judge=judge)
+
+    def territory(self, want_owner=False):
+        """territory_codes on every env's current board (the player-1 codes playout takes): (counts int32 [N, 6],
+        owner int8 [N, S, S] | None).  The env itself is left exactly as it was; a finished env's row is what
+        territory_codes makes of its image."""
+        return territory_codes(self._p1_codes(), want_owner=want_owner)
 
     def slide_rates(self):
         """float64 [N, 2] on the device: the rate each player's `random.random() <= rate` meets in this env's mode
@@ -339,25 +346,26 @@ class VecTron:
             return self.obs[:, 0]
         return self.encode("codes", out=self._alloc_obs(nat.OBS_CODES_I8))[:, 0]
 
-    def playout_values(self, k_steps, copies=1, call=0, want_actions=True, rates=None, weights=None):
-        """playout_values on every env's current board (no board is copied): (counts int32 [N, 4, 4, 4], steps int32
+    def playout_values(self, k_steps, copies=1, call=0, want_actions=True, rates=None, weights=None, judge=None):
+        """playout_values on every env's current board (no board is copied unless judge= is given): (counts int32 [N, 4, 4, 4], steps int32
         [N, 4, 4], actions int8 [N, 2] | None), the draws keyed by this env's seed and rank.  The env itself is left
         exactly as it was.  rates as in playout: None is mode None's rule and mode None only, True this env's
-        slide_rates(), a tensor the caller's; weights as in playout.  A finished env's row is what playout_values makes of its
-        image."""
+        slide_rates(), a tensor the caller's; weights and judge as in the function playout_values.  A finished env's row is
+        what playout_values makes of its image."""
         rates = self._playout_rates(rates, "playout_values")
         return playout_values(self._p1_codes(), k_steps, copies, seed=self.seed, stream_id=self.rank, call=call,
-                              want_actions=want_actions, rates=rates, weights=weights)
+                              want_actions=want_actions, rates=rates, weights=weights, judge=judge)
 
-    def montecarlo_actions(self, player, k_steps=None, copies=4, call=0, out=None, rates=None, weights=None):
+    def montecarlo_actions(self, player, k_steps=None, copies=4, call=0, out=None, rates=None, weights=None, judge=None):
         """The flat Monte-Carlo opponent, minimax_actions' counterpart: int8 [N], `player`'s (1|2) maximin move over the
         tallies of playout_values(k_steps, copies, call, rates=rates, weights=weights) — 16 * copies random playouts of at
         most k_steps (default W * W) steps per env.  Pass the step number as `call` so that every step draws its own
-        playouts, rates=True in a sliding mode, and weights (HUG_WEIGHTS) for playouts that prefer room."""
+        playouts, rates=True in a sliding mode, and weights (HUG_WEIGHTS) for playouts that prefer room.  judge="territory"
+        with a short k_steps judges the playouts that k_steps cuts off by territory instead of leaving them out."""
         if int(player) not in (1, 2):
             raise ValueError("player is 1 or 2")
         k_steps = self.W * self.W if k_steps is None else k_steps
-        actions = self.playout_values(k_steps, copies, call, rates=rates, weights=weights)[2][:, int(player) - 1]
+        actions = self.playout_values(k_steps, copies, call, rates=rates, weights=weights, judge=judge)[2][:, int(player) - 1]
         if out is None:
             return actions.contiguous()
         out.copy_(actions)
@@ -455,7 +463,7 @@ def _packed_weights(weights, what):
 
 
 def playout_codes(codes, actions=None, k_steps=None, seed=0x5EED, stream_id=0, call=0, want_codes=False, rates=None,
-                  uniforms=None, weights=None):
+                  uniforms=None, weights=None, judge=None):
     """Plays a stack of observation-code boards int8 [n, S, S] (player 1's view: encode_codes(.., 1), a VecTron's
     obs[:, 0]) forward up to k_steps steps of mode None's Game.step, without restart (tron_playout_codes).  Returns
     (steps int32 [n], winner int8 [n], final_codes int8 [n, S, S] or None): steps played, 0 draw / 1 / 2 / -1 not
@@ -471,7 +479,12 @@ def playout_codes(codes, actions=None, k_steps=None, seed=0x5EED, stream_id=0, c
     weights[k] is the weight of a safe move whose target has k EMPTY cells among its three neighbours other than the
     mover's head, and the move is the first safe one whose running sum of weights exceeds mulhi(u, sum) at the word u the
     uniform draw uses; safe moves that all weigh 0 are drawn uniformly.  Four equal weights are the uniform draw bit
-    for bit; HUG_WEIGHTS is a preset that prefers tight cells.  None calls the entries without weights."""
+    for bit; HUG_WEIGHTS is a preset that prefers tight cells.  None calls the entries without weights.
+    judge: None, or "territory": a playout that comes back unfinished (winner -1) has its last position judged by
+    territory_winner(territory_codes(final)), and the returned winner carries that verdict (1, 2, or 0 for equal
+    territory) in the place of -1; steps and codes are as without it.  The last positions are computed whether or not
+    want_codes asks for them."""
+    _checked_judge(judge, "playout_codes")
     c = codes.contiguous()
     if c.dtype != torch.int8 or c.dim() != 3 or c.shape[1] != c.shape[2]:
         raise ValueError(f"playout_codes takes int8 boards [n, S, S], got {c.dtype} {tuple(c.shape)}")
@@ -512,7 +525,7 @@ def playout_codes(codes, actions=None, k_steps=None, seed=0x5EED, stream_id=0, c
         raise ValueError(f"the tape must be on {c.device}, got {a.device}")
     steps = torch.empty(n, dtype=torch.int32, device=c.device)
     winner = torch.empty(n, dtype=torch.int8, device=c.device)
-    final = torch.empty_like(c) if want_codes else None
+    final = torch.empty_like(c) if want_codes or judge is not None else None
     key = (seed & 0xFFFFFFFF, stream_id & 0xFFFFFFFF, int(call) & 0xFFFFFFFFFFFFFFFF)
     with torch.cuda.device(c.device):
         if packed is not None:
@@ -526,10 +539,47 @@ def playout_codes(codes, actions=None, k_steps=None, seed=0x5EED, stream_id=0, c
             nat.check(nat.lib().tron_playout_slide_codes(cp, n, side, int(k_steps), ap, nat.ptr(rates), nat.ptr(uniforms), *key,
                                                          nat.ptr(steps), nat.ptr(winner), nat.ptr(final), nat.stream_ptr()),
                       "tron_playout_slide_codes")
-    return steps, winner, final
+    if judge is not None:
+        winner = torch.where(winner == -1, territory_winner(territory_codes(final)[0]), winner)
+    return steps, winner, (final if want_codes else None)
 
 
-def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, want_actions=True, rates=None, weights=None):
+def _checked_judge(judge, what):
+    if judge not in (None, "territory"):
+        raise ValueError(f'{what}: judge is None or "territory", got {judge!r}')
+
+
+def territory_codes(codes, want_owner=False):
+    """Who reaches which cell first on a stack of observation-code boards int8 [n, S, S] (tron_territory_codes; the boards
+    playout_codes takes).  Returns (counts int32 [n, 6], owner int8 [n, S, S] or None).  Over a board's open cells — byte
+    1, strictly inside the border; the heads' cells and the border ring are closed — and the breadth-first distances d1,
+    d2 from the +10 and the -10 head: counts = (first1: d1 < d2, first2: d2 < d1, tied: d1 = d2 finite, neither: both
+    infinite, reach1: d1 finite, reach2: d2 finite).  reach1 + reach2 - (first1 + first2 + tied) is 0 exactly when the
+    players are cut off from each other.  owner: 1, 2, 3 on first1, first2 and tied cells, 0 elsewhere.  A rejected board
+    (not exactly one +10 and one -10 inside the border) gets six -1 and an owner plane of zeros."""
+    c = codes.contiguous()
+    if c.dtype != torch.int8 or c.dim() != 3 or c.shape[1] != c.shape[2]:
+        raise ValueError(f"territory_codes takes int8 boards [n, S, S], got {c.dtype} {tuple(c.shape)}")
+    n, side = int(c.shape[0]), int(c.shape[-1])
+    cp = nat.ptr(c)                                                    # a host tensor is refused here
+    counts = torch.empty(n, 6, dtype=torch.int32, device=c.device)
+    owner = torch.empty_like(c) if want_owner else None
+    with torch.cuda.device(c.device):
+        nat.check(nat.lib().tron_territory_codes(cp, n, side, nat.ptr(counts), nat.ptr(owner), nat.stream_ptr()),
+                  "tron_territory_codes")
+    return counts, owner
+
+
+def territory_winner(counts):
+    """The verdict of territory_codes' counts [n, 6] as playout_codes reports winners, int8 [n]: -2 for a rejected row, else
+    1 / 2 for the player that reaches more cells first, 0 for equal territory."""
+    first1, first2 = counts[:, 0], counts[:, 1]
+    verdict = (first1 < first2).to(torch.int8) * 2 + (first1 > first2).to(torch.int8)
+    return torch.where(first1 < 0, torch.full_like(verdict, -2), verdict)
+
+
+def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, want_actions=True, rates=None, weights=None,
+                   judge=None):
     """Monte-Carlo move values of a stack of observation-code boards int8 [n, S, S] (tron_playout_values): every board is
     played 16 * copies times, `copies` playouts behind each joint first move (a1, a2), every later move a safe draw.
     Playout (i, a1, a2, j) is what playout_codes does at launch index q = ((i * 16 + a1 * 4 + a2) * copies + j) with board
@@ -541,7 +591,14 @@ def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, w
     rates: float64 [n, 2] on the boards' device plays the sliding rule (tron_playout_slide_values): board i's row serves
     all its playouts, which are playout_codes(rates=...)'s at the same index, with drawn uniforms.
     weights: four ints 0..255 as in playout_codes (tron_playout_weighted_values): every move behind the first is
-    playout_codes(weights=...)'s at the same index, under either rule."""
+    playout_codes(weights=...)'s at the same index, under either rule.
+    judge: None, or "territory": the playouts that k_steps cuts off are judged by territory (playout_codes(judge=...)) and
+    tallied under that verdict, so counts[..., 3] is 0.  This is the composition the definition above names, actually
+    made: the boards copied 16 * copies times, the tape, playout_codes at the same key (playout q has the Philox index q
+    it has without judge, so where no playout is left unfinished the counts are the same), territory_codes on the last
+    positions, the tallies summed on the device and tron_values_pick.  Memory: two code planes (the copy and the last
+    position, 2 * S * S bytes) and 2 * k_steps tape bytes per playout, n * 16 * copies playouts."""
+    _checked_judge(judge, "playout_values")
     c = codes.contiguous()
     if c.dtype != torch.int8 or c.dim() != 3 or c.shape[1] != c.shape[2]:
         raise ValueError(f"playout_values takes int8 boards [n, S, S], got {c.dtype} {tuple(c.shape)}")
@@ -559,6 +616,8 @@ def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, w
     if rates is not None:
         rates = _slide_rates(rates, n, c.device, "playout_values")
     cp = nat.ptr(c)                                                    # a host tensor is refused here
+    if judge is not None:
+        return _judged_values(c, k_steps, copies, seed, stream_id, call, want_actions, rates, weights, judge)
     counts = torch.empty(n, 4, 4, 4, dtype=torch.int32, device=c.device)
     steps = torch.empty(n, 4, 4, dtype=torch.int32, device=c.device)
     actions = torch.empty(n, 2, dtype=torch.int8, device=c.device) if want_actions else None
@@ -576,6 +635,28 @@ def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, w
                                                           nat.ptr(steps), nat.ptr(actions), nat.stream_ptr()),
                       "tron_playout_slide_values")
     return counts, steps, actions
+
+
+def _judged_values(c, k_steps, copies, seed, stream_id, call, want_actions, rates, weights, judge):
+    """playout_values(judge=...) on checked arguments: the fan-out, playout_codes, the tallies, the pick."""
+    n, per = int(c.shape[0]), 16 * copies
+    tape = torch.full((k_steps, n * per, 2), -1, dtype=torch.int8, device=c.device)
+    if k_steps:
+        move = (torch.arange(n * per, device=c.device) // copies) % 16
+        tape[0, :, 0], tape[0, :, 1] = (move >> 2).to(torch.int8), (move & 3).to(torch.int8)
+    if rates is not None:
+        rates = rates.repeat_interleave(per, dim=0)
+    steps, winner, _ = playout_codes(c.repeat_interleave(per, dim=0), tape, k_steps, seed=seed, stream_id=stream_id, call=call,
+                                     rates=rates, weights=weights, judge=judge)
+    winner = winner.view(n, 4, 4, copies)
+    counts = torch.stack([(winner == w).sum(-1, dtype=torch.int32) for w in (0, 1, 2, -1)], -1).contiguous()
+    total = steps.view(n, 4, 4, copies).sum(-1, dtype=torch.int32)
+    actions = None
+    if want_actions:
+        actions = torch.empty(n, 2, dtype=torch.int8, device=c.device)
+        with torch.cuda.device(c.device):
+            nat.check(nat.lib().tron_values_pick(nat.ptr(counts), n, nat.ptr(actions), nat.stream_ptr()), "tron_values_pick")
+    return counts, total, actions
 
 
 def pop_up_planes(codes):

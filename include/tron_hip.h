@@ -537,6 +537,37 @@ int tron_playout_weighted_values(const int8_t *codes, int64_t n, int32_t side, i
                                  int32_t *out_steps,     /* i32[n][4][4]    or NULL */
                                  int8_t  *out_actions,   /* i8[n][2]        or NULL */
                                  void *stream);
+/* out_actions of the values entries alone, on counts the caller tallied: counts i32[n][4][4][4] -> out_actions i8[n][2],
+ * the maximin of tron_playout_values (a row of all zeros gets -1 for both players).  TRON_ERR_BAD_ARG: n < 0, n >= 2^31,
+ * counts == NULL or out_actions == NULL with n > 0.  n == 0 launches nothing.  counts is only read.                    */
+int tron_values_pick(const int32_t *counts, int64_t n, int8_t *out_actions, void *stream);
+
+/* ---- territory: who reaches which cell first (csrc/tron_territory.hip) ------------------------------------------------
+ * Both players' breadth-first floods on each of n boards, counted and optionally written out cell by cell.  No handle: a
+ * pure function of its arguments, like tron_playout_codes, whose boards it takes.
+ * codes      i8[n][side][side]: player 1's observation of each board, at any base alignment.  A board is playable under
+ *            tron_playout_codes' condition: exactly one +10 and exactly one -10, both strictly inside the border; any
+ *            other board is REJECTED.
+ * open cell  a cell strictly inside the border whose byte is 1.  Everything else is closed: the whole border ring,
+ *            whatever its bytes say, and the heads' own cells (bytes +10 / -10), so a flood never passes through the other
+ *            head.
+ * d_p(cell)  the breadth-first distance from head p (1: the +10, 2: the -10) over open cells, 4-neighbourhood: 1 for an
+ *            open neighbour of the head; infinite where head p cannot reach the cell.
+ * out_counts i32[n][6] or NULL: six numbers over the open cells of board i:
+ *              [0] d1 < d2 ("first1"; d2 may be infinite)     [3] both infinite ("neither")
+ *              [1] d2 < d1 ("first2")                         [4] d1 finite ("reach1")
+ *              [2] d1 = d2, finite ("tied")                   [5] d2 finite ("reach2")
+ *            Hence [0] + [1] + [2] + [3] is the number of open cells, and [4] + [5] - ([0] + [1] + [2]) is the number of
+ *            cells both players reach: 0 exactly when the players are separated.
+ * out_owner  i8[n][side][side] or NULL, not `codes` itself: 1, 2, 3 on first1, first2 and tied cells, 0 everywhere else.
+ * A REJECTED board gets six counts of -1 and an owner plane of all 0.
+ * TRON_ERR_BAD_ARG: codes == NULL with n > 0, n < 0, n >= 2^31, out_owner == codes; TRON_ERR_UNSUPPORTED: side outside
+ * 6..34.  n == 0, or both outputs NULL, launches nothing and returns TRON_OK.  Nothing outside [0, n) of an output is
+ * written, and codes is only read.                                                                                      */
+int tron_territory_codes(const int8_t *codes, int64_t n, int32_t side,
+                         int32_t *out_counts,   /* i32[n][6] or NULL */
+                         int8_t  *out_owner,    /* i8[n][side][side] or NULL */
+                         void *stream);
 
 /* ---- K-FAC helper of the ACKTR path (Net/kfac.py:28-38 `_extract_patches`; its TODO at kfac.py:9-12
  * asks for this kernel) -------------------------------------------------------------------------- */
