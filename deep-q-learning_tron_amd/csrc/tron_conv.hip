@@ -28,10 +28,11 @@
 
 #include "../../include/tron_hip.h"
 #include "tron_conv.hpp"
+#include "tron_mish.hpp"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace tron;
 
 constexpr int CIC = 8;           // input channels per K chunk
 constexpr int KSTEPS = 18;       // 9 taps x 2 channel quads per chunk
@@ -66,22 +67,6 @@ struct Cfg {
     static_assert((CIC - 1) * CI_STRIDE * 4 + (2 * SP + 2) * 4 < 65536, "ds_read immediate offset");
     static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU");
 };
-
-// mish(x) = x * tanh(softplus(x)) = x * n / (n + 2), n = e (e + 2), e = exp(x) (csrc/tron_nn.hip has the derivation).
-// The epilogue runs 72-88 of these per lane with the matrix pipe idle, so it is built from the two hardware
-// transcendentals: exp2 of x * log2(e) — its argument rounding costs |x| 2^-24 relative in e, which mish turns into
-// < 4e-8 ABSOLUTE (x^2 e^x <= 0.55 where e matters, and n / (n + 2) -> 1 where e is large) — and a reciprocal
-// refined by one Newton step (v_rcp_f32 alone is 1 ulp) instead of the ~10-instruction IEEE division.
-__device__ __forceinline__ float mish1(float x)
-{
-    const float e = __builtin_amdgcn_exp2f(x * 1.44269504088896341f);
-    const float n = __fmaf_rn(e, e, e + e);
-    const float d = n + 2.0f;
-    float r = __builtin_amdgcn_rcpf(d);
-    r = __fmaf_rn(r, __fmaf_rn(-d, r, 1.0f), r);
-    const float y = x * (n * r);
-    return x > 20.0f ? x : y;                        // e * e overflows beyond x = 44; the quotient is 1 from 20 on
-}
 
 // operands of k-step KS (compile-time) of the chunk in (ib, wb) -> a[MT], b[NT]
 template <class C, int KS>
@@ -396,7 +381,7 @@ __global__ __launch_bounds__(THREADS, 2) void k_conv3x3(const void *__restrict__
         for (int n = 0; n < NT; ++n) {
             f32x4 v = acc[t][n];
             if (pre_wg) *reinterpret_cast<f32x4 *>(pre_wg + o[t] + n * 16 * C::SS) = v;
-            if (apply_mish) v = (f32x4){mish1(v[0]), mish1(v[1]), mish1(v[2]), mish1(v[3])};
+            if (apply_mish) v = (f32x4){mish_fast(v[0]), mish_fast(v[1]), mish_fast(v[2]), mish_fast(v[3])};
             *reinterpret_cast<f32x4 *>(out_wg + o[t] + n * 16 * C::SS) = v;
         }
     }

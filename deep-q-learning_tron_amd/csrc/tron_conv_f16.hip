@@ -31,6 +31,7 @@
 
 #include "../../include/tron_hip.h"
 #include "tron_conv.hpp"
+#include "tron_mish.hpp"
 
 #ifndef TRON_F16_ABLATE      // diagnostic builds only (wrong results): 1 = no staging of the next chunk, 2 = A fragments not re-read, 5 = one split-image store per tile instead of eight, 6 = no weight copies, 7 = no input loads
 #define TRON_F16_ABLATE 0
@@ -38,10 +39,7 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+using namespace tron;
 
 constexpr int CIC = 16;           // input channels per K chunk
 constexpr int TAPS_PAD = 10;      // 9 taps + one with zero weights: 5 slabs of 2 taps x 16 channels
@@ -49,7 +47,6 @@ constexpr int SLABS = 5;
 constexpr int PITCH = 32;         // bytes per LDS row: 16 f16
 constexpr int NWM = 4, NWN = 2;   // waves along M and N
 constexpr int THREADS = 64 * NWM * NWN;
-constexpr float ACT_SCALE = 1.0f / 64.0f, ACT_UNSCALE = 64.0f, LO_SCALE = 2048.0f, LO_UNSCALE = 1.0f / 2048.0f;
 
 // A workgroup's region: P whole images (small boards) or one row band of one image (NB bands; larger boards).  A band
 // starts on an even row, so its first pixel's offset (row * S, S even) is a multiple of 4: epilogue float4s stay aligned.
@@ -84,62 +81,6 @@ struct Cfg {
     static_assert(P == 1 || NB == 1, "several images or several bands, not both");
     static_assert(MT <= 6, "accumulators: MT x NT x 2 x 4 registers");
 };
-
-__device__ __forceinline__ float mish1(float x)                         // as in tron_conv.hip
-{
-    const float e = __builtin_amdgcn_exp2f(x * 1.44269504088896341f);
-    const float n = __fmaf_rn(e, e, e + e);
-    const float d = n + 2.0f;
-    float r = __builtin_amdgcn_rcpf(d);
-    r = __fmaf_rn(r, __fmaf_rn(-d, r, 1.0f), r);
-    const float y = x * (n * r);
-    return x > 20.0f ? x : y;
-}
-
-// Four values at once, written on vectors so that the compiler packs the arithmetic two per instruction (v_pk_*): the
-// epilogue is VALU-issue-bound (docs/DESIGN_history_r01_r03.md 4b).  No select for large x: e^x is capped at 1e18 (an unsigned integer min
-// on the bits — e is never negative — so no NaN-canonicalising v_max comes with it); n = e (e + 2) then stays finite
-// and n / (n + 2) is exactly 1 up there, so the product is x itself.  One rcp (1 ulp), no Newton step.
-__device__ __forceinline__ f32x4 mish4(f32x4 x)
-{
-    const f32x4 t = x * 1.44269504088896341f;
-    f32x4 e;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t b = __float_as_uint(__builtin_amdgcn_exp2f(t[i]));
-        e[i] = __uint_as_float(b < 0x5D5E0B6Bu ? b : 0x5D5E0B6Bu);      // min(e, 1e18)
-    }
-    const f32x4 n = __builtin_elementwise_fma(e, e, e + e);
-    const f32x4 d = n + 2.0f;
-    const f32x4 r = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1]), __builtin_amdgcn_rcpf(d[2]), __builtin_amdgcn_rcpf(d[3])};
-    return x * (n * r);
-}
-
-// gy * mish'(x) the same way (tron_nn.hip's mish_grad1 with exp2 / rcp): t = n / (n + 2), 1 - t^2 = (2 / (n + 2)) (1 + t),
-// mish' = t + x (1 - t^2) e / (1 + e).  With e capped at 1e18, t is exactly 1 and the second term 0 up there.
-__device__ __forceinline__ f32x4 mish_grad4(f32x4 x, f32x4 gy)
-{
-    const f32x4 t2 = x * 1.44269504088896341f;
-    f32x4 e;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t b = __float_as_uint(__builtin_amdgcn_exp2f(t2[i]));
-        e[i] = __uint_as_float(b < 0x5D5E0B6Bu ? b : 0x5D5E0B6Bu);
-    }
-    const f32x4 n = __builtin_elementwise_fma(e, e, e + e);
-    const f32x4 d = n + 2.0f, e1 = e + 1.0f;
-    const f32x4 r = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1]), __builtin_amdgcn_rcpf(d[2]), __builtin_amdgcn_rcpf(d[3])};
-    const f32x4 q = {__builtin_amdgcn_rcpf(e1[0]), __builtin_amdgcn_rcpf(e1[1]), __builtin_amdgcn_rcpf(e1[2]), __builtin_amdgcn_rcpf(e1[3])};
-    const f32x4 t = n * r, u = r + r;
-    return gy * (t + x * (u * (1.0f + t)) * (e * q));
-}
-
-// v -> (hi, lo): v = hi + lo * 2^-11 up to 2^-22 |v|
-__device__ __forceinline__ void split(float v, f16 &hi, f16 &lo)
-{
-    hi = (f16)v;
-    lo = (f16)((v - (float)hi) * LO_SCALE);
-}
 
 // W[cout][cin][3][3] f32 -> workspace f16 [chunk][half][tap 10][cout][16 ci]: per chunk exactly the LDS weight image
 // (hi image, then lo image; tenth tap and channels >= cin zero)
@@ -264,7 +205,8 @@ __global__ __launch_bounds__(THREADS, 2) void k_conv3x3_f16(
 #endif
     // Scale of the f32 activations on their way into f16: 2^-6 for the network's activations; a gradient tensor (the
     // data-gradient call) is orders of magnitude smaller and brings its per-block maxima along: the power of two that
-    // puts its largest magnitude in [2^13, 2^14) keeps the halves in f16's normal range.
+    // puts its largest magnitude in [2^13, 2^14) keeps the halves in f16's normal range.  (This kernel's own copy of the
+    // reduction in tron_f16x3.hpp, which says why.)
     float act_scale = ACT_SCALE, act_unscale = ACT_UNSCALE;
     if (absmax) {
         __shared__ float red[THREADS / 64];
@@ -277,7 +219,7 @@ __global__ __launch_bounds__(THREADS, 2) void k_conv3x3_f16(
 #pragma unroll
         for (int k = 0; k < THREADS / 64; ++k) m = fmaxf(m, red[k]);
         const int e = (int)((__float_as_uint(m) >> 23) & 255u) - 126;   // m = f 2^e, f in [0.5, 1)
-        if (m > 0.0f && e >= -100 && e <= 100) {
+        if (m > 0.0f && e >= -100 && e <= 100) {                        // (no usable maximum: the activation scale stays)
             act_scale = __uint_as_float((uint32_t)(127 + 14 - e) << 23);
             act_unscale = __uint_as_float((uint32_t)(127 - 14 + e) << 23);
         }
@@ -627,7 +569,7 @@ __global__ __launch_bounds__(THREADS, 2) void k_conv3x3_f16(
 #pragma unroll
             for (int n = 0; n < NT; ++n) {
                 const f32x4 z = live[t] ? *reinterpret_cast<const f32x4 *>(z_wg + (uint32_t)(o[t] + n * 16 * C::SS)) : (f32x4){0.f, 0.f, 0.f, 0.f};
-                const f32x4 v = live[t] ? mish_grad4(z, acc0[t][n]) : (f32x4){0.f, 0.f, 0.f, 0.f};
+                const f32x4 v = live[t] ? mish_grad4_capped(z, acc0[t][n]) : (f32x4){0.f, 0.f, 0.f, 0.f};
                 acc0[t][n] = v;
                 bsum[n] += (v[0] + v[1]) + (v[2] + v[3]);
                 bmax[n] = fmaxf(fmaxf(bmax[n], fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
@@ -658,7 +600,7 @@ __global__ __launch_bounds__(THREADS, 2) void k_conv3x3_f16(
             f32x4 v = acc0[t][n];
             const uint32_t ob = (uint32_t)(o[t] + n * 16 * C::SS);       // unsigned 32-bit offsets from a uniform base: no 64-bit address math per store
             if (pre_wg) *reinterpret_cast<f32x4 *>(pre_wg + ob) = v;
-            if (apply_mish) v = mish4(v);
+            if (apply_mish) v = mish4_capped(v);
             if (out_wg) *reinterpret_cast<f32x4 *>(out_wg + ob) = v;
             if (o16_wg) {                 // the same values as the next layer's operand halves: [chunk][hi | lo][pixel][16 ci]
                 unsigned char *d = o16_wg + (uint32_t)(img * cout * C::SS * 4 + ((wn * NT + n) * 2) * C::SS * 32 + pg * 32 + li * 2);

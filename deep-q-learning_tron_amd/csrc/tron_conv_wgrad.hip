@@ -23,19 +23,16 @@
 #include <stdint.h>
 
 #include "../../include/tron_hip.h"
+#include "tron_f16x3.hpp"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16;
+using namespace tron;
+
 typedef __attribute__((address_space(1))) const f32x4 gvec4;      // global memory, explicitly
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int SIDE = 12, HW = SIDE * SIDE, ROWP = 14, IMG_K = 192, SLABS_IMG = IMG_K / 32, MARGIN = 16;
 constexpr int THREADS = 256, GRID_MAX = 256, STAGE2 = 8, ABSMAX_BLOCKS = 1024;
-constexpr float IN_SCALE = 1.0f / 64.0f, LO_SCALE = 2048.0f;
 #ifndef TRON_WG_ABLATE       // diagnostic builds: 1 no MFMA slabs, 2 no staging inside the loop, 3 no global loads
 #define TRON_WG_ABLATE 0
 #endif
@@ -59,12 +56,6 @@ struct Cfg {
     static_assert(SLABS_IMG * IMGS % KSPLIT == 0, "slabs must split evenly");
 };
 
-__device__ __forceinline__ uint32_t pack2(f16 a, f16 b)
-{
-    const f16x2 v = {a, b};
-    return __builtin_bit_cast(uint32_t, v);
-}
-
 // the operand that starts IDX elements into the 40-element window D (20 dwords)
 template <int IDX>
 __device__ __forceinline__ f16x8 window_frag(const uint32_t (&D)[20])
@@ -78,22 +69,6 @@ __device__ __forceinline__ f16x8 window_frag(const uint32_t (&D)[20])
                     __builtin_amdgcn_alignbit(D[k + 3], D[k + 2], 16), __builtin_amdgcn_alignbit(D[k + 4], D[k + 3], 16)};
     }
     return __builtin_bit_cast(f16x8, v);
-}
-
-// per-block maxima of |g| -> one power-of-two scale that puts the largest magnitude in [2^13, 2^14)
-__device__ __forceinline__ float grad_scale(const float *__restrict__ absmax, int n_absmax, float *red)
-{
-    float m = 0.0f;
-    for (int i = threadIdx.x; i < n_absmax; i += THREADS) m = fmaxf(m, absmax[i]);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    const uint32_t bits = __float_as_uint(m);
-    const int e = (int)((bits >> 23) & 255u) - 126;                     // m = f 2^e, f in [0.5, 1)
-    if (!(m > 0.0f) || e < -100 || e > 100) return 1.0f;                // zero, denormal, huge or NaN gradients: unscaled
-    return __uint_as_float((uint32_t)(127 + 14 - e) << 23);            // 2^(14 - e)
 }
 
 #ifdef TRON_WG_STAMPS        // diagnostic build only (scripts/wgrad_stamps.py): per-workgroup clocks, read back by tron_wgrad_stamps
@@ -123,7 +98,8 @@ __global__ __launch_bounds__(THREADS, 1) void k_wgrad(const float *__restrict__ 
 
     for (int i = tid * 16; i < C::LDS; i += THREADS * 16) *reinterpret_cast<f32x4 *>(lds + i) = (f32x4){0.f, 0.f, 0.f, 0.f};
     TRON_WG_STAMP(0)
-    const float gscale = grad_scale(absmax, n_absmax, red);            // (contains the barrier after the clear)
+    wave_absmax<THREADS>(absmax, n_absmax, red);                         // (contains the barrier after the clear)
+    const float gscale = absmax_scale(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])), 1.0f);
     const int in_items = IMGS * cin * SIDE;
 
     f32x4 acc0[COT][9], acc1[COT][9];
@@ -179,7 +155,7 @@ __global__ __launch_bounds__(THREADS, 1) void k_wgrad(const float *__restrict__ 
 #define TRON_WG_CONVERT_PIECE(round_, p_)                                                                                \
     {                                                                                                                    \
         constexpr int k_ = (p_) / 3, q_ = (p_) % 3;                                                                      \
-        const float sc_ = ((int64_t)(round_) * IMGS + TRON_WG_J(k_) < batch) ? (TRON_WG_IS_GP(k_) ? gscale : IN_SCALE) : 0.0f; \
+        const float sc_ = ((int64_t)(round_) * IMGS + TRON_WG_J(k_) < batch) ? (TRON_WG_IS_GP(k_) ? gscale : ACT_SCALE) : 0.0f; \
         const f32x4 v_ = pf[k_][q_] * sc_;                                                                               \
         const f16 h0_ = (f16)v_[0], h1_ = (f16)v_[1], h2_ = (f16)v_[2], h3_ = (f16)v_[3];                                \
         const f16 l0_ = (f16)((v_[0] - (float)h0_) * LO_SCALE), l1_ = (f16)((v_[1] - (float)h1_) * LO_SCALE);            \

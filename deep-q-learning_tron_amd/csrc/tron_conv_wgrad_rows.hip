@@ -23,19 +23,16 @@
 #include <stdint.h>
 
 #include "../../include/tron_hip.h"
+#include "tron_f16x3.hpp"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16;
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+using namespace tron;
 
 #ifndef TRON_WR_ABLATE      // diagnostic builds only (wrong results): 1 = no LDS stores of the staged rows, 2 = no MFMAs, 3 = no global loads,
 #define TRON_WR_ABLATE 0    // 4 = no barrier
 #endif
 constexpr int ROWEL = 48, ROWB = ROWEL * 2, PADL = 8;                   // an LDS row: 8 zeros, 32 pixels (>= S real), 8 zeros
-constexpr float IN_SCALE = 1.0f / 64.0f, LO_SCALE = 2048.0f;
 
 template <int S_, int CIN_, int COW_, int HALVES_ = 1>
 struct RCfg {
@@ -56,31 +53,6 @@ struct RCfg {
     static_assert(LDS <= 160 * 1024, "LDS");
 };
 
-__device__ __forceinline__ uint32_t pack2(f16 a, f16 b)
-{
-    const f16x2 v = {a, b};
-    return __builtin_bit_cast(uint32_t, v);
-}
-
-// per-block maxima of |g| -> one power-of-two scale that puts the largest magnitude in [2^13, 2^14) (as tron_conv_wgrad.hip)
-template <int THREADS>
-__device__ __forceinline__ float grad_scale(const float *__restrict__ absmax, int n_absmax, float *red)
-{
-    float m = 0.0f;
-    for (int i = threadIdx.x; i < n_absmax; i += THREADS) m = fmaxf(m, absmax[i]);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    m = 0.0f;
-#pragma unroll
-    for (int k = 0; k < THREADS / 64; ++k) m = fmaxf(m, red[k]);
-    const uint32_t bits = __float_as_uint(m);
-    const int e = (int)((bits >> 23) & 255u) - 126;                     // m = f 2^e, f in [0.5, 1)
-    if (!(m > 0.0f) || e < -100 || e > 100) return 1.0f;
-    return __uint_as_float((uint32_t)(127 + 14 - e) << 23);            // 2^(14 - e)
-}
-
 template <class C>
 __global__ __launch_bounds__(C::THREADS, 2) void k_wgrad_rows(const float *__restrict__ in, const float *__restrict__ gp,
                                                               const float *__restrict__ absmax, int n_absmax,
@@ -98,7 +70,11 @@ __global__ __launch_bounds__(C::THREADS, 2) void k_wgrad_rows(const float *__res
     const int it = wave % C::NCI, ct = wave / C::NCI;                    // this wave's input / output channel tile
 
     for (int i = tid * 16; i < C::LDS; i += THREADS * 16) *reinterpret_cast<f32x4 *>(lds + i) = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const float gscale = grad_scale<THREADS>(absmax, n_absmax, red);     // (contains the barrier after the clear)
+    wave_absmax<THREADS>(absmax, n_absmax, red);                         // (contains the barrier after the clear)
+    float gmax = 0.0f;
+#pragma unroll
+    for (int k = 0; k < THREADS / 64; ++k) gmax = fmaxf(gmax, red[k]);
+    const float gscale = absmax_scale(gmax, 1.0f);
 
     f32x4 acc0[9], acc1[9];
 #pragma unroll
@@ -151,7 +127,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void k_wgrad_rows(const float *__res
             const int pidx = wave + r * C::WAVES;
             if (pidx >= NPI + NPG) continue;
             const bool is_in = pidx < NPI;                               // (wave-uniform)
-            const float sc = st_src[r] < 0 ? 0.0f : is_in ? (in_ok ? IN_SCALE : 0.0f) : (g_ok ? gscale : 0.0f);
+            const float sc = st_src[r] < 0 ? 0.0f : is_in ? (in_ok ? ACT_SCALE : 0.0f) : (g_ok ? gscale : 0.0f);
             const int lo = pos_lo(is_in, is_in ? in_half : g_half), span = pos_hi(is_in, is_in ? in_half : g_half) - lo;
             auto at = [&](int j, float v) { return (unsigned)(4 * q + j - lo) < (unsigned)span ? v * sc : 0.0f; };
             const float v0 = at(0, pf[r][0].x), v1 = at(1, pf[r][0].y), v2 = at(2, pf[r][1].x), v3 = at(3, pf[r][1].y);

@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "../../include/tron_hip.h"
+#include "tron_mish.hpp"
 
 // 34x34 images (32x32 boards: the actor-critic nets): the gradient-free forward's instantiations live beside the training ones in
 // tron_conv_ws_train.hip (tron_conv_ws.hip keeps the tuned 12x12 / 26x26 inference variants to itself); tron_conv3x3_ws_fwd calls this
@@ -20,10 +21,7 @@ int ws_fwd_side34(const void *in_px16, const void *wfrag, const float *bias, con
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+using namespace tron;
 
 #ifndef TRON_WS_POOL_ABLATE // diagnostic builds only (wrong results; scripts/ws_ablate.sh poolflags): 1 = WS_POOL without its pooling pass,
 #define TRON_WS_POOL_ABLATE 0 // 2 = and without the barrier in front of it, 3 = and the epilogue's LDS write goes to the dump
@@ -31,7 +29,6 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 #ifndef TRON_WS_ABLATE      // diagnostic builds only (wrong results; scripts/ws_ablate.sh): 1 = no epilogue arithmetic, 2 = B fragments
 #define TRON_WS_ABLATE 0    // not re-read from LDS, 3 = no image DMA, 4 = no stores, 5 = no MFMAs, 6 = no item barrier
 #endif
-constexpr float ACT_SCALE = 1.0f / 64.0f, ACT_UNSCALE = 64.0f, LO_SCALE = 2048.0f, LO_UNSCALE = 1.0f / 2048.0f;
 
 constexpr int align256(int x) { return (x + 255) & ~255; }
 
@@ -73,28 +70,6 @@ struct Geo {
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
     static_assert(NS % TPS == 0 || TPS == 1, "epilogue stages over the slabs");
 };
-
-// as tron_conv_f16.hip's: four values at once, e^x capped by an unsigned min (no select), one rcp
-__device__ __forceinline__ f32x4 mish4(f32x4 x)
-{
-    const f32x4 t = x * 1.44269504088896341f;
-    f32x4 e;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t b = __float_as_uint(__builtin_amdgcn_exp2f(t[i]));
-        e[i] = __uint_as_float(b < 0x5D5E0B6Bu ? b : 0x5D5E0B6Bu);      // min(e, 1e18)
-    }
-    const f32x4 n = __builtin_elementwise_fma(e, e, e + e);
-    const f32x4 d = n + 2.0f;
-    const f32x4 r = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1]), __builtin_amdgcn_rcpf(d[2]), __builtin_amdgcn_rcpf(d[3])};
-    return x * (n * r);
-}
-
-__device__ __forceinline__ void split(float v, f16 &hi, f16 &lo)
-{
-    hi = (f16)v;
-    lo = (f16)((v - (float)hi) * LO_SCALE);
-}
 
 // ---- weights: W[cout][cin][3][3] f32 -> fragment image f16 [M tile][slab][hi | lo][lane][8] -------------------------
 // Lane l of an A fragment holds row l & 15 (output channel 16 ct + row), k = 8 (l >> 4) + j: slab s = (tap s / NCB,
@@ -167,12 +142,19 @@ struct WsBwd {
     float *out_info;             // record of `out`: {s_out, 1 / s_out} are written here (the maxima: k_wsb_finish)
     float *stats;                // [2][gridDim.x][COUT]: column sums | column maxima of |out|
 };
-__device__ __forceinline__ float pow2_at_most(float x)                   // the largest power of two <= x (x > 0, finite); exponent clamped to +-60
+// the largest power of two <= x (x > 0, finite); exponent clamped to +-60.  Stays here, beside its one caller: it rounds a
+// BOUND on what a layer is about to write down to a power of two, where tron_f16x3.hpp's absmax_scale places maxima that
+// were measured
+__device__ __forceinline__ float pow2_at_most(float x)
 {
     int e = (int)((__float_as_uint(x) >> 23) & 0xFFu) - 127;
     e = e < -60 ? -60 : (e > 60 ? 60 : e);
     return __uint_as_float((uint32_t)(e + 127) << 23);
 }
+
+// row index (with halo and separator rows counted) of stack row t of a window that stacks whole images with one separator row
+// between them (tron_conv_ws_train.hip's k_wgrad_px, tron_kfac_px.hip): image i = t / S occupies e = i (S + 1) + 1 ... i (S + 1) + S
+template <class C> __device__ __forceinline__ int stack_e(int t) { return t + t / C::S + 1; }
 
 template <class G, bool RES, bool F32OUT, int MODE = WS_INFER>
 __global__ __launch_bounds__(G::THREADS, G::WAVES / 4) void k_conv_ws(
@@ -798,8 +780,8 @@ __global__ __launch_bounds__(256) void k_conv1_px(const int8_t *__restrict__ cod
                 *reinterpret_cast<f16x8 *>(zp + (size_t)oct * SS * 16) = __builtin_shufflevector(zh0, zh1, 0, 1, 2, 3, 4, 5, 6, 7);
                 *reinterpret_cast<f16x8 *>(zp + (size_t)(4 + oct) * SS * 16) = __builtin_shufflevector(zl0, zl1, 0, 1, 2, 3, 4, 5, 6, 7);
             }
-            a0 = mish4(a0) * ACT_SCALE;
-            a1 = mish4(a1) * ACT_SCALE;
+            a0 = mish4_capped(a0) * ACT_SCALE;
+            a1 = mish4_capped(a1) * ACT_SCALE;
             const f16x4 h0 = __builtin_convertvector(a0, f16x4), h1 = __builtin_convertvector(a1, f16x4);
             const f16x4 l0 = __builtin_convertvector((a0 - __builtin_convertvector(h0, f32x4)) * LO_SCALE, f16x4);
             const f16x4 l1 = __builtin_convertvector((a1 - __builtin_convertvector(h1, f32x4)) * LO_SCALE, f16x4);
@@ -877,32 +859,6 @@ int launch_ws(const void *in, const void *wfrag, const float *bias, const void *
     else     { if (f32o) TRON_WS_LAUNCH(false, true); else TRON_WS_LAUNCH(false, false); }
 #undef TRON_WS_LAUNCH
     return hipGetLastError() == hipSuccess ? TRON_OK : TRON_ERR_LAUNCH;
-}
-
-// ds_read_b64_tr_b16 by inline asm, not by __builtin_amdgcn_ds_read_tr16_b64: behind the builtin hipcc (ROCm 7.2) puts an
-// s_waitcnt vmcnt(0) in front of every transposed read that follows an LDS-DMA (it cannot tell the read from the copy's
-// destination), which serialised each of an item's nine copies with the multiply — 11 us per item instead of 3 (the .s showed
-// ten vmcnt(0) per item).  The asm is invisible to that pass; what it costs is that the waits are ours: the reads of a tap go
-// out one tap ahead, `lds_wait()` (s_waitcnt lgkmcnt(0) + sched_barrier, so that no consumer moves above it) stands between a
-// read and the first use of its registers, and the two 8-byte halves are joined into the MFMA operand only AFTER that wait (a
-// copy the compiler might make of them then reads landed data).  EXEC must be all ones (the read crosses lanes).
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ s16x4 lds_tr(uint32_t addr)
-{
-    s16x4 r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=&v"(r) : "v"(addr));
-    return r;
-}
-__device__ __forceinline__ void lds_wait()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ f16x8 join8(s16x4 a, s16x4 b)
-{
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_bit_cast(f16x8, v);
 }
 
 

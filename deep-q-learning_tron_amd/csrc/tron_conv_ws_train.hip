@@ -215,9 +215,6 @@ struct WCfg {
     static_assert(2 * NI * 8 * SS < 0xFFFF, "source offsets in 16 bits");
 };
 
-// row index (with halo and separator rows counted) of stack row t: image i = t / S occupies e = i (S + 1) + 1 ... i (S + 1) + S
-template <class C> __device__ __forceinline__ int stack_e(int t) { return t + t / C::S + 1; }
-
 struct WBands { int n[8]; };                                             // workgroups per band
 
 template <class C>
@@ -342,7 +339,7 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_px(const unsigned char *__rest
                 f16x8 gh[2], gl[2];
 #pragma unroll
                 for (int tap = 0; tap < 9; ++tap) {
-                    lds_wait();                                          // this tap's operands (and, at tap 0, the gradient's) have landed
+                    lds_tr_wait();                                          // this tap's operands (and, at tap 0, the gradient's) have landed
                     if (tap == 0) {
 #pragma unroll
                         for (int t = 0; t < 2; ++t) {
@@ -620,12 +617,11 @@ __global__ __launch_bounds__(256) void k_conv1_wgrad_px(const int8_t *__restrict
 #pragma unroll
             for (int nt = 0; nt < 3; ++nt) {
                 const f16 *P = reinterpret_cast<const f16 *>(Ip + b_base[nt] + 2 * s * C::RPS * C::PW);
-                typedef _Float16 f16x4v __attribute__((ext_vector_type(4)));
-                const f16x4v r0 = *reinterpret_cast<const f16x4v *>(P), r1 = *reinterpret_cast<const f16x4v *>(P + (C::XW == 16 ? C::PW : 16));
+                const f16x4 r0 = *reinterpret_cast<const f16x4 *>(P), r1 = *reinterpret_cast<const f16x4 *>(P + (C::XW == 16 ? C::PW : 16));
                 bf[nt] = __builtin_shufflevector(r0, r1, 0, 1, 2, 3, 4, 5, 6, 7);
                 if (TRON_C1W_ABLATE == 1) asm volatile("" : "=v"(bf[nt]) : "v"(P));
             }
-            lds_wait();
+            lds_tr_wait();
             f16x8 gh[2], gl[2];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {

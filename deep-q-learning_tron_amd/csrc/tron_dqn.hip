@@ -114,7 +114,8 @@ __global__ __launch_bounds__(1024) void k_eps_schedule(const int8_t *__restrict_
 // floats order like their bit patterns, so the block maxima meet in an integer atomicMax and the last block to finish
 // writes the result.
 // (At most 256 workgroups of 1 024 threads: the two atomics per workgroup serialise on their address at ~25 ns each — 2 048
-// small workgroups took 51 us for a 9 MB tensor.)
+// small workgroups took 51 us for a 9 MB tensor.)  (Its own exponent arithmetic, not tron_f16x3.hpp's: one maximum across
+// workgroups, a caller's target, a clamp — and written with that header's helpers its select compiles to a branch.)
 __global__ __launch_bounds__(1024) void k_absmax_pow2(const float *__restrict__ x, int64_t n, int target_exp, float *__restrict__ out)
 {
     __shared__ float red[16];

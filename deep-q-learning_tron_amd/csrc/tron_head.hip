@@ -28,30 +28,12 @@
 #include <stdint.h>
 
 #include "../../include/tron_hip.h"
+#include "tron_mish.hpp"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+using namespace tron;
 
-constexpr float ACT_SCALE = 1.0f / 64.0f, ACT_UNSCALE = 64.0f, LO_SCALE = 2048.0f, LO_UNSCALE = 1.0f / 2048.0f;
-
-__device__ __forceinline__ float mish1(float x)                         // as in tron_conv.hip
-{
-    const float e = __builtin_amdgcn_exp2f(x * 1.44269504088896341f);
-    const float n = __fmaf_rn(e, e, e + e);
-    const float d = n + 2.0f;
-    float r = __builtin_amdgcn_rcpf(d);
-    r = __fmaf_rn(r, __fmaf_rn(-d, r, 1.0f), r);
-    const float y = x * (n * r);
-    return x > 20.0f ? x : y;
-}
-__device__ __forceinline__ void split(float v, f16 &hi, f16 &lo)
-{
-    hi = (f16)v;
-    lo = (f16)((v - (float)hi) * LO_SCALE);
-}
 
 // x f32 [B][C][12][12] -> AvgPool2d(3, stride 2, padding 1) (divisor 9 everywhere: count_include_pad) -> rows
 // [B][C * 6 * 6] in NCHW-flatten order, pre-scaled by 2^-6 and split.  One thread = one pooled row of one plane: three
@@ -59,7 +41,6 @@ __device__ __forceinline__ void split(float v, f16 &hi, f16 &lo)
 __global__ __launch_bounds__(256) void k_pool_split12(const float *__restrict__ x, int64_t rows, f16 *__restrict__ oh,
                                                       f16 *__restrict__ ol)
 {
-    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += stride) {
         const int py = (int)(i % 6);
@@ -303,7 +284,6 @@ __global__ __launch_bounds__(256) void k_pool_split_cl(const float *__restrict__
         tl[px * C + c] = l;
     }
     __syncthreads();
-    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
     const size_t row = ((size_t)b * PS + py) * PS * C;                   // the row's 13 pixels x 64 channels are contiguous
     for (int i = threadIdx.x; i < PS * C / 2; i += 256) {
         *reinterpret_cast<f16x2 *>(oh + row + 2 * i) = (f16x2){th[2 * i], th[2 * i + 1]};
@@ -314,11 +294,10 @@ __global__ __launch_bounds__(256) void k_pool_split_cl(const float *__restrict__
 // ---- the same two poolings reading the trunk's output as the PX16 image of csrc/tron_conv_ws.hip ----------------------
 // PX16: per image [hi | lo][channel octet][pixel][8 channels] f16, value / 64 = hi + lo 2^-11 — already in this file's
 // scale, so the pooled value is the average of (hi + lo 2^-11) over the window, split again.
-typedef _Float16 f16x8h __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ void px16_window_sum(const unsigned char *img, int S, int half_bytes, int oct, int py, int px, float (&sum)[8])
 {
     // all 18 loads are issued before the first use: positions outside the image are clamped and weighted 0
-    f16x8h h[9], l[9];
+    f16x8 h[9], l[9];
     float wgt[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
@@ -326,8 +305,8 @@ __device__ __forceinline__ void px16_window_sum(const unsigned char *img, int S,
         const bool in = yy >= 0 && yy < S && xx >= 0 && xx < S;
         const int yc = yy < 0 ? 0 : (yy >= S ? S - 1 : yy), xc = xx < 0 ? 0 : (xx >= S ? S - 1 : xx);
         const unsigned char *p = img + ((size_t)oct * S * S + yc * S + xc) * 16;
-        h[t] = *reinterpret_cast<const f16x8h *>(p);
-        l[t] = *reinterpret_cast<const f16x8h *>(p + half_bytes);
+        h[t] = *reinterpret_cast<const f16x8 *>(p);
+        l[t] = *reinterpret_cast<const f16x8 *>(p + half_bytes);
         wgt[t] = in ? 1.0f : 0.0f;
     }
 #pragma unroll
@@ -352,7 +331,7 @@ __global__ __launch_bounds__(256) void k_pool_split12_px(const unsigned char *__
         const int r = (int)(i - b * 288), oct = r / 36, pp = r - oct * 36;
         float sum[8];
         px16_window_sum(x + (size_t)b * 2 * HALF, S, HALF, oct, pp / 6, pp % 6, sum);
-        f16x8h h, l;
+        f16x8 h, l;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             f16 hh, ll;
@@ -360,8 +339,8 @@ __global__ __launch_bounds__(256) void k_pool_split12_px(const unsigned char *__
             h[j] = hh;
             l[j] = ll;
         }
-        *reinterpret_cast<f16x8h *>(oh + (size_t)i * 8) = h;
-        *reinterpret_cast<f16x8h *>(ol + (size_t)i * 8) = l;
+        *reinterpret_cast<f16x8 *>(oh + (size_t)i * 8) = h;
+        *reinterpret_cast<f16x8 *>(ol + (size_t)i * 8) = l;
     }
 }
 
@@ -399,7 +378,7 @@ __global__ __launch_bounds__(512) void k_pool_split26_px(const unsigned char *__
         const int r = (int)(pix - b * (PS * PS)), py = r / PS, px = r % PS;
         float sum[8];
         px16_window_sum(x + (size_t)b * 2 * HALF, S, HALF, oct, py, px, sum);
-        f16x8h h, l;
+        f16x8 h, l;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             f16 hh, ll;
@@ -407,14 +386,14 @@ __global__ __launch_bounds__(512) void k_pool_split26_px(const unsigned char *__
             h[j] = hh;
             l[j] = ll;
         }
-        *reinterpret_cast<f16x8h *>(th + lane * ROW + oct * 16) = h;
-        *reinterpret_cast<f16x8h *>(tl + lane * ROW + oct * 16) = l;
+        *reinterpret_cast<f16x8 *>(th + lane * ROW + oct * 16) = h;
+        *reinterpret_cast<f16x8 *>(tl + lane * ROW + oct * 16) = l;
     }
     __syncthreads();
     const int p = threadIdx.x >> 3, part = threadIdx.x & 7;
     if (pix0 + p < total) {
-        *reinterpret_cast<f16x8h *>(oh + (size_t)(pix0 + p) * C + part * 8) = *reinterpret_cast<const f16x8h *>(th + p * ROW + part * 16);
-        *reinterpret_cast<f16x8h *>(ol + (size_t)(pix0 + p) * C + part * 8) = *reinterpret_cast<const f16x8h *>(tl + p * ROW + part * 16);
+        *reinterpret_cast<f16x8 *>(oh + (size_t)(pix0 + p) * C + part * 8) = *reinterpret_cast<const f16x8 *>(th + p * ROW + part * 16);
+        *reinterpret_cast<f16x8 *>(ol + (size_t)(pix0 + p) * C + part * 8) = *reinterpret_cast<const f16x8 *>(tl + p * ROW + part * 16);
     }
 }
 
@@ -653,7 +632,7 @@ __global__ __launch_bounds__(G_THREADS, 4) void k_gemm_f16x3(const f16 *__restri
             for (int r = 0; r < 4; ++r) {
                 const int m = m0 + wm * 32 + t * 16 + 4 * g + r;
                 if (m >= M) continue;
-                const float y = act ? mish1(v[r]) : v[r];
+                const float y = act ? mish_fast(v[r]) : v[r];
                 if constexpr (MODE == G_DGRAD7) {                        // row m of the class -> its pooled pixel, channels-last
                     const RowGeo o = row_geo<MODE, PS>(m, cls);
                     const int iy = 2 * o.y + ((cls & 2) ? 1 : 0), ix = 2 * o.x + (cls & 1);
@@ -788,7 +767,7 @@ __global__ __launch_bounds__(G_THREADS, 2) void k_gemm_wide(const f16 *__restric
                     partial[((size_t)blockIdx.y * M + m) * N + col] = raw[r];
                     continue;
                 }
-                const float y = act ? mish1(v[r]) : v[r];
+                const float y = act ? mish_fast(v[r]) : v[r];
                 if (out_f32) out_f32[(size_t)m * N + col] = y;
                 if (out_h) {
                     f16 hh, ll;
@@ -816,7 +795,7 @@ __global__ void k_gemm_finish(const float *__restrict__ partial, int splitk, int
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const float x = v[r] * out_scale + (bias ? bias[(col + r) / bias_div] : 0.0f);
-        y[r] = act ? mish1(x) : x;
+        y[r] = act ? mish_fast(x) : x;
     }
     if (out_f32) *reinterpret_cast<f32x4 *>(out_f32 + i) = y;
     if (out_h) {
@@ -1016,7 +995,7 @@ __global__ __launch_bounds__(256) void k_mish_cl_to_nchw(const float *__restrict
     __shared__ float t[OPIX * 65];
     for (int b = blockIdx.x; b < B; b += gridDim.x) {
         const float *src = pre + (size_t)b * OPIX * 64;
-        for (int i = threadIdx.x; i < OPIX * 64; i += 256) t[(i >> 6) * 65 + (i & 63)] = act ? mish1(src[i]) : src[i];
+        for (int i = threadIdx.x; i < OPIX * 64; i += 256) t[(i >> 6) * 65 + (i & 63)] = act ? mish_fast(src[i]) : src[i];
         __syncthreads();
         float *dst = y + (size_t)b * OPIX * 64;
         for (int i = threadIdx.x; i < OPIX * 64; i += 256) {
@@ -1025,16 +1004,6 @@ __global__ __launch_bounds__(256) void k_mish_cl_to_nchw(const float *__restrict
         }
         __syncthreads();
     }
-}
-
-__device__ __forceinline__ float mish_grad1(float x)                    // d mish / dx, as csrc/tron_conv_f16.hip's mish_grad4
-{
-    const uint32_t eb = __float_as_uint(__builtin_amdgcn_exp2f(x * 1.44269504088896341f));
-    const float e = __uint_as_float(eb < 0x5D5E0B6Bu ? eb : 0x5D5E0B6Bu);      // e^x capped at 1e18: t is exactly 1 up there
-    const float n = __fmaf_rn(e, e, e + e);                              // tanh(softplus x) = n / (n + 2)
-    const float r = __builtin_amdgcn_rcpf(n + 2.0f), q = __builtin_amdgcn_rcpf(e + 1.0f);
-    const float t = n * r;
-    return t + x * ((r + r) * (1.0f + t)) * (e * q);                     // t + x (1 - t^2) sigmoid(x)
 }
 
 // gp[b][p][co] = gy[b][co * OPIX + p] * mish'(pre[b][p][co]), written channels-last split (scaled by 2^-6 and the power of two
@@ -1059,7 +1028,7 @@ __global__ __launch_bounds__(256) void k_mish_bwd_to_cl(const float *__restrict_
         __syncthreads();
         const float *pr = pre + (size_t)b * OPIX * 64;
         for (int i = threadIdx.x; i < OPIX * 64; i += 256) {            // i & 63 == co for every i of this thread
-            const float g = pre ? t[(i >> 6) * 65 + co] * mish_grad1(pr[i]) : t[(i >> 6) * 65 + co];   // (pre == NULL: no activation behind the convolution)
+            const float g = pre ? t[(i >> 6) * 65 + co] * mish_grad_capped(pr[i]) : t[(i >> 6) * 65 + co];   // (pre == NULL: no activation behind the convolution)
             sum += g;
             f16 h, l;
             split(g * sc, h, l);
@@ -1202,31 +1171,6 @@ struct W7 {
     static constexpr int G_LO = GROWS * W7_PITCH, P_BASE = 2 * GROWS * W7_PITCH, P_LO = PROWS * W7_PITCH;
     static_assert(LDS <= 160 * 1024 && NSLOT <= 32, "layout");
 };
-// ds_read_b64_tr_b16 by inline asm (EXEC must be all ones).  Behind __builtin_amdgcn_ds_read_tr16_b64 hipcc (ROCm 7.2) puts an
-// s_waitcnt vmcnt(0) in front of the first transposed read that follows an LDS-DMA — the next image's copy, issued right before
-// the multiply, was waited for before the multiply began: no overlap (found on csrc/tron_conv_ws_train.hip's k_wgrad_px, round 4).
-// The asm is invisible to that pass, so the waits are written here: a step's reads go out one step ahead, `lds_tr_wait()`
-// (s_waitcnt lgkmcnt(0) + sched_barrier) stands between a read and the first use of its registers, and the two 8-byte halves
-// are joined into the MFMA operand only after that wait.
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ s16x4 lds_tr(uint32_t addr)
-{
-    s16x4 r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=&v"(r) : "v"(addr));
-    return r;
-}
-__device__ __forceinline__ void lds_tr_wait()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ f16x8 join8(s16x4 a, s16x4 b)
-{
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_bit_cast(f16x8, v);
-}
-
 template <int PS>
 __global__ __launch_bounds__(W7_THREADS) void k_conv7_wgrad(const f16 *__restrict__ gph, const f16 *__restrict__ gpl,
                                                             const f16 *__restrict__ ph, const f16 *__restrict__ pl, int B, int nsl,

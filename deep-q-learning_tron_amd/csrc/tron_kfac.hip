@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "../../include/tron_hip.h"
+#include "tron_f16x3.hpp"
 #include "tron_kfac_px.hpp"
 #include <stdlib.h>
 
@@ -84,18 +85,9 @@ extern "C" int tron_extract_patches(const float *x, int64_t batch, int32_t chann
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+using namespace tron;
 
-constexpr float ACT_SCALE = 1.0f / 64.0f, LO_SCALE = 2048.0f, LO_UNSCALE = 1.0f / 2048.0f;
 constexpr float GRAM_UNSCALE = 4096.0f;            // both operands carry 2^-6
-
-__device__ __forceinline__ void split(float v, f16 &hi, f16 &lo)
-{
-    hi = (f16)v;
-    lo = (f16)((v - (float)hi) * LO_SCALE);
-}
 
 __global__ __launch_bounds__(256) void k_patches_t(const float *__restrict__ x, int n_img, int C, int H, int W, int kh, int kw,
                                                    int pad, int stride, int OH, int OW, int d, int dpad, int64_t rows,
@@ -149,7 +141,6 @@ __global__ __launch_bounds__(256) void k_patches_t_plane(const float *__restrict
                                                          const float *__restrict__ in_scale, f16 *__restrict__ xh, f16 *__restrict__ xl)
 {
     extern __shared__ float plane[];                                     // [(H + 2 pad)][(W + 2 pad)]
-    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
     const float sc = ACT_SCALE * (in_scale ? *in_scale : 1.0f);
     const int b = blockIdx.x / C, c = blockIdx.x - b * C;
     const int Hp = H + 2 * pad, Wp = W + 2 * pad;
@@ -467,7 +458,6 @@ __global__ __launch_bounds__(256) void k_gram_nchw(const float *__restrict__ g, 
 #pragma unroll
         for (int j = 0; j < NLD; ++j) {
             const int i = tid + j * 256, c = i >> 3, q = i & 7;          // q-th float4 = k 4q .. 4q+3: half of piece q / 2
-            typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
             f16x4 h, l;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {

@@ -58,7 +58,6 @@ struct KCfg {
     static_assert(2 * NI * 8 * SS < 0xFFFF, "source offsets in 16 bits");
     static_assert(GPX % 4 == 0, "padding pixels come in whole 4-pixel read groups");
 };
-template <class C> __device__ __forceinline__ int kstack_e(int t) { return t + t / C::S + 1; }
 
 struct KBands { int n[8]; };
 
@@ -78,7 +77,7 @@ __device__ __forceinline__ void kfac_px_body(const unsigned char *__restrict__ x
     if (wb >= nwb) return;
     const int r0 = band * C::R, nrows = (C::ROWS - r0 < C::R) ? C::ROWS - r0 : C::R, npx = nrows * S;
     const int nslab = (npx + 31) >> 5;
-    const int e0 = kstack_e<C>(r0) - 1, e_last = kstack_e<C>(r0 + nrows - 1) + 1;
+    const int e0 = stack_e<C>(r0) - 1, e_last = stack_e<C>(r0 + nrows - 1) + 1;
     const int blk = wave % C::NBLK, kgroup = wave / C::NBLK;
     const int cot2 = blk / (CH / 16), cit = blk % (CH / 16);
 
@@ -122,7 +121,7 @@ __device__ __forceinline__ void kfac_px_body(const unsigned char *__restrict__ x
             ok[s][j] = 32 * s + 16 * j + 4 * g < npx;
             px = px < npx ? px : 0;
             const int t = r0 + px / S, x = px - (px / S) * S;
-            addr[s][j] = (p4 >> 1) * C::PLANE + ((kstack_e<C>(t) - e0) * C::WC + x + 1) * 16 + (p4 & 1) * 8;
+            addr[s][j] = (p4 >> 1) * C::PLANE + ((stack_e<C>(t) - e0) * C::WC + x + 1) * 16 + (p4 & 1) * 8;
         }
     const int m_off = 4 * cot2 * C::PLANE, n_off = 2 * cit * C::PLANE;   // this wave's channel tiles: M 32 channels (two tiles), N 16
 
@@ -203,7 +202,7 @@ __device__ __forceinline__ void kfac_px_body(const unsigned char *__restrict__ x
                 const s16x4 zero4 = {0, 0, 0, 0};
 #pragma unroll
                 for (int i = 0; i < 9; ++i) {
-                    lds_wait();
+                    lds_tr_wait();
                     if (i == 0) {
 #pragma unroll
                         for (int w = 0; w < (KIND > 0 ? 2 : 1); ++w)

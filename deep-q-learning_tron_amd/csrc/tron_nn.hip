@@ -3,43 +3,26 @@
 //
 // torch's composed form is three elementwise launches; its fused F.mish is one, but spends ~86 us on a
 // 4096 x 32 x 12 x 12 tensor (75 MB in + out: ~15 us of traffic) evaluating exp, log1p and tanh in turn —
-// 14 % of the DDQN trainer's GPU time (rocprofv3, profiles/r01_dqn_kernel_stats.csv).  With e = exp(x):
-//     tanh(log1p(e)) = ((1+e)^2 - 1) / ((1+e)^2 + 1) = n / (n + 2),   n = e * (e + 2)
-// so one exp and one division give the forward value, with no cancellation anywhere (for x -> -inf,
-// n -> 2e and the quotient -> e; for x > 20 the result is x to fp32 precision — the same cut-over as
-// F.softplus's threshold — which also keeps e*e from overflowing).  Backward:
-//     d/dx = t + x * (1 - t^2) * e / (1 + e),   t = n / (n + 2),   1 - t^2 = (2 / (n + 2)) (1 + t).
+// 14 % of the DDQN trainer's GPU time (rocprofv3, profiles/r01_dqn_kernel_stats.csv).  Here one exp and one division
+// give the forward value (mish_exact / mish_grad_exact: tron_mish.hpp has the derivation).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/tron_hip.h"
+#include "tron_mish.hpp"
 
 namespace {
 
-__device__ __forceinline__ float mish1(float x)
-{
-    if (x > 20.0f) return x;
-    const float e = expf(x);
-    const float n = e * (e + 2.0f);
-    return x * (n / (n + 2.0f));
-}
-__device__ __forceinline__ float mish_grad1(float x, float gy)
-{
-    if (x > 20.0f) return gy;
-    const float e = expf(x);
-    const float n = e * (e + 2.0f);
-    const float t = n / (n + 2.0f), u = 2.0f / (n + 2.0f);       // u = 1 - t without the cancellation
-    return gy * (t + x * (u * (1.0f + t)) * (e / (1.0f + e)));   // sech^2 = 1 - t^2 = (1 - t)(1 + t)
-}
+using namespace tron;
 
 __global__ void k_mish_fwd(const float *__restrict__ x, float *__restrict__ y, size_t n4, size_t n)
 {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         const float4 v = reinterpret_cast<const float4 *>(x)[i];
-        reinterpret_cast<float4 *>(y)[i] = make_float4(mish1(v.x), mish1(v.y), mish1(v.z), mish1(v.w));
+        reinterpret_cast<float4 *>(y)[i] = make_float4(mish_exact(v.x), mish_exact(v.y), mish_exact(v.z), mish_exact(v.w));
     }
-    for (size_t i = n4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) y[i] = mish1(x[i]);
+    for (size_t i = n4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) y[i] = mish_exact(x[i]);
 }
 __global__ void k_mish_bwd(const float *__restrict__ x, const float *__restrict__ gy, float *__restrict__ gx, size_t n4,
                            size_t n)
@@ -48,10 +31,10 @@ __global__ void k_mish_bwd(const float *__restrict__ x, const float *__restrict_
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         const float4 v = reinterpret_cast<const float4 *>(x)[i], g = reinterpret_cast<const float4 *>(gy)[i];
         reinterpret_cast<float4 *>(gx)[i] =
-            make_float4(mish_grad1(v.x, g.x), mish_grad1(v.y, g.y), mish_grad1(v.z, g.z), mish_grad1(v.w, g.w));
+            make_float4(mish_grad_exact(v.x, g.x), mish_grad_exact(v.y, g.y), mish_grad_exact(v.z, g.z), mish_grad_exact(v.w, g.w));
     }
     for (size_t i = n4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        gx[i] = mish_grad1(x[i], gy[i]);
+        gx[i] = mish_grad_exact(x[i], gy[i]);
 }
 
 // pre = y + bias[c] (+ residual), out = mish(pre): what follows every convolution of the DQN net
@@ -70,7 +53,7 @@ __global__ void k_bias_mish_fwd(float *__restrict__ y, const float *__restrict__
             v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
         }
         reinterpret_cast<float4 *>(y)[i] = v;
-        reinterpret_cast<float4 *>(out)[i] = make_float4(mish1(v.x), mish1(v.y), mish1(v.z), mish1(v.w));
+        reinterpret_cast<float4 *>(out)[i] = make_float4(mish_exact(v.x), mish_exact(v.y), mish_exact(v.z), mish_exact(v.w));
     }
 }
 
@@ -93,7 +76,7 @@ __global__ __launch_bounds__(256) void k_bias_mish_bwd(const float *__restrict__
         const int n = n0 + i / hw4, q = i - (i / hw4) * hw4;
         const size_t o = ((size_t)n * C + c) * hw4 + q;
         const float4 v = reinterpret_cast<const float4 *>(pre)[o], g = reinterpret_cast<const float4 *>(gy)[o];
-        const float4 r = make_float4(mish_grad1(v.x, g.x), mish_grad1(v.y, g.y), mish_grad1(v.z, g.z), mish_grad1(v.w, g.w));
+        const float4 r = make_float4(mish_grad_exact(v.x, g.x), mish_grad_exact(v.y, g.y), mish_grad_exact(v.z, g.z), mish_grad_exact(v.w, g.w));
         reinterpret_cast<float4 *>(gx)[o] = r;
         acc += (r.x + r.y) + (r.z + r.w);
         amax = fmaxf(fmaxf(amax, fmaxf(fabsf(r.x), fabsf(r.y))), fmaxf(fabsf(r.z), fabsf(r.w)));
