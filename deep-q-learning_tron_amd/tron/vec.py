@@ -214,16 +214,8 @@ class VecTron:
         on this device, any of them None (not recorded), and is returned as it is.  The persistent launches store the
         records as they step (tron_rollout_actions_records); the tensors hold them once the call's work completes on the
         stream."""
-        if not torch.is_tensor(actions):
-            raise TypeError("rollout_actions takes an int8 tensor [K, N, 2]")
-        if actions.dtype != torch.int8:
-            raise TypeError(f"rollout_actions takes int8 actions, got {actions.dtype}")
-        if actions.dim() != 3 or tuple(actions.shape[1:]) != (self.N, 2):
-            raise ValueError(f"expected shape (K, {self.N}, 2), got {tuple(actions.shape)}")
-        if actions.device != self.device:
-            raise ValueError(f"the tape must be on {self.device}, got {actions.device}")
-        if not actions.is_contiguous():
-            raise ValueError("the tape must be contiguous")
+        _checked_tensor(actions, torch.int8, (None, self.N, 2), self.device, "rollout_actions takes an int8 tensor [K, N, 2]",
+                        "rollout_actions takes int8 actions", f"expected shape (K, {self.N}, 2)", "the tape")
         K = int(actions.shape[0])
         if records is not None:
             records = self._record_tapes(records, K)
@@ -253,18 +245,10 @@ class VecTron:
         if not isinstance(records, (tuple, list)) or len(records) != 3:
             raise TypeError("records is None, True or a tuple (reward, done, winner)")
         for t, (name, dtype, shape) in zip(records, spec):
-            if t is None:
-                continue
-            if not torch.is_tensor(t):
-                raise TypeError(f"the {name} records take a {dtype} tensor {shape} or None")
-            if t.dtype != dtype:
-                raise TypeError(f"the {name} records are {dtype}, got {t.dtype}")
-            if tuple(t.shape) != shape:
-                raise ValueError(f"expected {name} records of shape {shape}, got {tuple(t.shape)}")
-            if t.device != self.device:
-                raise ValueError(f"the {name} records must be on {self.device}, got {t.device}")
-            if not t.is_contiguous():
-                raise ValueError(f"the {name} records must be contiguous")
+            if t is not None:
+                _checked_tensor(t, dtype, shape, self.device, f"the {name} records take a {dtype} tensor {shape} or None",
+                                f"the {name} records are {dtype}", f"expected {name} records of shape {shape}",
+                                f"the {name} records")
         return records
 
     def minimax_actions(self, player, mode="voronoi", out=None, want_values=False):
@@ -429,19 +413,59 @@ def minimax_codes(codes, draws=None, mode="voronoi", depth=2):
     return act, values, expanded
 
 
+def _fits(t, shape):
+    """Whether tensor t has the shape `shape`, in which None stands for any size."""
+    return t.dim() == len(shape) and all(want is None or want == got for want, got in zip(shape, t.shape))
+
+
+def _checked_tensor(t, dtype, shape, device, takes, is_dtype, of_shape, name):
+    """The check of a tensor argument: a tensor, of `dtype`, of `shape` (None: any size), on `device`, contiguous — in
+    that order, each fault with its own exception.  The last four arguments are the argument's name as its messages
+    spell it: the whole message for something that is no tensor, the openings of the dtype and the shape message (", got
+    ..." follows), and the subject of "... must be on ..." and "... must be contiguous"."""
+    if not torch.is_tensor(t):
+        raise TypeError(takes)
+    if t.dtype != dtype:
+        raise TypeError(f"{is_dtype}, got {t.dtype}")
+    if not _fits(t, shape):
+        raise ValueError(f"{of_shape}, got {tuple(t.shape)}")
+    if t.device != device:
+        raise ValueError(f"{name} must be on {device}, got {t.device}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    return t
+
+
 def _slide_rates(rates, n, device, what):
     """The checked rates argument of playout_codes / playout_values: float64 [n, 2], contiguous, on the boards' device."""
-    if not torch.is_tensor(rates):
-        raise TypeError(f"{what}: rates is None or a float64 tensor [n, 2]")
-    if rates.dtype != torch.float64:
-        raise TypeError(f"{what}: rates are float64, got {rates.dtype}")
-    if tuple(rates.shape) != (n, 2):
-        raise ValueError(f"{what}: expected rates of shape ({n}, 2), got {tuple(rates.shape)}")
-    if rates.device != device:
-        raise ValueError(f"{what}: rates must be on {device}, got {rates.device}")
-    if not rates.is_contiguous():
-        raise ValueError(f"{what}: rates must be contiguous")
-    return rates
+    return _checked_tensor(rates, torch.float64, (n, 2), device, f"{what}: rates is None or a float64 tensor [n, 2]",
+                           f"{what}: rates are float64", f"{what}: expected rates of shape ({n}, 2)", f"{what}: rates")
+
+
+def _boards(codes, what):
+    """The boards argument of `what` as (contiguous int8 [n, S, S], n, S)."""
+    c = codes.contiguous()
+    if c.dtype != torch.int8 or c.dim() != 3 or c.shape[1] != c.shape[2]:
+        raise ValueError(f"{what} takes int8 boards [n, S, S], got {c.dtype} {tuple(c.shape)}")
+    return c, int(c.shape[0]), int(c.shape[-1])
+
+
+def _key(seed, stream_id, call):
+    """(seed, stream_id, call) as the entries take them: 32, 32 and 64 bits."""
+    return seed & 0xFFFFFFFF, stream_id & 0xFFFFFFFF, int(call) & 0xFFFFFFFFFFFFFFFF
+
+
+def _playout_entry(kind, head, sliding, packed, key, outs):
+    """Calls the "codes" or "values" entry that the arguments choose: tron_playout_weighted_<kind> under weights (which
+    takes the sliding rule's tensors too, None for mode None's rule), else tron_playout_<kind> where rates, the first of
+    `sliding`, is None, else tron_playout_slide_<kind>.  head: the arguments before them, outs: the output tensors."""
+    if packed is not None:
+        name, chosen = f"tron_playout_weighted_{kind}", (*map(nat.ptr, sliding), packed)
+    elif sliding[0] is None:
+        name, chosen = f"tron_playout_{kind}", ()
+    else:
+        name, chosen = f"tron_playout_slide_{kind}", tuple(map(nat.ptr, sliding))
+    nat.check(getattr(nat.lib(), name)(*head, *chosen, *key, *map(nat.ptr, outs), nat.stream_ptr()), name)
 
 
 HUG_WEIGHTS = (0, 4, 2, 1)                                              # measured: profiles/r27_playout_policy_match.txt
@@ -485,14 +509,11 @@ def playout_codes(codes, actions=None, k_steps=None, seed=0x5EED, stream_id=0, c
     territory) in the place of -1; steps and codes are as without it.  The last positions are computed whether or not
     want_codes asks for them."""
     _checked_judge(judge, "playout_codes")
-    c = codes.contiguous()
-    if c.dtype != torch.int8 or c.dim() != 3 or c.shape[1] != c.shape[2]:
-        raise ValueError(f"playout_codes takes int8 boards [n, S, S], got {c.dtype} {tuple(c.shape)}")
-    n, side = int(c.shape[0]), int(c.shape[-1])
+    c, n, side = _boards(codes, "playout_codes")
     packed = None if weights is None else _packed_weights(weights, "playout_codes")
     a = None
-    if actions is not None:
-        if actions.dtype != torch.int8 or actions.dim() != 3 or tuple(actions.shape[1:]) != (n, 2):
+    if actions is not None:                                            # one message for dtype and shape; any strides
+        if actions.dtype != torch.int8 or not _fits(actions, (None, n, 2)):
             raise ValueError(f"expected an int8 tape of shape (K, {n}, 2), got {actions.dtype} {tuple(actions.shape)}")
         a = actions.contiguous()
         if k_steps is None:
@@ -502,16 +523,8 @@ def playout_codes(codes, actions=None, k_steps=None, seed=0x5EED, stream_id=0, c
     if uniforms is not None:
         if rates is None:
             raise ValueError("uniforms belong to the sliding rule: pass rates with them")
-        if not torch.is_tensor(uniforms):
-            raise TypeError("uniforms is None or a float32 tensor [K, n, 2]")
-        if uniforms.dtype != torch.float32:
-            raise TypeError(f"the uniforms are float32, got {uniforms.dtype}")
-        if uniforms.dim() != 3 or tuple(uniforms.shape[1:]) != (n, 2):
-            raise ValueError(f"expected a float32 uniforms tape of shape (K, {n}, 2), got {tuple(uniforms.shape)}")
-        if uniforms.device != c.device:
-            raise ValueError(f"the uniforms must be on {c.device}, got {uniforms.device}")
-        if not uniforms.is_contiguous():
-            raise ValueError("the uniforms must be contiguous")
+        _checked_tensor(uniforms, torch.float32, (None, n, 2), c.device, "uniforms is None or a float32 tensor [K, n, 2]",
+                        "the uniforms are float32", f"expected a float32 uniforms tape of shape (K, {n}, 2)", "the uniforms")
         if k_steps is None:
             k_steps = int(uniforms.shape[0])
         elif int(k_steps) > int(uniforms.shape[0]):
@@ -526,19 +539,9 @@ def playout_codes(codes, actions=None, k_steps=None, seed=0x5EED, stream_id=0, c
     steps = torch.empty(n, dtype=torch.int32, device=c.device)
     winner = torch.empty(n, dtype=torch.int8, device=c.device)
     final = torch.empty_like(c) if want_codes or judge is not None else None
-    key = (seed & 0xFFFFFFFF, stream_id & 0xFFFFFFFF, int(call) & 0xFFFFFFFFFFFFFFFF)
     with torch.cuda.device(c.device):
-        if packed is not None:
-            nat.check(nat.lib().tron_playout_weighted_codes(cp, n, side, int(k_steps), ap, nat.ptr(rates), nat.ptr(uniforms), packed,
-                                                            *key, nat.ptr(steps), nat.ptr(winner), nat.ptr(final),
-                                                            nat.stream_ptr()), "tron_playout_weighted_codes")
-        elif rates is None:
-            nat.check(nat.lib().tron_playout_codes(cp, n, side, int(k_steps), ap, *key, nat.ptr(steps), nat.ptr(winner),
-                                                   nat.ptr(final), nat.stream_ptr()), "tron_playout_codes")
-        else:
-            nat.check(nat.lib().tron_playout_slide_codes(cp, n, side, int(k_steps), ap, nat.ptr(rates), nat.ptr(uniforms), *key,
-                                                         nat.ptr(steps), nat.ptr(winner), nat.ptr(final), nat.stream_ptr()),
-                      "tron_playout_slide_codes")
+        _playout_entry("codes", (cp, n, side, int(k_steps), ap), (rates, uniforms), packed, _key(seed, stream_id, call),
+                       (steps, winner, final))
     if judge is not None:
         winner = torch.where(winner == -1, territory_winner(territory_codes(final)[0]), winner)
     return steps, winner, (final if want_codes else None)
@@ -557,10 +560,7 @@ def territory_codes(codes, want_owner=False):
     infinite, reach1: d1 finite, reach2: d2 finite).  reach1 + reach2 - (first1 + first2 + tied) is 0 exactly when the
     players are cut off from each other.  owner: 1, 2, 3 on first1, first2 and tied cells, 0 elsewhere.  A rejected board
     (not exactly one +10 and one -10 inside the border) gets six -1 and an owner plane of zeros."""
-    c = codes.contiguous()
-    if c.dtype != torch.int8 or c.dim() != 3 or c.shape[1] != c.shape[2]:
-        raise ValueError(f"territory_codes takes int8 boards [n, S, S], got {c.dtype} {tuple(c.shape)}")
-    n, side = int(c.shape[0]), int(c.shape[-1])
+    c, n, side = _boards(codes, "territory_codes")
     cp = nat.ptr(c)                                                    # a host tensor is refused here
     counts = torch.empty(n, 6, dtype=torch.int32, device=c.device)
     owner = torch.empty_like(c) if want_owner else None
@@ -599,10 +599,7 @@ def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, w
     positions, the tallies summed on the device and tron_values_pick.  Memory: two code planes (the copy and the last
     position, 2 * S * S bytes) and 2 * k_steps tape bytes per playout, n * 16 * copies playouts."""
     _checked_judge(judge, "playout_values")
-    c = codes.contiguous()
-    if c.dtype != torch.int8 or c.dim() != 3 or c.shape[1] != c.shape[2]:
-        raise ValueError(f"playout_values takes int8 boards [n, S, S], got {c.dtype} {tuple(c.shape)}")
-    n, side = int(c.shape[0]), int(c.shape[-1])
+    c, n, side = _boards(codes, "playout_values")
     packed = None if weights is None else _packed_weights(weights, "playout_values")
     k_steps, copies = int(k_steps), int(copies)
     if k_steps < 0:
@@ -621,19 +618,9 @@ def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, w
     counts = torch.empty(n, 4, 4, 4, dtype=torch.int32, device=c.device)
     steps = torch.empty(n, 4, 4, dtype=torch.int32, device=c.device)
     actions = torch.empty(n, 2, dtype=torch.int8, device=c.device) if want_actions else None
-    key = (seed & 0xFFFFFFFF, stream_id & 0xFFFFFFFF, int(call) & 0xFFFFFFFFFFFFFFFF)
     with torch.cuda.device(c.device):
-        if packed is not None:
-            nat.check(nat.lib().tron_playout_weighted_values(cp, n, side, k_steps, copies, nat.ptr(rates), packed, *key,
-                                                             nat.ptr(counts), nat.ptr(steps), nat.ptr(actions), nat.stream_ptr()),
-                      "tron_playout_weighted_values")
-        elif rates is None:
-            nat.check(nat.lib().tron_playout_values(cp, n, side, k_steps, copies, *key, nat.ptr(counts), nat.ptr(steps),
-                                                    nat.ptr(actions), nat.stream_ptr()), "tron_playout_values")
-        else:
-            nat.check(nat.lib().tron_playout_slide_values(cp, n, side, k_steps, copies, nat.ptr(rates), *key, nat.ptr(counts),
-                                                          nat.ptr(steps), nat.ptr(actions), nat.stream_ptr()),
-                      "tron_playout_slide_values")
+        _playout_entry("values", (cp, n, side, k_steps, copies), (rates,), packed, _key(seed, stream_id, call),
+                       (counts, steps, actions))
     return counts, steps, actions
 
 

@@ -1,23 +1,17 @@
-"""What the weighted-playout tests share (tests/test_playout_weighted_model_cpu.py, tests/test_gpu_playout_weighted.py): the
-host model of tron_playout_weighted_codes / tron_playout_weighted_values and the inputs both files use.  The model is
-playout_support.Playouts (mode None's rule) or playout_slide_support.SlidePlayouts (the sliding rule) with safe_moves
-alone replaced by the weighted draw of include/tron_hip.h, written here in coordinates: the step stays the oracle's
-orc_step, the slide decision stays SlidePlayouts'.  A plain module, imported by name; nothing here needs a GPU."""
+"""The inputs of the weighted-playout tests (tests/test_playout_weighted_model_cpu.py, tests/test_gpu_playout_weighted.py):
+the weight vectors, the soups with planted dead ends behind them, the values boards and hand-built boards.  The model is
+playout_support's, given weights.  A plain module, imported by name; nothing here needs a GPU."""
 import numpy as np
 
-import oracle
 import playout_support as ps
 import playout_slide_support as pss
 import playout_values_support as pv
-from rollout_support import start_positions
 
 UNIFORM_EQUAL = ((1, 1, 1, 1), (0, 0, 0, 0), (7, 7, 7, 7), (255, 255, 255, 255))   # the uniform draw, bit for bit
 WEIGHTED = ((1, 8, 4, 2), (0, 255, 0, 1), (3, 0, 0, 0))
 WEIGHT_SETS = UNIFORM_EQUAL + WEIGHTED
 CANDIDATES = ((1, 8, 4, 2), (1, 4, 2, 1), (0, 4, 2, 1), (1, 1, 2, 4))     # of scripts/playout_policy_match.py: HUG_WEIGHTS is one
-# what a drawn move can be: the room of the move taken; a safe move of weight 0 beside one that weighs something; all safe
-# moves of weight 0, two or more of them; no safe move; a move other than the uniform draw's at the same u
-DRAW_CLASSES = ("room0", "room1", "room2", "room3", "zero_skipped", "fallback", "no_candidate", "not_uniform")
+DRAW_CLASSES = ps.DRAW_CLASSES
 
 
 def classes_of(weights):
@@ -28,117 +22,6 @@ def classes_of(weights):
 
 def packed(weights):
     return sum(int(w) << (8 * k) for k, w in enumerate(weights))
-
-
-def pick(w, free, u):
-    """The rule's steps 1 and 2 for arrays [..., 4] in UP, RIGHT, DOWN, LEFT order: w the weight of each direction's room
-    (looked at where `free`), u the Philox word [...].  Returns (move, T, cnt)."""
-    free = np.asarray(free, bool)
-    w = np.where(free, np.asarray(w, np.uint64), np.uint64(0))
-    u = np.asarray(u, np.uint64)
-    cnt = free.sum(-1)
-    T = w.sum(-1)
-    x = (u * T) >> np.uint64(32)                                       # mulhi(u, T), < T
-    weighted = (np.cumsum(w, -1) > x[..., None]).argmax(-1)            # the first whose running sum exceeds x
-    j = (u * cnt.astype(np.uint64)) >> np.uint64(32)                   # mulhi(u, cnt): the uniform rule
-    uniform = (free & (np.cumsum(free, -1) - 1 == j[..., None].astype(np.int64))).argmax(-1)
-    return np.where(T > 0, weighted, np.where(cnt > 0, uniform, 0)), T, cnt
-
-
-class _Weighted:
-    """safe_moves under four weights; `drawn` counts the drawn moves of live playouts per DRAW_CLASSES."""
-
-    def set_weights(self, weights):
-        self.weights = np.array(weights, np.uint64)
-        assert self.weights.shape == (4,) and (self.weights <= 255).all()
-        self.drawn = dict.fromkeys(DRAW_CLASSES, 0)
-
-    def rooms(self, rows):
-        """(free bool [m, 2, 4], room int [m, 2, 4]) of players' four moves on the board as it stands: the EMPTY cells
-        among the target's three neighbours other than the mover's head; a cell outside the image is not EMPTY."""
-        v, S = self.v, self.S
-        grid = v.grid[rows].reshape(len(rows), S, S)
-        pos = v.pos[rows].astype(np.int64).reshape(-1, 2, 2) + 1        # [m, player, (r, c)] in the padded image
-        take = np.arange(len(rows))[:, None, None]
-        tr, tc = pos[:, :, 0, None] + ps.DR, pos[:, :, 1, None] + ps.DC  # [m, 2, 4]
-        free = grid[take, tr, tc] == ps.EMPTY                          # a head is strictly inside: its targets are cells
-        room = np.zeros(free.shape, np.int64)
-        for b in range(4):
-            nr, nc = tr + ps.DR[b], tc + ps.DC[b]
-            inside = (nr >= 0) & (nc >= 0) & (nr < S) & (nc < S)
-            back = (np.arange(4) ^ 2) == b                             # direction b from the target of a leads to the head
-            cell = grid[take, np.clip(nr, 0, S - 1), np.clip(nc, 0, S - 1)]
-            room += inside & ~back & (cell == ps.EMPTY)
-        return free, room
-
-    def safe_moves(self, need):
-        out = np.zeros((self.n, 2), np.int8)
-        rows = np.nonzero(need.any(1))[0]
-        if not len(rows):
-            return out
-        free, room = self.rooms(rows)
-        u = np.array([self.philox.words(self.first_index + i, self.t)[:2].copy() for i in rows], np.uint64)
-        move, T, cnt = pick(self.weights[room], free, u)
-        plain = pick(np.ones(4, np.uint64), free, u)[0]
-        out[rows] = np.where(need[rows], move, 0)
-        self.boxed_in[rows] |= (need[rows] & (cnt == 0)).any(1)
-        nd = need[rows]
-        taken = np.take_along_axis(room, move[:, :, None], 2)[:, :, 0]
-        zero = (free & (self.weights[room] == 0)).any(2)
-        for k in range(4):
-            self.drawn[f"room{k}"] += int((nd & (cnt > 0) & (taken == k)).sum())
-        self.drawn["zero_skipped"] += int((nd & (T > 0) & zero).sum())
-        self.drawn["fallback"] += int((nd & (T == 0) & (cnt >= 2)).sum())
-        self.drawn["no_candidate"] += int((nd & (cnt == 0)).sum())
-        self.drawn["not_uniform"] += int((nd & (move != plain)).sum())
-        return out
-
-    def tally(self):
-        return dict(self.drawn, **super().tally())
-
-
-class WeightedPlayouts(_Weighted, ps.Playouts):
-    def __init__(self, codes, weights, **key):
-        super().__init__(codes, **key)
-        self.set_weights(weights)
-
-
-class WeightedSlidePlayouts(_Weighted, pss.SlidePlayouts):
-    def __init__(self, codes, weights, rates, uniforms=None, **key):
-        super().__init__(codes, rates, uniforms, **key)
-        self.set_weights(weights)
-
-
-def playout(codes, weights, rates=None, actions=None, uniforms=None, k_steps=None, ks=None, **key):
-    """The model of one tron_playout_weighted_codes call, at several k_steps at once: {k: ((steps, winner, codes), tally)}
-    for every k in `ks` (default: k_steps alone), as playout_support.playout.  rates=None: mode None's rule."""
-    assert rates is not None or uniforms is None
-    ks = sorted(set([k_steps] if ks is None else ks))
-    m = WeightedPlayouts(codes, weights, **key) if rates is None else WeightedSlidePlayouts(codes, weights, rates, uniforms, **key)
-    out = {}
-    for t in range(ks[-1] + 1):
-        if t in ks:
-            out[t] = (m.result(k0=t == 0), m.tally())
-        if t < ks[-1] and m.live().any():
-            m.step(None if actions is None else actions[t])
-        elif t < ks[-1]:
-            m.t += 1
-    return out
-
-
-def values_model(codes, weights, k_steps, copies, rates=None, ks=None, **key):
-    """The model of one tron_playout_weighted_values call, built as playout_values_support.values_model is: the weighted
-    codes model on the fanned-out launch (board i's rates row for all its playouts), tallied.  (counts, steps, actions),
-    or with `ks` {k: that triple}."""
-    many = sorted(set([k_steps] if ks is None else ks))
-    n = len(codes)
-    boards, tape = pv.fan_out(codes, many[-1], copies)
-    fanned = None if rates is None else np.repeat(np.asarray(rates, np.float64), 16 * copies, axis=0)
-    out = {}
-    for k, ((steps, winner, _), _) in playout(boards, weights, fanned, tape, ks=many, **key).items():
-        counts, total = pv.tally(steps, winner, n, copies)
-        out[k] = (counts, total, pv.pick(counts))
-    return out if ks is not None else out[k_steps]
 
 
 # ---- the inputs of the GPU tests ------------------------------------------------------------------------------------------
@@ -155,23 +38,13 @@ KEY = dict(seed=0xB0A7, stream_id=6, call=(2 << 32) | 27)
 TAPES = ("none", "mixed")
 RULES = ("plain", "slide")
 
-_cache = {}
-
 
 def planted_boards(W, n=EXTRA_N, seed=None):
     """[n, S, S] positions of uniform safe-move model games after 0..W-1 steps (the last live one of a game that ends
     earlier); where the head of player 1 (even boards) or 2 (odd boards) has two safe moves or more, one of those that
     lead strictly inside the border is made a dead end: the EMPTY neighbours of its target take the player's trail."""
     rs = np.random.RandomState(EXTRA_SEEDS[W] if seed is None else seed)
-    S = W + 2
-    fresh = np.stack([oracle.state_for_player(oracle.game_init(W, s), 1) for s in start_positions(rs, n, W)])
-    length = rs.randint(0, W, n)
-    m = ps.Playouts(fresh, seed=rs.randint(1 << 30), stream_id=4, call=rs.randint(1 << 30))
-    boards = fresh.copy()
-    for t in range(int(length.max())):
-        m.step()
-        keep = m.live() & (length > t)
-        boards[keep] = oracle.state_for_player(m.v.grid[keep], 1).reshape(-1, S, S)
+    boards = ps.stopped_games(rs, W, n, W, stream_id=4)
     for i, b in enumerate(boards):
         head, trail = (10, -2) if i % 2 == 0 else (-10, -3)
         r, c = np.argwhere(b == head)[0]
@@ -187,29 +60,28 @@ def planted_boards(W, n=EXTRA_N, seed=None):
     return boards
 
 
+@ps.once
 def soup_boards(W):
-    """int8 [N, S, S]: the soup's boards, then the planted ones; computed once per process and never changed."""
-    if ("boards", W) not in _cache:
-        _cache["boards", W] = np.concatenate([ps.soup(W)[0], planted_boards(W)])
-    return _cache["boards", W]
+    """int8 [N, S, S]: the soup's boards, then the planted ones."""
+    return np.concatenate([ps.soup(W)[0], planted_boards(W)])
+
+
+@ps.once
+def soup_tapes_and_rates(W):
+    return ps.soup_tapes(W, n=N), pss.soup_rates(W, n=N)
 
 
 def soup_inputs(W, rule, tape):
     """(boards, rates | None, tape | None) of one GPU case."""
-    if ("tapes", W) not in _cache:
-        _cache["tapes", W] = (ps.soup_tapes(W, n=N), pss.soup_rates(W, n=N))
-    tapes, rates = _cache["tapes", W]
+    tapes, rates = soup_tapes_and_rates(W)
     return soup_boards(W), (rates if rule == "slide" else None), tapes[tape]
 
 
+@ps.once
 def soup_model(W, weights, rule, tape):
-    """{k: ((steps, winner, codes), tally)} at soup_ks(W) of the N boards of width W under KEY, computed once per process
-    and never changed."""
-    at = (W, tuple(weights), rule, tape)
-    if at not in _cache:
-        boards, rates, actions = soup_inputs(W, rule, tape)
-        _cache[at] = playout(boards, weights, rates, actions, ks=ps.soup_ks(W), **KEY)
-    return _cache[at]
+    """{k: ((steps, winner, codes), tally)} at soup_ks(W) of the N boards of width W under KEY."""
+    boards, rates, actions = soup_inputs(W, rule, tape)
+    return ps.playout(boards, actions, ks=ps.soup_ks(W), rates=rates, weights=weights, **KEY)
 
 
 def values_boards(W):
@@ -220,13 +92,11 @@ def values_rates(W):
     return pss.soup_rates(W)[list(pv.SELECT)]
 
 
+@ps.once
 def values_soup_model(W, weights, rule, copies):
     """{k: (counts, steps, actions)} of playout_values_support's 38 boards of width W at its ks(W) under KEY."""
-    at = ("values", W, tuple(weights), rule, copies)
-    if at not in _cache:
-        rates = values_rates(W) if rule == "slide" else None
-        _cache[at] = values_model(values_boards(W), weights, None, copies, rates, ks=pv.ks(W), **KEY)
-    return _cache[at]
+    rates = values_rates(W) if rule == "slide" else None
+    return ps.values_model(values_boards(W), None, copies, ks=pv.ks(W), rates=rates, weights=weights, **KEY)
 
 
 # ---- hand-built boards: a head with two safe moves, one into a dead end and one into the open --------------------------

@@ -4,9 +4,7 @@ builders, the boards both files use, and a list of wrong models that the inputs 
 module, imported by name; nothing here needs a GPU."""
 import numpy as np
 
-import oracle
 import playout_support as ps
-from rollout_support import start_positions
 
 INF = np.int32(1 << 30)
 FIRST1, FIRST2, TIED, NEITHER, REACH1, REACH2 = range(6)
@@ -205,27 +203,7 @@ PLANT_N = 320
 def early_boards(W, n=EARLY_N, seed=None):
     """The soup's recipe (playout_support.soup_boards) with at most W steps played, rejected boards included."""
     rs = np.random.RandomState(7000 + W if seed is None else seed)
-    S = W + 2
-    fresh = np.stack([oracle.state_for_player(oracle.game_init(W, s), 1) for s in start_positions(rs, n, W)])
-    length = rs.randint(0, W + 1, n)
-    m = ps.Playouts(fresh, seed=rs.randint(1 << 30), stream_id=4, call=rs.randint(1 << 30))
-    boards = fresh.copy()
-    for t in range(int(length.max())):
-        m.step()
-        keep = m.live() & (length > t)
-        boards[keep] = oracle.state_for_player(m.v.grid[keep], 1).reshape(-1, S, S)
-    for i in range(5, n, 53):
-        b, kind = boards[i], (i // 53) % 3
-        r, c = np.argwhere(b == 10)[0]
-        if kind == 0:
-            b[r, c] = -2
-        elif kind == 1:
-            er, ec = np.argwhere(b == 1)[0] if (b == 1).any() else np.argwhere(b == -1)[0]
-            b[er, ec] = 10
-        else:
-            b[r, c] = -2
-            b[0, c] = 10
-    return boards
+    return ps.spoil_some(ps.stopped_games(rs, W, n, W + 1, stream_id=4))
 
 
 def planted_boards(W, n=PLANT_N):
@@ -288,19 +266,13 @@ def planted_boards(W, n=PLANT_N):
     return np.concatenate([np.stack(doors), np.stack(pockets), rings, rejected])
 
 
-_cache = {}
-
-
+@ps.once
 def boards(W):
-    """Every board of width W the tests use: the soup, the early boards, the planted boards.  Computed once per process
-    and never changed."""
-    if ("b", W) not in _cache:
-        _cache[("b", W)] = np.concatenate([ps.soup_boards(W), early_boards(W), planted_boards(W)])
-    return _cache[("b", W)]
+    """Every board of width W the tests use: the soup, the early boards, the planted boards."""
+    return np.concatenate([ps.soup_boards(W), early_boards(W), planted_boards(W)])
 
 
+@ps.once
 def expected(W):
-    """model(boards(W)), computed once per process and never changed."""
-    if ("m", W) not in _cache:
-        _cache[("m", W)] = model(boards(W))
-    return _cache[("m", W)]
+    """model(boards(W))."""
+    return model(boards(W))

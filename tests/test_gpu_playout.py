@@ -7,34 +7,11 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from playout_gpu_support import mods, dev, run, same  # noqa: F401 (mods is a fixture)
 import playout_support as ps
 import rollout_support as rs
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def mods():
-    tv, _ = rs.gpu_modules()
-    import torch
-    return tv, torch
-
-
-def dev(torch, a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def run(mods, boards, tape, k_steps, **key):
-    """playout_codes with want_codes on host arrays -> (steps, winner, codes) as host arrays."""
-    tv, torch = mods
-    s, w, c = tv.playout_codes(dev(torch, boards), dev(torch, tape), k_steps, want_codes=True, **key)
-    torch.cuda.synchronize()
-    return rs.np_(s), rs.np_(w), rs.np_(c)
-
-
-def same(got, exp, tag):
-    for name, g, e in zip(("steps", "winner", "codes"), got, exp):
-        assert g.dtype == e.dtype and g.shape == e.shape and np.array_equal(g, e), (tag, name)
 
 
 @pytest.mark.parametrize("name", ["episodes_none_4", "episodes_none_10"])

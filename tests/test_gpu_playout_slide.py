@@ -1,6 +1,6 @@
 """tron_playout_slide_codes / tron_playout_slide_values, tron.vec.playout_codes / playout_values with rates, VecTron's
 rates= keyword and play.rating's "montecarlo-slide" seat on the GPU, against the recorded sliding episodes, the host
-model of tests/playout_slide_support.py and the mode-None entries.  Every comparison is exact.
+model of tests/playout_support.py and the mode-None entries.  Every comparison is exact.
 tests/test_playout_slide_model_cpu.py shows, without a GPU, that the model reproduces the recorded episodes and that the
 inputs used here meet every class of step and ending."""
 import ctypes as C
@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from playout_gpu_support import mods, dev, run, same, composed  # noqa: F401 (mods is a fixture)
 import playout_support as ps
 import playout_slide_support as pss
 import playout_values_support as pv
@@ -17,44 +18,19 @@ import rollout_support as rs
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def mods():
-    tv, _ = rs.gpu_modules()
-    import torch
-    return tv, torch
-
-
-def dev(torch, a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def run(mods, boards, rates, tape, k_steps, uniforms=None, **key):
-    """playout_codes with rates and want_codes on host arrays -> (steps, winner, codes) as host arrays."""
-    tv, torch = mods
-    s, w, c = tv.playout_codes(dev(torch, boards), dev(torch, tape), k_steps, want_codes=True, rates=dev(torch, rates),
-                               uniforms=dev(torch, uniforms), **key)
-    torch.cuda.synchronize()
-    return rs.np_(s), rs.np_(w), rs.np_(c)
-
-
-def same(got, exp, tag, names=("steps", "winner", "codes")):
-    for name, g, e in zip(names, got, exp):
-        assert g.dtype == e.dtype and g.shape == e.shape and np.array_equal(g, e), (tag, name)
-
-
 @pytest.mark.parametrize("name", ["episodes_ice_4", "episodes_temper_4"])
 def test_recorded_suffixes(mods, name):
     """Every suffix of every recorded sliding episode in one launch, under the recorded uniforms and rates: the remaining
     length, the recorded winner and final_obs1."""
     boards, tape, u, rates, length, winner, final = pss.suffixes(load_golden(name))
-    same(run(mods, boards, rates, tape, len(tape), u), (length, winner, final), name)
+    same(run(mods, boards, tape, len(tape), rates=rates, uniforms=u), (length, winner, final), name)
 
 
 @pytest.mark.parametrize("name", ["episodes_ice_4", "episodes_ice_10", "episodes_ice_24", "episodes_temper_4",
                                   "episodes_temper_10", "episodes_temper_24"])
 def test_recorded_episodes_from_the_start(mods, name):
     boards, tape, u, rates, length, winner, final = pss.starts(load_golden(name))
-    same(run(mods, boards, rates, tape, len(tape), u), (length, winner, final), name)
+    same(run(mods, boards, tape, len(tape), rates=rates, uniforms=u), (length, winner, final), name)
 
 
 @pytest.mark.parametrize("W", ps.SOUP_WIDTHS)
@@ -67,18 +43,18 @@ def test_soups_against_the_model(mods, W):
             exp, tally = model[name][k]
             if name == "none" and k in (1, 7):
                 assert tally["unfinished"] > 0 and tally["slide"] > 0     # out_codes of an unfinished playout with slide tiles
-            same(run(mods, boards, rates, tape, k, **ps.SOUP_KEY), exp, (W, name, k))
+            same(run(mods, boards, tape, k, rates=rates, **ps.SOUP_KEY), exp, (W, name, k))
 
 
 def test_hand_built_boards(mods):
     """The orderings of one step, forced: player 2's slide tile on player 1's new cell, player 1's on player 2's target,
     both onto the border, a slide onto a trail — the endings worked out by hand, under a tape and under uniforms of 0."""
     boards, tape, rates, steps, winner, final = pss.hand_built()
-    same(run(mods, boards, rates, tape, 1), (steps, winner, final), "drawn uniforms")
-    same(run(mods, boards, rates, tape, 1, np.zeros((1, 4, 2), np.float32)), (steps, winner, final), "taped uniforms")
+    same(run(mods, boards, tape, 1, rates=rates), (steps, winner, final), "drawn uniforms")
+    same(run(mods, boards, tape, 1, rates=rates, uniforms=np.zeros((1, 4, 2), np.float32)), (steps, winner, final), "taped uniforms")
     # ... and a uniform above every rate of 1 slides nowhere: mode None's step
     plain = ps.playout(boards, tape, k_steps=1)[1][0]
-    same(run(mods, boards, rates, tape, 1, np.full((1, 4, 2), 1.25, np.float32)), plain, "no slide")
+    same(run(mods, boards, tape, 1, rates=rates, uniforms=np.full((1, 4, 2), 1.25, np.float32)), plain, "no slide")
 
 
 @pytest.mark.parametrize("W", [5, 24])
@@ -107,27 +83,27 @@ def test_draw_keying(mods):
     twice, rates2 = np.concatenate([boards[:m], boards[:m]]), np.concatenate([rates[:m], rates[:m]])
     K = W * W
     # with drawn moves and uniforms each index follows its own draws, under every key
-    base = pss.playout(twice, rates2, None, k_steps=K, **ps.SOUP_KEY)[K][0]
+    base = ps.playout(twice, None, k_steps=K, rates=rates2, **ps.SOUP_KEY)[K][0]
     assert not np.array_equal(base[0][:m], base[0][m:])
-    same(run(mods, twice, rates2, None, K, **ps.SOUP_KEY), base, "own index")
+    same(run(mods, twice, None, K, rates=rates2, **ps.SOUP_KEY), base, "own index")
     # ... scripted moves leave the slide uniforms to the index
     tape = np.concatenate([ps.soup(W)[1]["full"][:, :m]] * 2, 1)
-    scripted = pss.playout(twice, rates2, tape, k_steps=K, **ps.SOUP_KEY)[K][0]
+    scripted = ps.playout(twice, tape, k_steps=K, rates=rates2, **ps.SOUP_KEY)[K][0]
     assert not np.array_equal(scripted[2][:m], scripted[2][m:])
-    same(run(mods, twice, rates2, tape, K, **ps.SOUP_KEY), scripted, "scripted moves")
+    same(run(mods, twice, tape, K, rates=rates2, **ps.SOUP_KEY), scripted, "scripted moves")
     # ... and a uniforms tape leaves nothing to it
     u = np.concatenate([np.random.RandomState(5).random_sample((K, m, 2)).astype(np.float32)] * 2, 1)
-    got = run(mods, twice, rates2, tape, K, u, **ps.SOUP_KEY)
+    got = run(mods, twice, tape, K, rates=rates2, uniforms=u, **ps.SOUP_KEY)
     same([g[:m] for g in got], [g[m:] for g in got], "same tapes")
-    same(got, pss.playout(twice, rates2, tape, u, k_steps=K, **ps.SOUP_KEY)[K][0], "taped")
+    same(got, ps.playout(twice, tape, k_steps=K, rates=rates2, uniforms=u, **ps.SOUP_KEY)[K][0], "taped")
     for change in (dict(call=ps.SOUP_KEY["call"] + 1), dict(call=ps.SOUP_KEY["call"] + (1 << 32)), dict(seed=1),
                    dict(stream_id=6)):
         key = dict(ps.SOUP_KEY, **change)
-        exp = pss.playout(twice, rates2, tape, k_steps=K, **key)[K][0]
+        exp = ps.playout(twice, tape, k_steps=K, rates=rates2, **key)[K][0]
         assert not np.array_equal(exp[2], scripted[2]), change         # the moves are scripted: only the slides differ
-        same(run(mods, twice, rates2, tape, K, **key), exp, change)
+        same(run(mods, twice, tape, K, rates=rates2, **key), exp, change)
     # a launch of the first half agrees with the launch of the whole on its rows
-    same(run(mods, twice[:m], rates2[:m], None, K, **ps.SOUP_KEY), [g[:m] for g in base], "half")
+    same(run(mods, twice[:m], None, K, rates=rates2[:m], **ps.SOUP_KEY), [g[:m] for g in base], "half")
 
 
 @pytest.mark.parametrize("W", [5, 24])
@@ -166,21 +142,6 @@ def test_output_discipline(mods, W):
     assert np.array_equal(rs.np_(rates), rates_h, equal_nan=True)
 
 
-def composed(mods, boards, rates, K, copies, **key):
-    """tron_playout_slide_values' definition, run: playout_codes with rates on the copied boards and rate rows under the
-    constructed tape, tallied on the host."""
-    tv, torch = mods
-    n, per = len(boards), 16 * copies
-    q = torch.arange(n * per, device="cuda")
-    tape = torch.full((K, n * per, 2), -1, dtype=torch.int8, device="cuda")
-    move = (q // copies) % 16
-    tape[0, :, 0], tape[0, :, 1] = (move >> 2).to(torch.int8), (move & 3).to(torch.int8)
-    steps, winner, _ = tv.playout_codes(dev(torch, boards).repeat_interleave(per, dim=0), tape, K,
-                                        rates=dev(torch, rates).repeat_interleave(per, dim=0), **key)
-    counts, total = pv.tally(rs.np_(steps), rs.np_(winner), n, copies)
-    return counts, total, pv.pick(counts)
-
-
 @pytest.mark.parametrize("W", [4, 10, 24])
 def test_values_are_the_composition(mods, W):
     """67 boards at copies 1 and 3 — 1 072 and 3 216 playouts, no multiple of 64, waves that straddle boards: counts,
@@ -193,7 +154,7 @@ def test_values_are_the_composition(mods, W):
     rejected = np.zeros(n, bool)
     rejected[[5, 58]] = True
     for copies in (1, 3):
-        exp = composed(mods, boards, rates, K, copies, **pv.KEY)
+        exp = composed(mods, boards, K, copies, rates=rates, **pv.KEY)
         got = tuple(rs.np_(t) for t in tv.playout_values(dev(torch, boards), K, copies, rates=dev(torch, rates), **pv.KEY))
         same(got, exp, (W, copies), ("counts", "steps", "actions"))
         assert (got[0][~rejected].sum(3) == copies).all() and (got[0][rejected] == 0).all()
@@ -254,7 +215,7 @@ def test_vectron(mods, mode):
     got = tuple(rs.np_(t) for t in got)
     fork, fork_rates = boards.repeat_interleave(copies, dim=0), rates.repeat_interleave(copies, dim=0)
     same(tuple(rs.np_(t) for t in tv.playout_codes(fork, k_steps=K, want_codes=True, rates=fork_rates, **key)), got, "playout_codes")
-    same(got, pss.playout(rs.np_(fork), rs.np_(fork_rates), None, k_steps=K, **key)[K][0], "model")
+    same(got, ps.playout(rs.np_(fork), None, k_steps=K, rates=rs.np_(fork_rates), **key)[K][0], "model")
     assert (got[1] >= 0).any() and (got[1] == -1).any()
     for x, y in zip(values, tv.playout_values(boards, K, copies, rates=rates, **key)):
         assert torch.equal(x, y)

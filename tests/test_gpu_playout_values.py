@@ -1,5 +1,5 @@
 """tron_playout_values / tron.vec.playout_values / VecTron.playout_values / montecarlo_actions / play.rating's
-"montecarlo" seat on the GPU, against the host model of tests/playout_values_support.py and against tron_playout_codes
+"montecarlo" seat on the GPU, against the host model of tests/playout_support.py and against tron_playout_codes
 itself.  Every comparison is exact.  tests/test_playout_values_model_cpu.py shows, without a GPU, that the boards used
 here meet every class of ending."""
 import ctypes as C
@@ -7,34 +7,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from playout_gpu_support import VALUES, mods, dev, run_values, same  # noqa: F401 (mods is a fixture)
 import playout_support as ps
 import playout_values_support as pv
 import rollout_support as rs
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def mods():
-    tv, _ = rs.gpu_modules()
-    import torch
-    return tv, torch
-
-
-def dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def run(mods, boards, k_steps, copies, **key):
-    tv, torch = mods
-    out = tv.playout_values(dev(torch, boards), k_steps, copies, **key)
-    torch.cuda.synchronize()
-    return tuple(rs.np_(t) for t in out)
-
-
-def same(got, exp, tag):
-    for name, g, e in zip(("counts", "steps", "actions"), got, exp):
-        assert g.dtype == e.dtype and g.shape == e.shape and np.array_equal(g, e), (tag, name)
 
 
 @pytest.mark.parametrize("W", pv.WIDTHS)
@@ -45,7 +23,7 @@ def test_against_the_model(mods, W):
     for copies in pv.COPIES:
         model = pv.model(W, copies)
         for k in pv.ks(W):
-            same(run(mods, boards, k, copies, **pv.KEY), model[k], (W, copies, k))
+            same(run_values(mods, boards, k, copies, **pv.KEY), model[k], (W, copies, k), VALUES)
 
 
 @pytest.mark.parametrize("W", [5, 24])
@@ -61,9 +39,9 @@ def test_against_the_existing_kernel(mods, W):
     move = (q // copies) % 16
     tape[0, :, 0], tape[0, :, 1] = (move >> 2).to(torch.int8), (move & 3).to(torch.int8)
     steps, winner, _ = tv.playout_codes(codes.repeat_interleave(16 * copies, dim=0), tape, K, **pv.KEY)
-    exp = pv.tally(rs.np_(steps), rs.np_(winner), n, copies)
-    got = run(mods, boards, K, copies, **pv.KEY)
-    same(got, exp + (pv.pick(exp[0]),), W)
+    exp = ps.tally(rs.np_(steps), rs.np_(winner), n, copies)
+    got = run_values(mods, boards, K, copies, **pv.KEY)
+    same(got, exp + (ps.pick(exp[0]),), W, VALUES)
     assert (got[0].reshape(n, -1).sum(1) == 0).sum() == len(range(5, n, 53))   # the soup's rejected boards, and no other
     assert all((got[0][..., c] > 0).any() for c in range(3)) and got[0][..., 3].sum() == 0
 
@@ -77,9 +55,9 @@ def test_keying(mods):
     for change in (dict(call=pv.KEY["call"] + 1), dict(call=pv.KEY["call"] + (1 << 32)), dict(seed=1), dict(stream_id=6)):
         exp = pv.model(W, copies, **change)[K]
         assert not np.array_equal(exp[0], base[0]), change
-        same(run(mods, boards, K, copies, **dict(pv.KEY, **change)), exp, change)
+        same(run_values(mods, boards, K, copies, **dict(pv.KEY, **change)), exp, change, VALUES)
     for m in (1, 7, 23):                                               # 23 * 48 playouts: the last wave is ragged
-        same(run(mods, boards[:m], K, copies, **pv.KEY), [x[:m] for x in base], ("first", m))
+        same(run_values(mods, boards[:m], K, copies, **pv.KEY), [x[:m] for x in base], ("first", m), VALUES)
 
 
 @pytest.mark.parametrize("W", [5, 10])
@@ -123,7 +101,7 @@ def test_forced_move(mods, copies):
     b[4, 4], b[4, 5] = -10, -3                                         # its trail leaves UP, DOWN and LEFT free; RIGHT is not
     b2 = b.copy()
     b2[4, 5] = 1                                                       # ... and a player 2 with four safe moves
-    counts, steps, actions = run(mods, np.stack([b, b2]), 1, copies, **pv.KEY)
+    counts, steps, actions = run_values(mods, np.stack([b, b2]), 1, copies, **pv.KEY)
     assert actions[:, 0].tolist() == [2, 2]
     for a1 in (0, 1, 3):
         assert (counts[1, a1, :, 2] == copies).all() and (counts[0, a1, [0, 2, 3], 2] == copies).all()
@@ -152,8 +130,8 @@ def test_handle_untouched(mods):
     boards = tv.encode_codes(a.grid(), 1)
     key = dict(seed=0xABC, stream_id=2, call=4)
     got = tuple(rs.np_(t) for t in got)
-    same(tuple(rs.np_(t) for t in tv.playout_values(boards, K, copies, **key)), got, "playout_values")
-    same(got, pv.values_model(rs.np_(boards), K, copies, **key), "model")
+    same(tuple(rs.np_(t) for t in tv.playout_values(boards, K, copies, **key)), got, "playout_values", VALUES)
+    same(got, ps.values_model(rs.np_(boards), K, copies, **key), "model", VALUES)
     assert (got[0][..., 3] > 0).any() and (got[0][..., 1] > 0).any() and (got[0][..., 2] > 0).any()
     for p in (0, 1):
         assert mc[p].dtype == torch.int8 and np.array_equal(rs.np_(mc[p]), got[2][:, p])

@@ -1,11 +1,12 @@
 """tron_playout_weighted_codes / tron_playout_weighted_values, weights= on tron.vec.playout_codes / playout_values and on
 VecTron.playout / playout_values / montecarlo_actions, and play.rating's mc_weights on the GPU, against the host model of
-tests/playout_weighted_support.py, the existing entries and hand-built boards.  Every comparison is exact.
+tests/playout_support.py, the existing entries and hand-built boards.  Every comparison is exact.
 tests/test_playout_weighted_model_cpu.py shows, without a GPU, that the inputs used here meet every kind of drawn move and
 that a kernel which ignored the weights would fail here."""
 import numpy as np
 import pytest
 
+from playout_gpu_support import mods, dev, run, same, changed_cells, composed  # noqa: F401 (mods is a fixture)
 import playout_support as ps
 import playout_slide_support as pss
 import playout_values_support as pv
@@ -13,31 +14,6 @@ import playout_weighted_support as pw
 import rollout_support as rs
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def mods():
-    tv, _ = rs.gpu_modules()
-    import torch
-    return tv, torch
-
-
-def dev(torch, a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def run(mods, boards, weights, rates, tape, k_steps, uniforms=None, **key):
-    """playout_codes with weights and want_codes on host arrays -> (steps, winner, codes) as host arrays."""
-    tv, torch = mods
-    s, w, c = tv.playout_codes(dev(torch, boards), dev(torch, tape), k_steps, want_codes=True, rates=dev(torch, rates),
-                               uniforms=dev(torch, uniforms), weights=weights, **key)
-    torch.cuda.synchronize()
-    return rs.np_(s), rs.np_(w), rs.np_(c)
-
-
-def same(got, exp, tag, names=("steps", "winner", "codes")):
-    for name, g, e in zip(names, got, exp):
-        assert g.dtype == e.dtype and g.shape == e.shape and np.array_equal(g, e), (tag, name)
 
 
 @pytest.mark.parametrize("W", pw.WIDTHS)
@@ -51,7 +27,7 @@ def test_soups_against_the_model(mods, W, weights):
             boards, rates, actions = pw.soup_inputs(W, rule, tape)
             model = pw.soup_model(W, weights, rule, tape)
             for k in ps.soup_ks(W):
-                same(run(mods, boards, weights, rates, actions, k, **pw.KEY), model[k][0], (W, weights, rule, tape, k))
+                same(run(mods, boards, actions, k, rates=rates, weights=weights, **pw.KEY), model[k][0], (W, weights, rule, tape, k))
 
 
 @pytest.mark.parametrize("W", pw.WIDTHS)
@@ -78,10 +54,6 @@ def test_equal_weights_are_the_existing_entries(mods, W):
                 assert all(torch.equal(a, b) for a, b in zip(plain, got)), (W, copies, sorted(kw), weights)
 
 
-def changed_cells(before, after):
-    return {tuple(rc) for rc in np.argwhere(before != after)}
-
-
 def test_dead_end_or_open(mods):
     """A head with exactly two safe moves, a dead end (room 0) and an open cell (room 3): (1,0,0,0) takes the dead end and
     (0,0,0,1) the open cell whatever the draw — for either player, in all eight orientations, under several calls and
@@ -93,17 +65,17 @@ def test_dead_end_or_open(mods):
     for weights, move in (((1, 0, 0, 0), dead), ((0, 0, 0, 1), opened)):
         for call in (0, 1, 2, (5 << 32) | 3, 77):
             for rates in (None, never):
-                steps, winner, final = run(mods, boards, weights, rates, None, 1, seed=9, stream_id=1, call=call)
+                steps, winner, final = run(mods, boards, None, 1, rates=rates, weights=weights, seed=9, stream_id=1, call=call)
                 assert (steps == 1).all() and (winner == -1).all(), (weights, call)
                 for i in range(m):
                     r, c = np.argwhere(boards[i] == head_code[i])[0]
                     tr, tc = r + ps.DR[move[i]], c + ps.DC[move[i]]
                     assert final[i, tr, tc] == head_code[i] and final[i, r, c] == (-2 if player[i] == 1 else -3), (weights, call, i)
                     assert len(changed_cells(boards[i], final[i])) == 4, (weights, call, i)
-                same((steps, winner, final), pw.playout(boards, weights, rates, k_steps=1, seed=9, stream_id=1, call=call)[1][0],
+                same((steps, winner, final), ps.playout(boards, k_steps=1, seed=9, stream_id=1, call=call, rates=rates, weights=weights)[1][0],
                      (weights, call))
     # the dead end is the end: one step later its taker has no safe move, goes UP and dies
-    steps, winner, _ = run(mods, boards, (1, 0, 0, 0), None, None, 2, seed=9, stream_id=1, call=0)
+    steps, winner, _ = run(mods, boards, None, 2, rates=None, weights=(1, 0, 0, 0), seed=9, stream_id=1, call=0)
     assert (steps == 2).all() and (winner == np.where(player == 1, 2, 1)).all()
 
 
@@ -120,9 +92,9 @@ def test_borders_corners_and_a_second_wave(mods):
     key = dict(seed=31, stream_id=2, call=(1 << 32) | 5)
     for weights in ((1, 0, 0, 0), (0, 0, 0, 1), (1, 8, 4, 2), (0, 255, 0, 1)):
         for rates in (None, np.full((65, 2), 0.5)):
-            exp = pw.playout(boards, weights, rates, ks=(1, 3, 16), **key)
+            exp = ps.playout(boards, ks=(1, 3, 16), rates=rates, weights=weights, **key)
             for k in (1, 3, 16):
-                got = run(mods, boards, weights, rates, None, k, **key)
+                got = run(mods, boards, None, k, rates=rates, weights=weights, **key)
                 same(got, exp[k][0], (weights, rates is None, k))
                 if k == 1:
                     assert all(len(changed_cells(b, f)) <= (4 if rates is None else 6) for b, f in zip(boards, got[2]))
@@ -131,20 +103,8 @@ def test_borders_corners_and_a_second_wave(mods):
     odd = raw[3:].view(65, 6, 6)
     odd.copy_(dev(torch, boards))
     out = tv.playout_codes(odd, None, 16, want_codes=True, weights=(1, 8, 4, 2), **key)
-    same(tuple(rs.np_(t) for t in out), pw.playout(boards, (1, 8, 4, 2), ks=(16,), **key)[16][0], "odd address")
+    same(tuple(rs.np_(t) for t in out), ps.playout(boards, ks=(16,), weights=(1, 8, 4, 2), **key)[16][0], "odd address")
     assert np.array_equal(rs.np_(odd), boards) and not rs.np_(raw[:3]).any()
-
-
-def composed(mods, boards, weights, rates, K, copies, **key):
-    """tron_playout_weighted_values' definition, run: the weighted codes entry on the copied boards (and rate rows) under the
-    constructed tape at the defined launch indices, tallied on the host."""
-    tv, torch = mods
-    n, per = len(boards), 16 * copies
-    fanned, tape = pv.fan_out(boards, K, copies)
-    kw = {} if rates is None else dict(rates=dev(torch, rates).repeat_interleave(per, dim=0))
-    steps, winner, _ = tv.playout_codes(dev(torch, fanned), dev(torch, tape), K, weights=weights, **kw, **key)
-    counts, total = pv.tally(rs.np_(steps), rs.np_(winner), n, copies)
-    return counts, total, pv.pick(counts)
 
 
 @pytest.mark.parametrize("W", pw.WIDTHS)
@@ -165,7 +125,7 @@ def test_values(mods, W, weights):
                 got = tuple(rs.np_(t) for t in tv.playout_values(codes, k, copies, weights=weights, **kw, **pw.KEY))
                 same(got, model[k], (W, weights, rule, copies, k), names)
             got = tuple(rs.np_(t) for t in tv.playout_values(codes, W * W, copies, weights=weights, **kw, **pw.KEY))
-            same(got, composed(mods, boards, weights, rates, W * W, copies, **pw.KEY), (W, weights, rule, copies), names)
+            same(got, composed(mods, boards, W * W, copies, rates=rates, weights=weights, **pw.KEY), (W, weights, rule, copies), names)
         plain = tuple(rs.np_(t) for t in tv.playout_values(codes, W * W, 5, **kw, **pw.KEY))
         assert not np.array_equal(plain[0], got[0])                    # the weights are looked at
 
@@ -246,7 +206,7 @@ def test_vectron(mods, mode):
     fork = boards.repeat_interleave(copies, dim=0)
     for x, y in zip(got, tv.playout_codes(fork, k_steps=K, want_codes=True, weights=weights, **fork_rates, **key)):
         assert torch.equal(x, y)
-    exp = pw.playout(rs.np_(fork), weights, rs.np_(fork_rates["rates"]) if fork_rates else None, k_steps=K, **key)[K][0]
+    exp = ps.playout(rs.np_(fork), k_steps=K, rates=rs.np_(fork_rates["rates"]) if fork_rates else None, weights=weights, **key)[K][0]
     same(tuple(rs.np_(t) for t in got), exp, "model")
     for x, y in zip(values, tv.playout_values(boards, K, copies, weights=weights, **rates, **key)):
         assert torch.equal(x, y)

@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from playout_gpu_support import TERRITORY, mods, dev, run_territory, same  # noqa: F401 (mods is a fixture)
 import playout_support as ps
 import playout_values_support as pv
 import rollout_support as rs
@@ -17,38 +18,12 @@ pytestmark = pytest.mark.gpu
 COUNT_FILL, OWNER_FILL = 0x5A5A5A5A, 0x77
 
 
-@pytest.fixture(scope="module")
-def mods():
-    tv, _ = rs.gpu_modules()
-    import torch
-    assert callable(tv.territory_codes) and callable(tv.territory_winner)      # the feature: without it every test fails here
-    return tv, torch
-
-
-def dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def run(mods, boards, want_owner=True):
-    tv, torch = mods
-    counts, owner = tv.territory_codes(dev(torch, boards), want_owner=want_owner)
-    torch.cuda.synchronize()
-    return rs.np_(counts), (None if owner is None else rs.np_(owner))
-
-
-def same(got, exp, tag):
-    for name, g, e in zip(("counts", "owner"), got, exp):
-        assert g.dtype == e.dtype and g.shape == e.shape, (tag, name)
-        bad = np.nonzero((g != e).reshape(len(g), -1).any(1))[0]
-        assert not len(bad), (tag, name, bad[:5], g[bad[:1]], e[bad[:1]])
-
-
 @pytest.mark.parametrize("W", terr.WIDTHS)
 def test_counts_and_owner_equal_the_model(mods, W):
     """The soup, the early boards and the planted boards of the width, rejected boards included."""
     boards, exp = terr.boards(W), terr.expected(W)
-    same(run(mods, boards), exp, W)
-    counts, owner = run(mods, boards, want_owner=False)
+    same(run_territory(mods, boards), exp, W, TERRITORY)
+    counts, owner = run_territory(mods, boards, want_owner=False)
     assert owner is None and np.array_equal(counts, exp[0])
     tv, torch = mods
     assert np.array_equal(rs.np_(tv.territory_winner(dev(torch, exp[0]))), terr.winner(exp[0]))
@@ -85,7 +60,7 @@ def test_hand_built_boards_at_the_instantiation_boundaries(mods, S):
     split = exp[1][5]
     assert (split[2:S // 2, S - 2] == 1).all() and (split[S // 2 + 1:S - 2, S - 2] == 2).all()
     assert exp[0][5][4] + exp[0][5][5] == exp[0][5][:3].sum()        # separated
-    same(run(mods, boards), exp, S)
+    same(run_territory(mods, boards), exp, S, TERRITORY)
 
 
 @pytest.mark.parametrize("S", (8, 16, 32, 34))
@@ -97,7 +72,7 @@ def test_serpentine_next_to_empty_arenas(mods, S):
     boards = np.stack([snake if i in (1, 6, 19) else plain for i in range(21)])
     exp = terr.model(boards)
     assert exp[0][1][0] == exp[0][1][4] == (snake == 1).sum() and exp[0][1][5] == 0
-    same(run(mods, boards), exp, S)
+    same(run_territory(mods, boards), exp, S, TERRITORY)
 
 
 @pytest.mark.parametrize("W", (4, 10, 24))
@@ -109,10 +84,10 @@ def test_a_ring_of_ones_between_ordinary_boards(mods, W):
     exp = terr.model(boards)
     mixed = boards.copy()
     mixed[1::2] = terr.ring_of_ones(boards[1::2])
-    same(run(mods, mixed), exp, W)
+    same(run_territory(mods, mixed), exp, W, TERRITORY)
     mixed = boards.copy()
     mixed[0::2] = terr.ring_of_ones(boards[0::2])
-    same(run(mods, mixed), exp, W)
+    same(run_territory(mods, mixed), exp, W, TERRITORY)
 
 
 def raw(mods, codes_ptr, n, side, counts, owner, row=1):
@@ -179,7 +154,7 @@ def test_misaligned_boards_at_the_end_of_the_allocation(mods, W):
         check_guarded(counts, owner, n, exp)
         assert (rs.np_(obuf[:off]) == OWNER_FILL).all() and np.array_equal(rs.np_(codes), boards)
         got = tv.territory_codes(codes, want_owner=True)
-        same((rs.np_(got[0]), rs.np_(got[1])), exp, (W, off))
+        same((rs.np_(got[0]), rs.np_(got[1])), exp, (W, off), TERRITORY)
 
 
 def test_refused_arguments_write_nothing(mods):
@@ -257,7 +232,7 @@ def test_playout_values_judge_full_length(mods, W):
     assert (got[0][..., 3] == 0).all() and np.array_equal(got[0].sum(-1), plain[0].sum(-1))
     whole = done.all((1, 2))
     assert whole.any() and np.array_equal(got[2][whole], plain[2][whole])
-    assert np.array_equal(got[2], pv.pick(got[0]))
+    assert np.array_equal(got[2], ps.pick(got[0]))
 
 
 @pytest.mark.parametrize("W", pv.WIDTHS)
@@ -267,15 +242,15 @@ def test_playout_values_judge_one_step(mods, W):
     tv, torch = mods
     boards, copies = pv.boards(W), 3
     n = len(boards)
-    fanned, tape = pv.fan_out(boards, 1, copies)
+    fanned, tape = ps.fan_out(boards, 1, copies)
     (steps, winner, final), _ = ps.playout(fanned, tape, k_steps=1, **pv.KEY)[1]
-    counts, total = pv.tally(steps, judged(winner, final), n, copies)
+    counts, total = ps.tally(steps, judged(winner, final), n, copies)
     assert (winner == -1).any() and counts[..., 3].sum() == 0
     for want_actions in (True, False):
         got = tv.playout_values(dev(torch, boards), 1, copies, want_actions=want_actions, judge="territory", **pv.KEY)
         assert np.array_equal(rs.np_(got[0]), counts) and np.array_equal(rs.np_(got[1]), total)
         assert got[0].dtype == torch.int32 and got[1].dtype == torch.int32
-        assert (got[2] is None) if not want_actions else np.array_equal(rs.np_(got[2]), pv.pick(counts))
+        assert (got[2] is None) if not want_actions else np.array_equal(rs.np_(got[2]), ps.pick(counts))
 
 
 def test_values_pick_equals_playout_values_actions(mods):
@@ -289,7 +264,7 @@ def test_values_pick_equals_playout_values_actions(mods):
         assert nat.lib().tron_values_pick(nat.ptr(counts), n, C.c_void_p(out.data_ptr() + 2), nat.stream_ptr()) == nat.OK
         torch.cuda.synchronize()
         assert torch.equal(out[1:n + 1], actions) and (rs.np_(out[[0, n + 1]]) == 0x55).all()
-        assert (rs.np_(actions) == -1).any() and np.array_equal(rs.np_(actions), pv.pick(rs.np_(counts)))
+        assert (rs.np_(actions) == -1).any() and np.array_equal(rs.np_(actions), ps.pick(rs.np_(counts)))
     fill = out.clone()
     assert nat.lib().tron_values_pick(None, n, nat.ptr(out), nat.stream_ptr()) == nat.ERR_BAD_ARG
     assert nat.lib().tron_values_pick(nat.ptr(counts), n, None, nat.stream_ptr()) == nat.ERR_BAD_ARG

@@ -1,4 +1,4 @@
-"""The host model of tron_playout_slide_codes (tests/playout_slide_support.py) against the sliding episodes recorded
+"""The host model of tron_playout_slide_codes (tests/playout_support.py with rates) against the sliding episodes recorded
 from the reference and against the mode-None model, the coverage of the inputs the GPU tests play, and the product
 boundary of the two entry points.  No GPU."""
 import ctypes as C
@@ -12,7 +12,7 @@ import playout_slide_support as pss
 
 
 def check_batch(boards, tape, uniforms, rates, length, winner, final, tag):
-    (steps, win, codes), _ = pss.playout(boards, rates, tape, uniforms, k_steps=len(tape))[len(tape)]
+    (steps, win, codes), _ = ps.playout(boards, tape, k_steps=len(tape), rates=rates, uniforms=uniforms)[len(tape)]
     assert np.array_equal(steps, length), tag
     assert np.array_equal(win, winner), tag
     assert np.array_equal(codes, final), tag
@@ -41,12 +41,12 @@ def test_never_sliding_is_mode_none(W):
     boards, tapes, plain = ps.soup(W)
     rates = np.full((len(boards), 2), -1.0)
     for name, tape in tapes.items():
-        got = pss.playout(boards, rates, tape, ks=ps.soup_ks(W), **ps.SOUP_KEY)
+        got = ps.playout(boards, tape, ks=ps.soup_ks(W), rates=rates, **ps.SOUP_KEY)
         for k in ps.soup_ks(W):
             for g, e in zip(got[k][0], plain[name][k][0]):
                 assert np.array_equal(g, e), (W, name, k)
             assert all(got[k][1][cls] == cnt for cls, cnt in plain[name][k][1].items())
-            assert not any(got[k][1][cls] for cls in pss.SLIDE_CLASSES)
+            assert not any(got[k][1][cls] for cls in ps.SLIDE_CLASSES)
 
 
 def test_uniform_as_specified():
@@ -56,12 +56,12 @@ def test_uniform_as_specified():
     codes = oracle.state_for_player(oracle.game_init(5, [2, 2, 0, 4]), 1)[None]
     key = dict(seed=123, stream_id=4, call=(5 << 32) | 6)
     words = oracle.philox([17, 9, 6, 5], [123, 4])
-    u = pss.philox_uniform(words[2:])
+    u = ps.philox_uniform(words[2:])
     assert u.dtype == np.float32 and np.array_equal(u, ((words[2:] >> 8) / 2.0 ** 24).astype(np.float32))
     for rates, exp in (([float(u[0]), np.nextafter(np.float64(u[1]), -1.0)], [True, False]),
                        ([np.nextafter(np.float64(u[0]), -1.0), float(u[1])], [False, True]),
                        ([float("nan"), 1.5], [False, True]), ([-0.0, -1e-300], [bool(u[0] == 0), False])):
-        m = pss.SlidePlayouts(codes, np.array([rates]), first_index=17, **key)
+        m = ps.Playouts(codes, np.array([rates]), first_index=17, **key)
         m.t = 9
         assert m.slides(np.array([True])).tolist() == [exp]
 
@@ -70,7 +70,7 @@ def test_hand_built_boards():
     """Four one-step boards that force the orderings of a step: the model gives the endings worked out by hand and meets
     both ordering classes, a double slide, a slide onto the border and a slide onto a trail."""
     boards, tape, rates, steps, winner, final = pss.hand_built()
-    (got, tally), = pss.playout(boards, rates, tape, k_steps=1).values()
+    (got, tally), = ps.playout(boards, tape, k_steps=1, rates=rates).values()
     for g, e in zip(got, (steps, winner, final)):
         assert g.dtype == e.dtype and np.array_equal(g, e)
     assert tally["p1_dies_on_p2_tile"] == 1 and tally["p2_target_filled"] == 1

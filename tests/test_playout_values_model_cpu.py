@@ -1,4 +1,4 @@
-"""The product boundary of tron_playout_values, the maximin of tests/playout_values_support.py on matrices written by
+"""The product boundary of tron_playout_values, the maximin of tests/playout_support.py on matrices written by
 hand, and the coverage of the inputs tests/test_gpu_playout_values.py plays, shown on the host model alone.  No GPU."""
 import ctypes as C
 import os
@@ -7,6 +7,7 @@ import re
 import numpy as np
 import pytest
 
+import playout_support as ps
 import playout_values_support as pv
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -48,35 +49,35 @@ def test_pick_by_hand():
          [-4, 1, 2, 6],
          [2, 1, 3, 4],
          [0, 2, -5, 7]]
-    assert pv.pick(counts_of(m)).tolist() == [[2, 1]]
+    assert ps.pick(counts_of(m)).tolist() == [[2, 1]]
     # a full tie: UP for both
-    assert pv.pick(counts_of(np.zeros((4, 4), int))).tolist() == [[0, 0]]
-    assert pv.pick(counts_of(np.full((4, 4), -3))).tolist() == [[0, 0]]
+    assert ps.pick(counts_of(np.zeros((4, 4), int))).tolist() == [[0, 0]]
+    assert ps.pick(counts_of(np.full((4, 4), -3))).tolist() == [[0, 0]]
     # a tie between two moves: the first of them (rows 1 and 3 both have worst case 2; columns 2 and 3 both worst case 4)
     m = [[1, 9, 4, 0],
          [5, 2, 4, 4],
          [0, 7, 3, 4],
          [6, 9, 2, 2]]
-    assert pv.pick(counts_of(m)).tolist() == [[1, 2]]
+    assert ps.pick(counts_of(m)).tolist() == [[1, 2]]
     # player 2's negation: it minimises player 1's payoff, so where player 1 wins everything but column 3 it plays 3
     m = np.full((4, 4), 5)
     m[:, 3] = -5
-    assert pv.pick(counts_of(m)).tolist() == [[0, 3]]
+    assert ps.pick(counts_of(m)).tolist() == [[0, 3]]
     # nothing played: a rejected board
-    assert pv.pick(np.zeros((2, 4, 4, 4), np.int32)).tolist() == [[-1, -1], [-1, -1]]
+    assert ps.pick(np.zeros((2, 4, 4, 4), np.int32)).tolist() == [[-1, -1], [-1, -1]]
 
 
 def test_fan_out_index():
     """Index q = ((i * 16 + a1 * 4 + a2) * copies + j) holds board i and plays (a1, a2) first."""
     codes = np.arange(3 * 36, dtype=np.int8).reshape(3, 6, 6)
     copies = 3
-    boards, tape = pv.fan_out(codes, 4, copies)
+    boards, tape = ps.fan_out(codes, 4, copies)
     assert boards.shape == (3 * 16 * copies, 6, 6) and tape.shape == (4, 3 * 16 * copies, 2)
     for i, a1, a2, j in ((0, 0, 0, 0), (1, 2, 3, 1), (2, 3, 3, 2), (2, 0, 1, 0)):
         q = (i * 16 + a1 * 4 + a2) * copies + j
         assert np.array_equal(boards[q], codes[i]) and tape[0, q].tolist() == [a1, a2]
     assert (tape[1:] < 0).all()
-    assert pv.fan_out(codes, 0, copies)[1].shape == (0, 3 * 16 * copies, 2)
+    assert ps.fan_out(codes, 0, copies)[1].shape == (0, 3 * 16 * copies, 2)
 
 
 @pytest.mark.parametrize("W", pv.WIDTHS)

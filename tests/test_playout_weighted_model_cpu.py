@@ -1,4 +1,4 @@
-"""The host model of tron_playout_weighted_codes / tron_playout_weighted_values (tests/playout_weighted_support.py): the
+"""The host model of tron_playout_weighted_codes / tron_playout_weighted_values (tests/playout_support.py with weights): the
 cumulative pick on hand-written matrices, the weight vectors that are the uniform draw against the mode-None and sliding
 models, the coverage of the inputs the GPU tests play, the product boundary of the two entries and the checks of
 weights= that need no device.  No GPU."""
@@ -27,34 +27,34 @@ def test_cumulative_pick_by_hand():
     w, free = [3, 0, 5, 2], [True] * 4
     expected = {0: 0, 2: 0, 3: 2, 7: 2, 8: 3, 9: 3}
     for x, move in expected.items():
-        got, T, cnt = pw.pick(w, free, u_of(x, 10))
+        got, T, cnt = ps.weighted_pick(w, free, u_of(x, 10))
         assert (int(got), int(T), int(cnt)) == (move, 10, 4), x
     # UP and DOWN are no candidates, whatever their room weighs: running sums 0, 4, 4, 5
     w, free = [9, 4, 9, 1], [False, True, False, True]
     for x, move in {0: 1, 3: 1, 4: 3}.items():
-        got, T, cnt = pw.pick(w, free, u_of(x, 5))
+        got, T, cnt = ps.weighted_pick(w, free, u_of(x, 5))
         assert (int(got), int(T), int(cnt)) == (move, 5, 2), x
     # T = 1020, the largest sum: x = T - 1 at the largest word, and the running sums 255, 510, 765
     w = [255] * 4
     assert ((0xFFFFFFFF * 1020) >> 32) == 1019
     for x, move in {0: 0, 254: 0, 255: 1, 509: 1, 510: 2, 764: 2, 765: 3, 1019: 3}.items():
-        assert int(pw.pick(w, free=[True] * 4, u=u_of(x, 1020))[0]) == move, x
-    assert int(pw.pick(w, [True] * 4, 0xFFFFFFFF)[0]) == 3
+        assert int(ps.weighted_pick(w, free=[True] * 4, u=u_of(x, 1020))[0]) == move, x
+    assert int(ps.weighted_pick(w, [True] * 4, 0xFFFFFFFF)[0]) == 3
     # T == 0: candidates[mulhi(u, cnt)] — the second of three at u = 2^32 / 3 rounded up; no candidate: UP
-    got, T, cnt = pw.pick([0, 0, 0, 0], [True, False, True, True], u_of(1, 3))
+    got, T, cnt = ps.weighted_pick([0, 0, 0, 0], [True, False, True, True], u_of(1, 3))
     assert (int(got), int(T), int(cnt)) == (2, 0, 3)
-    assert int(pw.pick([0, 0, 0, 0], [True, False, True, True], u_of(1, 3) - 1)[0]) == 0
-    assert int(pw.pick([7, 7, 7, 7], [False] * 4, 0xDEADBEEF)[0]) == 0
+    assert int(ps.weighted_pick([0, 0, 0, 0], [True, False, True, True], u_of(1, 3) - 1)[0]) == 0
+    assert int(ps.weighted_pick([7, 7, 7, 7], [False] * 4, 0xDEADBEEF)[0]) == 0
     # a single non-zero weight on one candidate: the move does not depend on u
     for u in (0, 1, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFF):
-        assert int(pw.pick([0, 0, 6, 0], [True] * 4, u)[0]) == 2
+        assert int(ps.weighted_pick([0, 0, 6, 0], [True] * 4, u)[0]) == 2
     # equal weights are the uniform pick at every u of a sweep, for every set of candidates
     us = np.arange(0, 1 << 32, 0x01000193, dtype=np.uint64)
     for mask in range(16):
         free = np.array([[bool(mask >> a & 1) for a in range(4)]] * len(us))
-        plain = pw.pick(np.ones(4), free, us)[0]
+        plain = ps.weighted_pick(np.ones(4), free, us)[0]
         for w in (7, 255):
-            assert np.array_equal(pw.pick(np.full(4, w), free, us)[0], plain), (mask, w)
+            assert np.array_equal(ps.weighted_pick(np.full(4, w), free, us)[0], plain), (mask, w)
 
 
 def test_rooms_by_hand():
@@ -62,14 +62,14 @@ def test_rooms_by_hand():
     not EMPTY."""
     boards, player, dead, opened = pw.dead_end_boards()
     assert len(boards) == 16
-    m = pw.WeightedPlayouts(boards, (1, 1, 1, 1))
+    m = ps.Playouts(boards, weights=(1, 1, 1, 1))
     free, room = m.rooms(np.arange(len(boards)))
     for i in range(len(boards)):
         p = player[i] - 1
         assert free[i, p].sum() == 2 and free[i, p, dead[i]] and free[i, p, opened[i]], i
         assert room[i, p, dead[i]] == 0 and room[i, p, opened[i]] == 3, i
     leaky = pw.border_boards()[-2:]
-    free, room = pw.WeightedPlayouts(leaky, (1, 1, 1, 1)).rooms(np.arange(2))
+    free, room = ps.Playouts(leaky, weights=(1, 1, 1, 1)).rooms(np.arange(2))
     # head at (1, 1) under an EMPTY border: UP and LEFT are on the ring, two of their neighbours are ring cells
     assert free[0, 0].tolist() == [True, True, True, True] and room[0, 0].tolist() == [2, 3, 3, 2]
     assert free[1, 0].tolist() == [True, True, True, True] and room[1, 0].tolist() == [3, 2, 2, 3]
@@ -83,8 +83,8 @@ def test_equal_weights_are_the_uniform_draw(W):
     _, _, rates, slide = pss.soup(W)
     for weights in pw.UNIFORM_EQUAL:
         for name, tape in tapes.items():
-            got = pw.playout(boards, weights, None, tape, ks=ps.soup_ks(W), **ps.SOUP_KEY)
-            got_slide = pw.playout(boards, weights, rates, tape, ks=ps.soup_ks(W), **ps.SOUP_KEY)
+            got = ps.playout(boards, tape, ks=ps.soup_ks(W), rates=None, weights=weights, **ps.SOUP_KEY)
+            got_slide = ps.playout(boards, tape, ks=ps.soup_ks(W), rates=rates, weights=weights, **ps.SOUP_KEY)
             for k in ps.soup_ks(W):
                 for g, e in zip(got[k][0] + got_slide[k][0], plain[name][k][0] + slide[name][k][0]):
                     assert g.dtype == e.dtype and np.array_equal(g, e), (W, weights, name, k)
@@ -93,10 +93,10 @@ def test_equal_weights_are_the_uniform_draw(W):
 
 
 def test_values_model_at_equal_weights():
-    """The values model at equal weights is playout_values_support's, and the sliding one its composition."""
+    """The values model at equal weights is the one without weights, and the sliding one its composition."""
     W, copies = 5, 3
     for k, exp in pv.model(W, copies).items():
-        got = pw.values_model(pv.boards(W), (7, 7, 7, 7), k, copies, **pv.KEY)
+        got = ps.values_model(pv.boards(W), k, copies, weights=(7, 7, 7, 7), **pv.KEY)
         assert all(np.array_equal(g, e) for g, e in zip(got, exp)), k
     got = pw.values_soup_model(W, (1, 8, 4, 2), "slide", copies)[W * W]
     played = ps.decode(pv.boards(W))[2]
