@@ -147,6 +147,20 @@ __device__ __forceinline__ void start_cells(int S, uint32_t nstart, uint32_t &h1
     h1 = (uint32_t)cell_index(S, (int)(int8_t)(nstart), (int)(int8_t)(nstart >> 8));
     h2 = (uint32_t)cell_index(S, (int)(int8_t)(nstart >> 16), (int)(int8_t)(nstart >> 24));
 }
+// The two start cells as one word, 16 + 16 bits (head 1 low): what a restart that works in cell space takes in place of
+// nstart (k_obs_roll's start ring).  cells_pos is the way back to pack_pos: cell = (r + 1) S + (c + 1) with both terms in
+// [0, S), so the quotient and the remainder by S are r + 1 and c + 1.
+__device__ __forceinline__ uint32_t start_cells_word(int S, uint32_t nstart)
+{
+    uint32_t h1, h2;
+    start_cells(S, nstart, h1, h2);
+    return h1 | (h2 << 16);
+}
+__device__ __forceinline__ uint32_t cells_pos(int S, int cell1, int cell2)
+{
+    const uint32_t q0 = (uint32_t)cell1 / (uint32_t)S, q1 = (uint32_t)cell2 / (uint32_t)S;
+    return pack_pos((int)q0 - 1, cell1 - (int)q0 * S - 1, (int)q1 - 1, cell2 - (int)q1 * S - 1);
+}
 __device__ __forceinline__ uint32_t restart_word(int S, uint32_t nstart)
 {
     uint32_t h1, h2;

@@ -69,6 +69,7 @@
 #include <string.h>
 #include <new>
 #include <type_traits>
+#include <type_traits>
 
 using namespace tron;
 
@@ -981,11 +982,14 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 // block's action bytes in the lane's registers, the board in the lane's own region of LDS (4 bits per cell, above).
 // The state is carried DECODED and in CELL SPACE: the two heads' indices into the padded board (no r and no c: the index
 // determines both, and collide / settle have cell-space overloads with the argument, tron_device.hpp), the LDS address
-// and nibble shift of each head's dword and its chunk's mask bit, alive, done, winner, the two last actions + 1 (the
-// non-reversing policy), eplen and tick.  The prologue unpacks st4 into them once; a step moves a head's cell by +-1 or
+// and nibble shift of each head's dword, alive, done, winner, the two last actions + 1 (the non-reversing policy), eplen
+// and tick (deriving the two counters in the epilogue instead was built and taken out again: alone it lengthened the
+// stamped step, profiles/r31_rollout_ab.txt).  The prologue unpacks st4 once; a step moves a head's cell by +-1 or
 // +-S — one signed byte of the launch-uniform word cell_deltas(S), picked by the action — and derives the rest of the new
-// head from that, and the old heads' cells, addresses and bits are simply the ones the step before computed; a restart
-// sets them all from rs4.nstart; the epilogue divides r and c back out of the cells (one division by S per env and
+// head from that, and the old heads' cells and addresses are simply the ones the step before computed; a restart
+// sets them all from the next game's start cells, which the start ring holds IN CELL SPACE (start_cells_word: roll_cell
+// of each player, 16 + 16 bits; rs4.nstart is converted once by the prologue and back by the epilogue of a lane that
+// restarted); the epilogue divides r and c back out of the cells (one division by S per env and
 // launch) and packs st4 once, under st_dirty, into the bytes stepped_st4 / restarted_st4 of the env's last event would
 // have left.  A block's action bytes are consumed once where they are loaded, so no step waits for them: between a
 // step's last LDS operation and the next step's reads stands no s_waitcnt, and the restart's start-ring read is waited
@@ -1010,20 +1014,25 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 //          template.
 //   dirty: the chunks whose bytes in memory may differ from the env's board — 0 after the prologue.
 // Invariants: stale & mask == 0; a chunk outside mask | stale holds the template in LDS; stale is a subset of dirty.
+// The chunks of the two heads of a game in progress are in mask, and from the launch's first step on in dirty: a head
+// cell is not the template's EMPTY, so the entry (compare or entry mask) has its chunk in mask; a move puts the NEW
+// heads' chunks into both, a restart its heads; and dirty takes the entry heads' chunks once, behind the prologue (a
+// chunk stored for that alone is stored with the bytes memory has).  So a move marks its two new chunks and no more.
 // The prologue builds mask by comparing what it reads with the template, whoever wrote it (every writer of the API leaves the
 // player-2 plane the swap_codes4 image of the player-1 plane, and the caller never writes the buffer); stale starts at 0.
 // Nothing is compared in the loop.
 // A restart wipes nothing: stale |= mask & ~heads, dirty |= mask | heads, mask = heads (the chunks of the two new heads), and
-// only the head chunks are written, straight-line — the template's two dwords each, the head nibbles XORed in in registers —
-// and leave stale.  Most of a trail's chunks are never looked at again before the next restart; the few that are, are known
-// at the moment they are looked at:
+// only the head chunks are written, straight-line — the template's two dwords of each, THEN the two head nibbles (two
+// lds_set_nibble: a lane's LDS operations execute in order, so the nibbles land on the template bytes whichever chunk
+// write came last, both heads in one chunk or one dword included) — and leave stale.  Most of a trail's chunks are
+// never looked at again before the next restart; the few that are, are known at the moment they are looked at:
 // A move reads the two new heads' cells alone, one dword each (the old heads' cells are only overwritten), and only a new
 // head can lie in a stale chunk (the old heads' chunks are in mask).  The template's chunks of the two new heads are read in
 // the same LDS round trip as the two dwords; where the chunk is stale the cell's nibble is taken from the template, and the
 // chunk is refreshed (the template's two dwords) in front of the four cell writes and leaves stale.  The four writes are
 // four ds_mskor_b32 (lds_set_nibble: memory = (memory & ~mask) | data on the cell's dword) in the reference's order; a
 // lane's LDS operations execute in order, so cells that share a dword need no merging in registers.  plain_targets and collide so see what the wiped board would have shown, an out-of-bounds head on
-// the border wall and both heads in one stale chunk included.  A move marks the chunks of its four cells in mask and dirty.
+// the border wall and both heads in one stale chunk included.  A move marks the chunks of its two new heads in mask and dirty.
 // A lane writes only its own board in the loop, so the loop needs no fence and no wave barrier.
 // The epilogue stores dirty & (mask | mask0), mask0 being the mask the prologue built: a chunk outside both is the template
 // (in LDS or as a stale chunk) and was the template in memory when the launch began, so the bytes are equal.  That filter
@@ -1071,7 +1080,11 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 //   actions  [2][64] x ROLL_R bytes: action_byte of step s of env `lane` is byte s % ROLL_R of slot (s / ROLL_R) & 1
 //   starts   [2 ROLL_R][64] dwords: make_game_starts(env, episode0 + j), the start of the game the env's j-th restart of
 //            the launch draws, in slot (episode0 + j) % (2 ROLL_R): the slot of an ABSOLUTE episode, so that a ring image
-//            still means something to the next launch, whose episode0 has moved on (Hand-off below)
+//            still means something to the next launch, whose episode0 has moved on (Hand-off below).  A slot holds the
+//            start IN CELL SPACE: start_cells_word, roll_cell of player 1 | roll_cell of player 2 << 16.  Every writer of
+//            a slot converts once (the top-up loop here, the game wave's ROLL_GAME_STARTS draws); the restart reads
+//            cells and converts nothing, and neither does a handed entry: hand[0 .. 2 ROLL_R) are slots as they are.
+//            The format is the blob's own, written and read by this library alone, within one process.
 // and reads one word per env and block, counts[64]: the env's restarts so far.
 constexpr int ROLL_R = 8;
 // A launch flag of the host's own (rollout_wave), beside the TRON_STEP_* bits: every env's entry mask describes its planes.
@@ -1187,7 +1200,7 @@ __device__ __forceinline__ void roll_helper(const Params &P, int env, bool autor
 {
     ROLL_HSTAMP(0);
     const uint32_t seed = P.seed, stream = P.stream;
-    const int W = P.W, fair = P.fair;
+    const int W = P.W, fair = P.fair, S = P.S;
     const uint32_t tick0 = st.w - ((autoreset && (st.y & META_DONE)) ? 1u : 0u), ep0 = rs.y;
     const int nb = (k_steps + ROLL_R - 1) / ROLL_R;
     uint32_t *abytes = reinterpret_cast<uint32_t *>(aring);
@@ -1271,7 +1284,7 @@ __device__ __forceinline__ void roll_helper(const Params &P, int env, bool autor
             const uint32_t upto = b < 0 ? to - min(game_starts, to) : to;   // (block 0's last ordinals may be the game wave's)
 #pragma nounroll
             for (uint32_t j = hi + 1u; j <= upto; ++j)              // (per lane: nothing where hi >= upto)
-                sring[((ep0 + j) & (2u * ROLL_R - 1u)) * WAVE + (uint32_t)lane] = make_game_starts(seed, stream, W, fair, (uint32_t)env, ep0 + j);
+                sring[((ep0 + j) & (2u * ROLL_R - 1u)) * WAVE + (uint32_t)lane] = start_cells_word(S, make_game_starts(seed, stream, W, fair, (uint32_t)env, ep0 + j));
             hi = max(hi, to);
         }
         if (last) {
@@ -1331,7 +1344,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
     // per game wave: the helper's rings (roll_rings) and the restart counts the game lanes publish per block
     uint32_t *rings = tmpl + ((2u * cpe + (size_t)gw * (32u * cpe) + 1u) & ~(size_t)1u) + (size_t)wave * ROLL_RING_DWORDS;
     uint2 *aring = reinterpret_cast<uint2 *>(rings);                // [2][64]: a block's ROLL_R action bytes per env
-    uint32_t *sring = rings + 4 * WAVE;                             // [2 ROLL_R][64]: pack_pos of restart ordinal j in slot j % (2 ROLL_R)
+    uint32_t *sring = rings + 4 * WAVE;                             // [2 ROLL_R][64]: start_cells_word of restart ordinal j in slot (episode0 + j) % (2 ROLL_R)
     uint32_t *cring = sring + 2 * ROLL_R * WAVE;                    // [2][64]: the env's restarts in the launch before block b, in slot b & 1
     // (a tape has no policy: its instantiation holds nothing of TRON_STEP_NONREVERSING)
     const bool autoreset = (flags & TRON_STEP_AUTORESET) != 0u, nonrev = !TAPE && (flags & TRON_STEP_NONREVERSING) != 0u;
@@ -1455,7 +1468,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
                 const uint32_t to = (uint32_t)min(ROLL_R, k_steps);
 #pragma nounroll
                 for (uint32_t j = to - game_starts + 1u; j <= to; ++j)
-                    sring[((rs.y + j) & (2u * ROLL_R - 1u)) * WAVE + (uint32_t)lane] = make_game_starts(P.seed, P.stream, P.W, P.fair, (uint32_t)env, rs.y + j);
+                    sring[((rs.y + j) & (2u * ROLL_R - 1u)) * WAVE + (uint32_t)lane] = start_cells_word(S, make_game_starts(P.seed, P.stream, P.W, P.fair, (uint32_t)env, rs.y + j));
             }
         } else {
             // The wave reads its envs' player-1 planes one env at a time, lane = chunk (coalesced), packs them into the env's
@@ -1509,12 +1522,15 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         cell[1] = roll_cell(S, r[1], c[1]);
     }
     const uint32_t deltas = cell_deltas(S);                         // launch-uniform: one SGPR
-    unsigned long long hbit[2] = {1ull << (cell[0] >> 4), 1ull << (cell[1] >> 4)};   // the heads' chunks, as mask bits
     uint32_t alive = st.y & 3u;
     bool done = (st.y & META_DONE) != 0u;
     int winner = (int)((st.y >> 4) & 3u);
     uint32_t last[2] = {(st.y >> 8) & 0xFu, (st.y >> 12) & 0xFu};   // the players' last actions + 1, 0 before a game's first move
+    // The heads' chunks of a game in progress are in mask (the invariants above) and a move marks only the NEW heads' chunks;
+    // the chunks of the heads the launch begins with are marked dirty here, once.
+    if (mine && !done) dirty = (1ull << (cell[0] >> 4)) | (1ull << (cell[1] >> 4));
     uint32_t eplen = st.z, tick = st.w;
+    rs.z = start_cells_word(S, rs.z);                               // rs4.nstart in the ring's format (the epilogue converts it back; every lane, a launch without autoreset's zero word too: never read there)
     const uint32_t board_lds = (uint32_t)(uintptr_t)(lds_u32 *)board;
     uint32_t hdw[2] = {lds_cell_dword(board_lds, (uint32_t)cell[0]), lds_cell_dword(board_lds, (uint32_t)cell[1])};   // the heads' dwords in LDS
     uint32_t hsh[2] = {lds_cell_shift((uint32_t)cell[0]), lds_cell_shift((uint32_t)cell[1])};                         // and their nibbles' shifts
@@ -1531,6 +1547,11 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         ab = aring[((s0 / ROLL_R) & 1) * WAVE + lane];
         asm volatile("" : "+v"(ab.x), "+v"(ab.y));                  // consumed here, once: the wait for the block's bytes stands in front of the inner loop, not in every step's tail
         const int s1 = min(s0 + ROLL_R, k_steps);
+        // The block's steps, once per policy: the launch-uniform flag is a template argument of the body, so the uniform
+        // policy's steps hold nothing of the non-reversing draw (its selects were per-step VALU instructions) and the
+        // choice is one uniform branch per block.
+        auto block_steps = [&](auto nr) __attribute__((always_inline)) {
+        constexpr bool NONREV = decltype(nr)::value;
 #pragma nounroll
         for (int s = s0; s < s1; ++s) {                             // the block's steps: ab.x's low byte is this step's
             Params P;                                                   // REC alone: N and the reward table, re-read per step (see k_obs_roll)
@@ -1542,7 +1563,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
             float rw0 = 0.0f, rw1 = 0.0f;
             if (stepped) {
                 const uint32_t abyte = ab.x & 0xFFu;
-                const int a[2] = {draw_action_byte(abyte, 0, last[0], nonrev), draw_action_byte(abyte, 1, last[1], nonrev)};
+                const int a[2] = {draw_action_byte(abyte, 0, last[0], NONREV), draw_action_byte(abyte, 1, last[1], NONREV)};
                 int ncell[2];                                            // the new heads: the old ones' cells +-1 or +-S
                 unsigned long long nbit[2];
                 uint32_t nk[2], ndw[2], nsh[2];
@@ -1602,14 +1623,13 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
                     lds_set_nibble(hdw[1], hsh[1], NIB_P2_BODY);
                     lds_set_nibble(ndw[0], nsh[0], NIB_P1_HEAD);
                     lds_set_nibble(ndw[1], nsh[1], NIB_P2_HEAD);
-                    const unsigned long long sm = hbit[0] | hbit[1] | nbit[0] | nbit[1];
-                    mask |= sm;
-                    dirty |= sm;
+                    const unsigned long long nb = nbit[0] | nbit[1];         // (the old heads' chunks are in both already)
+                    mask |= nb;
+                    dirty |= nb;
                 }
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
                     cell[p] = ncell[p];
-                    hbit[p] = nbit[p];
                     hdw[p] = ndw[p];
                     hsh[p] = nsh[p];
                 }
@@ -1620,55 +1640,44 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
 
             // ---- a restart (ACKTR.py:307-310), one divergent region: the state words, the board, the next game's starts.
             // The board: the two head chunks only, straight-line (everything else the old game drew goes stale).  One LDS
-            // round trip reads the template's two dwords of each head chunk; the heads go in in registers — a head cell is
-            // EMPTY in the template: XOR turns that nibble into the head's (game.py:90-91); the two heads are different
-            // cells, possibly of one chunk or one dword, and then both chunks' words take both XORs and the two writes store
-            // the same bytes — and the two chunks are written.  A head on the short last chunk is no special case: the
-            // chunk's padding nibbles are 0 in the template and stay 0.  A lane writes only its own board: no fence, no wave
-            // barrier.  The next game: rs4.episode moves on and rs4.nstart is drawn, one Philox block (make_game_starts);
+            // round trip reads the template's two dwords of each head chunk; the write order is: chunk 1's two dwords,
+            // chunk 2's two dwords, head 1's nibble, head 2's nibble (game.py:90-91).  The two heads are different cells,
+            // possibly of one chunk or one dword: the chunk is then written twice with the same template bytes before
+            // either nibble is set, and each lds_set_nibble touches its own four bits.  A head on the short last chunk is
+            // no special case: the chunk's padding nibbles are 0 in the template and stay 0.  A lane writes only its own
+            // board: no fence, no wave barrier.  The next game: rs4.episode moves on and the start cells of the game after
+            // it are read from the helper's ring (rs.z: start_cells_word, no r and no c here);
             // rs4.envp and rs4.nenvp stay as the prologue read them until the epilogue (no step of mode None reads them).
-            // The carried state becomes restarted_st4's: the heads at rs4.nstart, both alive, no last action, eplen 0.
+            // The carried state becomes restarted_st4's: the heads at the start cells, both alive, no last action, eplen 0.
             if (mine && done && autoreset) {
-                int r[2], c[2];
-                unpack_pos(rs.z, r, c);
                 alive = META_ALIVE0 | META_ALIVE1;
                 done = false;
                 winner = 0;
                 last[0] = last[1] = 0u;
                 eplen = 0u;
                 st_dirty = true;
-                cell[0] = roll_cell(S, r[0], c[0]);                      // start_cells' values
-                cell[1] = roll_cell(S, r[1], c[1]);
-                const uint32_t h1 = (uint32_t)cell[0], h2 = (uint32_t)cell[1];
+                cell[0] = (int)(rs.z & 0xFFFFu);                     // the ring's word: start_cells' values
+                cell[1] = (int)(rs.z >> 16);
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
                     hdw[p] = lds_cell_dword(board_lds, (uint32_t)cell[p]);
                     hsh[p] = lds_cell_shift((uint32_t)cell[p]);
                 }
-                const uint32_t k1 = h1 >> 4, k2 = h2 >> 4;
-                hbit[0] = 1ull << k1;
-                hbit[1] = 1ull << k2;
-                const unsigned long long heads = hbit[0] | hbit[1];
+                const uint32_t k1 = (uint32_t)cell[0] >> 4, k2 = (uint32_t)cell[1] >> 4;
+                const unsigned long long heads = (1ull << k1) | (1ull << k2);
                 dirty |= mask | heads;
-                stale = (stale | mask) & ~heads;                         // the old trail is not wiped: its chunks go stale
+                stale = (stale | mask) & ~heads;                     // the old trail is not wiped: its chunks go stale
                 mask = heads;
-                uint32_t ta[2] = {tmpl[2u * k1], tmpl[2u * k1 + 1u]}, tb[2] = {tmpl[2u * k2], tmpl[2u * k2 + 1u]};
-                const uint32_t hx1 = (NIB_EMPTY ^ NIB_P1_HEAD) << hsh[0], hx2 = (NIB_EMPTY ^ NIB_P2_HEAD) << hsh[1];
-                const uint32_t d1 = (h1 >> 3) & 1u, d2 = (h2 >> 3) & 1u;
-                const bool same = k1 == k2;
-#pragma unroll
-                for (uint32_t d = 0; d < 2u; ++d) {
-                    const uint32_t y1 = d1 == d ? hx1 : 0u, y2 = d2 == d ? hx2 : 0u;
-                    ta[d] ^= y1 ^ (same ? y2 : 0u);
-                    tb[d] ^= y2 ^ (same ? y1 : 0u);
-                }
-                board[2u * k1] = ta[0];
+                const uint32_t ta[2] = {tmpl[2u * k1], tmpl[2u * k1 + 1u]}, tb[2] = {tmpl[2u * k2], tmpl[2u * k2 + 1u]};
+                board[2u * k1] = ta[0];                              // both chunks as the template has them, and only then ...
                 board[2u * k1 + 1u] = ta[1];
                 board[2u * k2] = tb[0];
                 board[2u * k2 + 1u] = tb[1];
+                lds_set_nibble(hdw[0], hsh[0], NIB_P1_HEAD);         // ... the two heads, on top of whichever write came last
+                lds_set_nibble(hdw[1], hsh[1], NIB_P2_HEAD);
                 rs.y += 1u;
                 nres += 1u;
-                rs.z = sring[(rs.y & (2u * ROLL_R - 1u)) * WAVE + lane];  // make_game_starts(env, rs.y), drawn by the helper, in the episode's slot
+                rs.z = sring[(rs.y & (2u * ROLL_R - 1u)) * WAVE + lane];  // the start cells of game rs.y, drawn by the helper, in the episode's slot
             }
             ROLL_STAMP(2);
 
@@ -1688,6 +1697,9 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
             ab.y >>= 8;
             ROLL_STAMP(3);
         }
+        };
+        if (nonrev) block_steps(std::true_type{});
+        else block_steps(std::false_type{});
     }
 
     ROLL_STAMP_LAUNCH(1);
@@ -1771,14 +1783,10 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
         ROLL_STAMP_LAUNCH(2);
         // st4 is packed here alone, from the carried state: the bytes stepped_st4 or restarted_st4 of the env's last event
         // would have left (last[] is the stored action + 1, and 0 behind a restart; a dead player's head may be off the board)
-        // r and c come back from the cells, one division by S per env and launch: cell = (r + 1) S + (c + 1) with both terms
-        // in [0, S), so the quotient and the remainder are r + 1 and c + 1 — a dead player's head on the border ring gives
-        // the -1 or W that carrying r and c through the moves gave
+        // r and c come back from the cells (cells_pos: one division by S per env and launch) — a dead player's head on the
+        // border ring gives the -1 or W that carrying r and c through the moves gave
         if (mine && st_dirty) {
-            const uint32_t q0 = (uint32_t)cell[0] / (uint32_t)S, q1 = (uint32_t)cell[1] / (uint32_t)S;
-            const int r[2] = {(int)q0 - 1, (int)q1 - 1};
-            const int c[2] = {cell[0] - (int)q0 * S - 1, cell[1] - (int)q1 * S - 1};
-            P.st4[env] = make_uint4(pack_pos(r[0], c[0], r[1], c[1]), pack_meta(alive, done, winner, (int)last[0] - 1, (int)last[1] - 1), eplen, tick);
+            P.st4[env] = make_uint4(cells_pos(S, cell[0], cell[1]), pack_meta(alive, done, winner, (int)last[0] - 1, (int)last[1] - 1), eplen, tick);
         }
         // The next launch's entry mask (the masked entry above): what differs from the template now lies inside mask, and the
         // stores above left memory outside it the template.  Every env of the launch, a lane that did not step (the mask it
@@ -1797,6 +1805,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
                 else rs.w = pack_envp(ng.w0, ng.w1, ng.degree);
             }
             rs.x = envp;
+            rs.z = cells_pos(S, (int)(rs.z & 0xFFFFu), (int)(rs.z >> 16));   // the ring's word back to pack_pos (a lane that never restarted stores nothing)
             P.rs4[env] = rs;
         }
     }
