@@ -34,19 +34,7 @@ using namespace tron;
 constexpr int TT_BLOCK = 256;
 constexpr int TT_WAVES = TT_BLOCK / 64;
 
-// Bits [start, start + S) of a bit plane (bit i of the board = bit i & 31 of word i >> 5), S <= 34: three words cover them
-// wherever they start; the plane has two words of slack behind its last cell.
-template <typename M>
-__device__ __forceinline__ M row_bits(const uint32_t *plane, int start, int S)
-{
-    const int k = start >> 5, off = start & 31;
-    uint64_t v = (((uint64_t)plane[k + 1] << 32) | plane[k]) >> off;
-    if (off) v |= (uint64_t)plane[k + 2] << (64 - off);
-    return (M)(v & ((1ull << S) - 1ull));
-}
-
 // LDS of one board: the owner tile (S * S bytes in whole 16-byte chunks), then the three bit planes of `plane_words` words.
-__host__ __device__ inline int plane_words(int G) { return ((G + 31) >> 5) + 2; }
 __host__ __device__ inline int board_lds(int G) { return ((((G + 15) >> 4) << 4) + 12 * plane_words(G) + 15) & ~15; }
 
 // GROUP lanes per board (one lane per row), 64 / GROUP boards per wave, TT_WAVES waves per block.
@@ -59,45 +47,17 @@ __global__ __launch_bounds__(TT_BLOCK) void k_territory(const int8_t *__restrict
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int grp = lane / GROUP, row = lane % GROUP, slot = wave * BPW + grp;
     const int64_t board = (int64_t)blockIdx.x * (TT_WAVES * BPW) + slot;
-    const int G = S * S, CHUNKS = (G + 15) >> 4, PW = plane_words(G);
+    const int G = S * S, CHUNKS = (G + 15) >> 4;
     int8_t *tile = reinterpret_cast<int8_t *>(tt_lds) + (size_t)slot * (size_t)board_lds(G);
     uint32_t *planes = reinterpret_cast<uint32_t *>(tile + CHUNKS * 16);      // [3][PW]: open, +10, -10
-    uint16_t *halves = reinterpret_cast<uint16_t *>(planes);
     const bool have = board < n;
     const int64_t total = n * (int64_t)G, base = board * (int64_t)G;
 
-    // ---- the board in: chunk w of the board is 16 bits of each plane
-    if (have) {
-        for (int w = row; w < CHUNKS; w += GROUP) {
-            uint32_t x[4];
-            load16(codes, total, base + 16 * w, x);
-            uint32_t open = 0u, h1 = 0u, h2 = 0u;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int v = (int)(int8_t)(x[i >> 2] >> (8 * (i & 3)));      // bytes behind the board's end belong to no row
-                open |= (uint32_t)(v == 1) << i;
-                h1 |= (uint32_t)(v == 10) << i;
-                h2 |= (uint32_t)(v == -10) << i;
-            }
-            halves[w] = (uint16_t)open;
-            halves[2 * PW + w] = (uint16_t)h1;
-            halves[4 * PW + w] = (uint16_t)h2;
-        }
-    }
+    // ---- the board in, then my row as masks
+    if (have) planes_in<GROUP>(codes, total, base, row, G, planes);
     __syncthreads();
-
-    // ---- my row as masks.  `inner` is the row's cells strictly inside the border: nothing outside it is ever open
-    const M inner = (row >= 1 && row <= S - 2) ? (M)((((M)1 << (S - 2)) - (M)1) << 1) : (M)0;
-    M E = 0, H1 = 0, H2 = 0;
-    if (have && row < S) {
-        E = row_bits<M>(planes, row * S, S) & inner;
-        H1 = row_bits<M>(planes + PW, row * S, S);
-        H2 = row_bits<M>(planes + 2 * PW, row * S, S);
-    }
-    // playable: exactly one +10 and one -10 on the whole image, both strictly inside the border
-    const int all = group_sum<GROUP>(popc<M>(H1) | (popc<M>(H2) << 16));
-    const int in = group_sum<GROUP>(popc<M>(H1 & inner) | (popc<M>(H2 & inner) << 16));
-    const bool playable = have && all == 0x00010001 && in == 0x00010001;
+    M inner, E, H1, H2;
+    const bool playable = row_masks<M, GROUP>(planes, row, S, have && row < S, inner, E, H1, H2) && have;
 
     // ---- both floods, level by level; a rejected or absent board has no frontier and takes no part
     M f1 = playable ? (M)(H1 & inner) : (M)0, f2 = playable ? (M)(H2 & inner) : (M)0;

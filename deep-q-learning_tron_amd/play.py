@@ -32,8 +32,8 @@ def rating(model, model2=None, n_games=10000, slides=None, width=10, gamemode="i
     opponent with rates=True — its playouts follow the env's own rule under every game's own slide rates — in any
     gamemode, the default ice sweep included.  mc_weights: the weights= of either Monte-Carlo seat's playouts (four ints
     0..255, tron.vec.HUG_WEIGHTS: drawn moves weighed by their room); None is the uniform draw.  mc_steps: the k_steps of
-    those playouts (None: width * width); mc_judge="territory" judges the playouts that mc_steps cuts off by territory
-    (VecTron.montecarlo_actions' judge=)."""
+    those playouts (None: width * width); mc_judge="territory" judges the playouts that mc_steps cuts off by territory,
+    mc_judge="fill" by the checkerboard fill bound (VecTron.montecarlo_actions' judge=)."""
     model2 = model2 or model
     if model2 == "montecarlo" and gamemode not in (None, "none"):
         raise ValueError('model2="montecarlo" plays mode None\'s rule: gamemode must be None or "none"')

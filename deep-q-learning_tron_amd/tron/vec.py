@@ -275,7 +275,8 @@ class VecTron:
         [K, N * copies, 2], replaces the drawn slide uniforms).  weights: four ints 0..255 (HUG_WEIGHTS) weigh the drawn
         moves by their room as playout_codes does; None is the uniform draw.  Returns (steps, winner, final_codes | None)
         as playout_codes does; a finished env's row is what playout_codes makes of its image.  judge="territory": an
-        unfinished playout's winner is territory_winner's verdict on its last position, as in playout_codes."""
+        unfinished playout's winner is territory_winner's verdict on its last position, as in playout_codes;
+        judge="fill": fill_winner's."""
         rates = self._playout_rates(rates, "playout")
         if int(copies) < 1:
             raise ValueError("copies is at least 1")
@@ -290,6 +291,12 @@ class VecTron:
         owner int8 [N, S, S] | None).  The env itself is left exactly as it was; a finished env's row is what
         territory_codes makes of its image."""
         return territory_codes(self._p1_codes(), want_owner=want_owner)
+
+    def reach(self, want_dist=False):
+        """reach_codes on every env's current board (the player-1 codes playout takes): (counts int32 [N, 8],
+        dist int16 [N, 2, S, S] | None).  The env itself is left exactly as it was; a finished env's row is what
+        reach_codes makes of its image."""
+        return reach_codes(self._p1_codes(), want_dist=want_dist)
 
     def slide_rates(self):
         """float64 [N, 2] on the device: the rate each player's `random.random() <= rate` meets in this env's mode
@@ -345,7 +352,8 @@ class VecTron:
         tallies of playout_values(k_steps, copies, call, rates=rates, weights=weights) — 16 * copies random playouts of at
         most k_steps (default W * W) steps per env.  Pass the step number as `call` so that every step draws its own
         playouts, rates=True in a sliding mode, and weights (HUG_WEIGHTS) for playouts that prefer room.  judge="territory"
-        with a short k_steps judges the playouts that k_steps cuts off by territory instead of leaving them out."""
+        with a short k_steps judges the playouts that k_steps cuts off by territory instead of leaving them out,
+        judge="fill" by the checkerboard bound on the territory each player can fill (fill_winner)."""
         if int(player) not in (1, 2):
             raise ValueError("player is 1 or 2")
         k_steps = self.W * self.W if k_steps is None else k_steps
@@ -506,8 +514,9 @@ def playout_codes(codes, actions=None, k_steps=None, seed=0x5EED, stream_id=0, c
     for bit; HUG_WEIGHTS is a preset that prefers tight cells.  None calls the entries without weights.
     judge: None, or "territory": a playout that comes back unfinished (winner -1) has its last position judged by
     territory_winner(territory_codes(final)), and the returned winner carries that verdict (1, 2, or 0 for equal
-    territory) in the place of -1; steps and codes are as without it.  The last positions are computed whether or not
-    want_codes asks for them."""
+    territory) in the place of -1; steps and codes are as without it.  "fill" does the same with
+    fill_winner(reach_codes(final)), the verdict of the checkerboard bound.  The last positions are computed whether or
+    not want_codes asks for them."""
     _checked_judge(judge, "playout_codes")
     c, n, side = _boards(codes, "playout_codes")
     packed = None if weights is None else _packed_weights(weights, "playout_codes")
@@ -543,13 +552,18 @@ def playout_codes(codes, actions=None, k_steps=None, seed=0x5EED, stream_id=0, c
         _playout_entry("codes", (cp, n, side, int(k_steps), ap), (rates, uniforms), packed, _key(seed, stream_id, call),
                        (steps, winner, final))
     if judge is not None:
-        winner = torch.where(winner == -1, territory_winner(territory_codes(final)[0]), winner)
+        winner = torch.where(winner == -1, _VERDICTS[judge](final), winner)
     return steps, winner, (final if want_codes else None)
 
 
+# judge= of the playout calls: the verdict int8 [n] on a stack of last positions
+_VERDICTS = {"territory": lambda final: territory_winner(territory_codes(final)[0]),
+             "fill": lambda final: fill_winner(reach_codes(final)[0])}
+
+
 def _checked_judge(judge, what):
-    if judge not in (None, "territory"):
-        raise ValueError(f'{what}: judge is None or "territory", got {judge!r}')
+    if not (judge is None or (isinstance(judge, str) and judge in _VERDICTS)):
+        raise ValueError(f'{what}: judge is None or "territory", got {judge!r}')      # or "fill": the older text is kept
 
 
 def territory_codes(codes, want_owner=False):
@@ -578,6 +592,32 @@ def territory_winner(counts):
     return torch.where(first1 < 0, torch.full_like(verdict, -2), verdict)
 
 
+def reach_codes(codes, want_dist=False):
+    """How far each player is from every cell of a stack of observation-code boards int8 [n, S, S] (tron_reach_codes; the
+    boards, open cells and distances d1, d2 of territory_codes).  Returns (counts int32 [n, 8], dist int16 [n, 2, S, S] or
+    None).  dist[i, p] holds d_(p+1) where finite, 0 on that head's own cell, -1 elsewhere.  counts = (opp1, same1, opp2,
+    same2, fill1, fill2, depth1, depth2): territory_codes' first1 / first2 cells split by checkerboard colour (r + c) & 1
+    into those of the head's own colour (same) and the others (opp); fill_p = 2 * same_p + 1 if opp_p > same_p else
+    2 * opp_p, the longest colour-alternating walk from beside the head those cells allow, an upper bound on the moves
+    player p can make in the cells it reaches first; depth_p the largest finite d_p.  A rejected board (not exactly one
+    +10 and one -10 inside the border) gets eight -1 and planes of -1."""
+    c, n, side = _boards(codes, "reach_codes")
+    cp = nat.ptr(c)                                                    # a host tensor is refused here
+    counts = torch.empty(n, 8, dtype=torch.int32, device=c.device)
+    dist = torch.empty(n, 2, side, side, dtype=torch.int16, device=c.device) if want_dist else None
+    with torch.cuda.device(c.device):
+        nat.check(nat.lib().tron_reach_codes(cp, n, side, nat.ptr(counts), nat.ptr(dist), nat.stream_ptr()), "tron_reach_codes")
+    return counts, dist
+
+
+def fill_winner(counts):
+    """The verdict of reach_codes' counts [n, 8] as playout_codes reports winners, int8 [n]: -2 for a rejected row, else
+    1 / 2 for the player whose fill bound is greater, 0 for equal bounds."""
+    fill1, fill2 = counts[:, 4], counts[:, 5]
+    verdict = (fill1 < fill2).to(torch.int8) * 2 + (fill1 > fill2).to(torch.int8)
+    return torch.where(fill1 < 0, torch.full_like(verdict, -2), verdict)
+
+
 def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, want_actions=True, rates=None, weights=None,
                    judge=None):
     """Monte-Carlo move values of a stack of observation-code boards int8 [n, S, S] (tron_playout_values): every board is
@@ -592,10 +632,10 @@ def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, w
     all its playouts, which are playout_codes(rates=...)'s at the same index, with drawn uniforms.
     weights: four ints 0..255 as in playout_codes (tron_playout_weighted_values): every move behind the first is
     playout_codes(weights=...)'s at the same index, under either rule.
-    judge: None, or "territory": the playouts that k_steps cuts off are judged by territory (playout_codes(judge=...)) and
+    judge: None, "territory" or "fill": the playouts that k_steps cuts off are judged (playout_codes(judge=...)) and
     tallied under that verdict, so counts[..., 3] is 0.  This is the composition the definition above names, actually
     made: the boards copied 16 * copies times, the tape, playout_codes at the same key (playout q has the Philox index q
-    it has without judge, so where no playout is left unfinished the counts are the same), territory_codes on the last
+    it has without judge, so where no playout is left unfinished the counts are the same), the judge's call on the last
     positions, the tallies summed on the device and tron_values_pick.  Memory: two code planes (the copy and the last
     position, 2 * S * S bytes) and 2 * k_steps tape bytes per playout, n * 16 * copies playouts."""
     _checked_judge(judge, "playout_values")

@@ -569,6 +569,31 @@ int tron_territory_codes(const int8_t *codes, int64_t n, int32_t side,
                          int8_t  *out_owner,    /* i8[n][side][side] or NULL */
                          void *stream);
 
+/* ---- reach: how far each player is from every cell (csrc/tron_reach.hip) -----------------------------------------------
+ * The same two floods on the same boards as tron_territory_codes — codes, playable / REJECTED, open cell and d_p are its
+ * definitions word for word — keeping the distances, and a bound on the territory a player can FILL, not only reach.
+ * out_dist   i16[n][2][side][side] or NULL, at any even address, not `codes` itself: plane p - 1 of board i holds d_p
+ *            where it is finite, 0 on head p's own cell, and -1 everywhere else: closed cells, the other head's cell,
+ *            the border ring, open cells flood p does not reach.  (d_p goes up to 525 at side 34: int16, not int8.)
+ * out_counts i32[n][8] or NULL.  With colour(r, c) = (r + c) & 1 and first_p = the open cells with d_p finite and d_p < d_q
+ *            or d_q infinite (q the other player; tron_territory_codes' first1 / first2):
+ *              [0] opp1:  first1 cells of the colour head 1 does NOT stand on     [2] opp2   [3] same2: likewise
+ *              [1] same1: first1 cells of head 1's colour
+ *              [4] fill1 = opp1 > same1 ? 2 * same1 + 1 : 2 * opp1                [5] fill2: likewise
+ *              [6] depth1: the largest finite d_1 over open cells, 0 if flood 1 reaches none   [7] depth2
+ *            A walk on the 4-neighbourhood alternates colours and its first cell, beside the head, has the other colour,
+ *            so fill_p is the length of the longest colour-alternating walk first_p has the cells for: an upper bound on
+ *            the moves player p can make inside first_p (the checkerboard bound).  [0] + [1] and [2] + [3] are
+ *            tron_territory_codes' [0] and [1].
+ * A REJECTED board gets eight counts of -1 and both planes all -1.
+ * TRON_ERR_BAD_ARG: codes == NULL with n > 0, n < 0, n >= 2^31, out_dist at an odd address, out_dist == codes;
+ * TRON_ERR_UNSUPPORTED: side outside 6..34.  n == 0, or both outputs NULL, launches nothing and returns TRON_OK.  Nothing
+ * outside [0, n) of an output is written, and codes is only read.                                                        */
+int tron_reach_codes(const int8_t *codes, int64_t n, int32_t side,
+                     int32_t *out_counts,   /* i32[n][8] or NULL */
+                     int16_t *out_dist,     /* i16[n][2][side][side] or NULL */
+                     void *stream);
+
 /* ---- K-FAC helper of the ACKTR path (Net/kfac.py:28-38 `_extract_patches`; its TODO at kfac.py:9-12
  * asks for this kernel) -------------------------------------------------------------------------- */
 /* x f32[batch][channels][height][width] -> out f32[batch*OH*OW][channels*kh*kw], row = (sample, oy, ox),
