@@ -33,7 +33,9 @@ def rating(model, model2=None, n_games=10000, slides=None, width=10, gamemode="i
     gamemode, the default ice sweep included.  mc_weights: the weights= of either Monte-Carlo seat's playouts (four ints
     0..255, tron.vec.HUG_WEIGHTS: drawn moves weighed by their room); None is the uniform draw.  mc_steps: the k_steps of
     those playouts (None: width * width); mc_judge="territory" judges the playouts that mc_steps cuts off by territory,
-    mc_judge="fill" by the checkerboard fill bound (VecTron.montecarlo_actions' judge=)."""
+    mc_judge="fill" by the checkerboard fill bound (VecTron.montecarlo_actions' judge=).  model2="lookahead" seats the
+    one-ply lookahead (VecTron.lookahead_actions: the safe move behind which player 2 reaches most cells first) in any
+    gamemode; its pick looks at no slide."""
     model2 = model2 or model
     if model2 == "montecarlo" and gamemode not in (None, "none"):
         raise ValueError('model2="montecarlo" plays mode None\'s rule: gamemode must be None or "none"')
@@ -57,6 +59,8 @@ def rating(model, model2=None, n_games=10000, slides=None, width=10, gamemode="i
             a2 = env.montecarlo_actions(2, k_steps=mc_steps, call=t, weights=mc_weights, judge=mc_judge)
         elif model2 == "montecarlo-slide":
             a2 = env.montecarlo_actions(2, k_steps=mc_steps, call=t, rates=True, weights=mc_weights, judge=mc_judge)
+        elif model2 == "lookahead":
+            a2 = env.lookahead_actions(2)
         else:
             a2 = env.minimax_actions(2) if isinstance(model2, str) else model_actions(model2, planes[:, 1], prob_plane, env2)
         obs, _, done, _ = env.step(torch.stack([a1, a2], 1), autoreset=False)

@@ -298,6 +298,24 @@ class VecTron:
         reach_codes makes of its image."""
         return reach_codes(self._p1_codes(), want_dist=want_dist)
 
+    def moves(self, want_actions=True):
+        """moves_codes on every env's current board (the player-1 codes playout takes): (moves int32 [N, 2, 4, 3],
+        actions int8 [N, 2] | None).  The env itself is left exactly as it was; a finished env's row is what moves_codes
+        makes of its image."""
+        return moves_codes(self._p1_codes(), want_actions=want_actions)
+
+    def lookahead_actions(self, player, out=None):
+        """The one-ply lookahead opponent, minimax_actions' and montecarlo_actions' counterpart: int8 [N], `player`'s
+        (1|2) pick of moves_codes — the safe move behind which it reaches most cells first, the greater fill bound among
+        equals.  One launch, no draws; no slide is looked at in any mode."""
+        if int(player) not in (1, 2):
+            raise ValueError("player is 1 or 2")
+        actions = self.moves()[1][:, int(player) - 1]
+        if out is None:
+            return actions.contiguous()
+        out.copy_(actions)
+        return out
+
     def slide_rates(self):
         """float64 [N, 2] on the device: the rate each player's `random.random() <= rate` meets in this env's mode
         (game.py:169) — ice: the env's slide for both players; temper: get_rate(degree, weight[p]) in game.py:100-102's
@@ -616,6 +634,29 @@ def fill_winner(counts):
     fill1, fill2 = counts[:, 4], counts[:, 5]
     verdict = (fill1 < fill2).to(torch.int8) * 2 + (fill1 > fill2).to(torch.int8)
     return torch.where(fill1 < 0, torch.full_like(verdict, -2), verdict)
+
+
+def moves_codes(codes, want_actions=True):
+    """What each move of a stack of observation-code boards int8 [n, S, S] leads into (tron_moves_codes; the boards, open
+    cells and distances of territory_codes).  Returns (moves int32 [n, 2, 4, 3], actions int8 [n, 2] or None).
+    moves[i, p, a] = (room, fill, first) of player p's (0: the +10 head) move in direction a = UP, RIGHT, DOWN, LEFT, three
+    -1 where the target is no open cell: room the open cells the flood from the target reaches, the target among them;
+    fill the checkerboard bound on the moves the player can still make, this one included (reach_codes' bound started on
+    the target); first the reached cells the player stands on before the opponent can, the step counted (1 + e < d_q).
+    actions[i, p] = the first direction of the greatest (first, fill), 0 when no move is safe.  A rejected board (not
+    exactly one +10 and one -10 inside the border) gets 24 times -1 and actions of -1."""
+    c, n, side = _boards(codes, "moves_codes")
+    cp = nat.ptr(c)                                                    # a host tensor is refused here
+    moves = torch.empty(n, 2, 4, 3, dtype=torch.int32, device=c.device)
+    actions = torch.empty(n, 2, dtype=torch.int8, device=c.device) if want_actions else None
+    with torch.cuda.device(c.device):
+        nat.check(nat.lib().tron_moves_codes(cp, n, side, nat.ptr(moves), nat.ptr(actions), nat.stream_ptr()), "tron_moves_codes")
+    return moves, actions
+
+
+def safe_moves(moves):
+    """moves_codes' moves [n, 2, 4, 3] as safe-move masks, bool [n, 2, 4]: room >= 0."""
+    return moves[..., 0] >= 0
 
 
 def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, want_actions=True, rates=None, weights=None,

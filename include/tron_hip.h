@@ -594,6 +594,38 @@ int tron_reach_codes(const int8_t *codes, int64_t n, int32_t side,
                      int16_t *out_dist,     /* i16[n][2][side][side] or NULL */
                      void *stream);
 
+/* ---- moves: what each of the up to eight safe moves of a board leads into (csrc/tron_moves.hip) -------------------------
+ * Boards, playable / REJECTED, open cell and d_p are tron_territory_codes' definitions.  Directions are UP, RIGHT, DOWN,
+ * LEFT = 0..3 with the row / column deltas of tron_playout.hip's action_delta.
+ * For board i, player p (0 = the +10 head, 1 = the -10 head), q the other player, direction a:
+ * target     t = head p's cell moved by a.
+ * safe       the move is safe when t is an open cell.  The opponent's simultaneous move is not looked at, as in playout's
+ *            safe move.
+ * e(c)       the breadth-first distance from t over open cells, 4-neighbourhood.  e(t) = 0.  Infinite where the flood does
+ *            not reach.  Head p's own cell is closed, as always.
+ * room       the number of open cells with e finite.  t counts, so a safe move has room >= 1.
+ * fill       with colour (r + c) & 1, same = reached cells of t's colour (t among them), opp = the others.
+ *            fill = same > opp ? 2 * opp + 1 : 2 * same.  This is the longest colour-alternating walk that starts on t,
+ *            counted in cells.  It is an upper bound on the moves player p can still make, this one included, if it takes
+ *            a.  It is tron_reach_codes' bound started one cell later.
+ * first      the number of open cells c with e(c) finite and (d_q(c) infinite or 1 + e(c) < d_q(c)).  d_q is the
+ *            opponent's flood from its head on the board as it stands.  When the opponent also stands beside t
+ *            (d_q(t) = 1), t itself is not counted.  When d_q(t) >= 2, letting q's flood pass through t changes nothing:
+ *            a path of q through t reaches c at d_q(t) + e(c) >= 2 + e(c), later than p's 1 + e(c), so whether t is open or
+ *            closed to q decides no cell.
+ * out_moves  i32[n][2][4][3] or NULL: [i][p][a] = (room, fill, first).  Three -1 for a move that is not safe.  All 24
+ *            values -1 for a REJECTED board.
+ * out_actions i8[n][2] or NULL: [i][p] = the first safe direction, in the order UP, RIGHT, DOWN, LEFT, of the greatest key
+ *            (first, fill) compared lexicographically.  0 (UP) when no move is safe, as playout's draw.  -1 for both
+ *            players of a REJECTED board.  Integer comparisons only.
+ * TRON_ERR_BAD_ARG: codes == NULL with n > 0, n < 0, n >= 2^31; TRON_ERR_UNSUPPORTED: side outside 6..34.  Bad arguments
+ * are reported before an unsupported side.  n == 0, or both outputs NULL, launches nothing and returns TRON_OK.  Nothing
+ * outside [0, n) of an output is written.  codes is only read and may sit at any alignment.                            */
+int tron_moves_codes(const int8_t *codes, int64_t n, int32_t side,
+                     int32_t *out_moves,    /* i32[n][2][4][3] or NULL */
+                     int8_t  *out_actions,  /* i8[n][2]        or NULL */
+                     void *stream);
+
 /* ---- K-FAC helper of the ACKTR path (Net/kfac.py:28-38 `_extract_patches`; its TODO at kfac.py:9-12
  * asks for this kernel) -------------------------------------------------------------------------- */
 /* x f32[batch][channels][height][width] -> out f32[batch*OH*OW][channels*kh*kw], row = (sample, oy, ox),
