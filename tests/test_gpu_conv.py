@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, load_golden
+from head_support import head_ref as _head_ref                           # the float64 tail of DQNNet.py:52-63
 
 pytestmark = pytest.mark.gpu
 
@@ -217,15 +218,6 @@ def test_dqn_head_26_matches_float64_reference(fused):
         ref = _head_ref(net, x)
         assert (q.double() - ref).abs().max().item() < TOL, (B, (q.double() - ref).abs().max().item())
         assert torch.equal(g.long(), q.argmax(1))
-
-
-def _head_ref(net, x):
-    d = lambda t: t.double()
-    y = F.avg_pool2d(x.double(), 3, stride=2, padding=1)
-    y = F.mish(F.conv2d(y, d(net.conv7.weight), d(net.conv7.bias), stride=2, padding=3)).reshape(x.shape[0], -1)
-    y = F.mish(F.linear(y, d(net.fc1.weight), d(net.fc1.bias)))
-    y = F.mish(F.linear(y, d(net.fc2.weight), d(net.fc2.bias)))
-    return F.linear(F.mish(F.linear(y, d(net.actor1.weight), d(net.actor1.bias))), d(net.actor2.weight), d(net.actor2.bias))
 
 
 @pytest.mark.parametrize("B", [1, 5, 127, 128, 129, 1000, 4099])

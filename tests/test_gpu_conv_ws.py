@@ -181,8 +181,9 @@ def test_infer_from_codes_takes_the_ws_chain(fused, W, monkeypatch):
 @pytest.mark.parametrize("B", [1, 2, 255, 256, 257, 777, 4096, 8192 + 3])
 def test_conv6_with_the_pooling_in_one_launch_has_the_bits_of_two(fused, B, monkeypatch):
     """tron_conv3x3_ws_fwd_pool12 (conv6's output stays in LDS, DQNNet.py:48-52) against tron_conv3x3_ws_fwd followed by the head's own
-    pooling: the pooled rows, Q and the greedy action bit for bit; and against float64 through Net.infer.  Batches below, at and
-    above one image per workgroup (256 CUs), and several images per workgroup with a ragged last round."""
+    pooling: the pooled rows, Q and the greedy action bit for bit.  (The pooled entry against float64:
+    test_gpu_head_dispatch.py::test_head_on_every_gemm_path_matches_float64.)  Batches below, at and above one image per workgroup
+    (256 CUs), and several images per workgroup with a ragged last round."""
     from Net.DQNNet import Net
     from tron import _native as nat
     torch.manual_seed(B)
