@@ -114,6 +114,9 @@ def test_gradient_factor_workspace_holds_the_nchw_partials(B, C, S):
     assert (gram.double() - want).abs().max().item() / want.abs().max().item() < 2e-6
 
 
+# The rows (40, 32, 12, 12), (3, 32, 26, 26) and (6, 64, 34, 34) run on the PX16 kernel today (csrc/tron_kfac_px.hip takes 3x3 /
+# pad 1 / stride 1 at 32 or 64 channels and sides 12, 26, 34); the others reach the patch-matrix kernels, whose exact tests
+# are in tests/test_gpu_kfac_gram.py.
 GRAM_SHAPES = [  # B, C, H, W, k, pad, stride
     (5, 3, 12, 12, 3, 1, 1),      # conv1 at 10x10 (d = 27: one ragged tile)
     (9, 4, 34, 34, 3, 1, 1),      # conv1 of MapNet at 32x32
@@ -161,8 +164,10 @@ def test_linear_gram_matches_float64(rows, d):
 
 
 def test_gram_over_several_passes_and_bad_arguments():
-    """A patch matrix larger than one 512 MB pass (here 64-channel 34x34 inputs: 1.3 GB split) goes through the kernel in
-    passes whose partial sums add up: the factor of a batch == the sum of the factors of its halves, each a single pass."""
+    """The factor of a batch == the sum of the factors of its two parts (200 and 300 images).  Written for a patch matrix larger
+    than one 512 MB pass (64-channel 34x34 inputs: 1.3 GB split), but tron_kfac_px_supported accepts this shape, so today the
+    PX16 kernel takes all three calls and no patch matrix is built; nor would the second part (300 images) have been a single
+    pass.  The loop over passes is tested in tests/test_gpu_kfac_gram.py::test_second_pass_adds_to_the_first, exactly."""
     import torch.nn as nn
     from Net import kfac
     from tron import _native as nat
