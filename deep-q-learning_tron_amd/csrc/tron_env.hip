@@ -1021,18 +1021,24 @@ __device__ __forceinline__ uint32_t swap_nibbles8(uint32_t p)
 // The prologue builds mask by comparing what it reads with the template, whoever wrote it (every writer of the API leaves the
 // player-2 plane the swap_codes4 image of the player-1 plane, and the caller never writes the buffer); stale starts at 0.
 // Nothing is compared in the loop.
-// A restart wipes nothing: stale |= mask & ~heads, dirty |= mask | heads, mask = heads (the chunks of the two new heads), and
-// only the head chunks are written, straight-line — the template's two dwords of each, THEN the two head nibbles (two
-// lds_set_nibble: a lane's LDS operations execute in order, so the nibbles land on the template bytes whichever chunk
-// write came last, both heads in one chunk or one dword included) — and leave stale.  Most of a trail's chunks are
-// never looked at again before the next restart; the few that are, are known at the moment they are looked at:
-// A move reads the two new heads' cells alone, one dword each (the old heads' cells are only overwritten), and only a new
-// head can lie in a stale chunk (the old heads' chunks are in mask).  The template's chunks of the two new heads are read in
-// the same LDS round trip as the two dwords; where the chunk is stale the cell's nibble is taken from the template, and the
-// chunk is refreshed (the template's two dwords) in front of the four cell writes and leaves stale.  The four writes are
-// four ds_mskor_b32 (lds_set_nibble: memory = (memory & ~mask) | data on the cell's dword) in the reference's order; a
-// lane's LDS operations execute in order, so cells that share a dword need no merging in registers.  plain_targets and collide so see what the wiped board would have shown, an out-of-bounds head on
-// the border wall and both heads in one stale chunk included.  A move marks the chunks of its two new heads in mask and dirty.
+// A step has ONE body and one LDS round trip.  A restart is due in the step its game finishes in (the lane has made its move)
+// and, for an env that entered the launch finished, in the launch's first step without a move.  The round trip reads, for
+// every lane: the template's two dwords of the two START chunks of the env's next game (rs.z is in registers since the
+// restart before) and the start ring's word of the game after that one — the next game's kit, dropped by a lane that does
+// not restart —, and for a moving lane the two new heads' cells, one dword each (the old heads' cells are only overwritten),
+// and the template's chunks of theirs.  Only a new head can lie in a stale chunk (the old heads' chunks are in mask);
+// where it does, the cell's nibble is taken from the template.  plain_targets and collide so see what the wiped board would
+// have shown, an out-of-bounds head on the border wall and both heads in one stale chunk included.
+// Behind the judgement the board work is one piece of code: its two cells are the new heads for a move that goes on and the
+// start cells for a restart; a chunk that must be refreshed (a new head's stale chunk; both of a restart's chunks, always)
+// gets the template's two dwords and leaves stale, THEN the cell writes go on top: the old heads' body nibbles (a move
+// alone) and the two head nibbles, four ds_mskor_b32 (lds_set_nibble: memory = (memory & ~mask) | data on the cell's dword)
+// in the reference's order.  A lane's LDS operations execute in order, so cells that share a dword need no merging in
+// registers and two heads in one chunk or one dword land on the template bytes whichever chunk write came last.  The two
+// chunks are marked in mask and dirty.  A restart wipes nothing: in front of the shared part it sets dirty |= mask,
+// stale |= mask, mask = 0, so that the shared part leaves stale = (stale | mask) & ~heads, dirty |= mask | heads,
+// mask = heads.  Most of a trail's chunks are never looked at again before the next restart; the few that are, are known at
+// the moment a move looks at them.  The restart's tail sets the state words and takes the ring's word: it waits for nothing.
 // A lane writes only its own board in the loop, so the loop needs no fence and no wave barrier.
 // The epilogue stores dirty & (mask | mask0), mask0 being the mask the prologue built: a chunk outside both is the template
 // (in LDS or as a stale chunk) and was the template in memory when the launch began, so the bytes are equal.  That filter
@@ -1534,6 +1540,7 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
     const uint32_t board_lds = (uint32_t)(uintptr_t)(lds_u32 *)board;
     uint32_t hdw[2] = {lds_cell_dword(board_lds, (uint32_t)cell[0]), lds_cell_dword(board_lds, (uint32_t)cell[1])};   // the heads' dwords in LDS
     uint32_t hsh[2] = {lds_cell_shift((uint32_t)cell[0]), lds_cell_shift((uint32_t)cell[1])};                         // and their nibbles' shifts
+    uint32_t snext = (rs.y + 1u) & (2u * ROLL_R - 1u);              // the start ring's slot of episode rs.y + 1: what the next restart reads
 
     for (int s0 = 0; s0 < k_steps; s0 += ROLL_R) {
         // ---- a block begins.  The one barrier per block: behind it the helper has this block's action bytes and the
@@ -1558,35 +1565,48 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
             if constexpr (REC) load_params_scalar(P, kp);
             ROLL_STAMP(0);
 
-            // ---- the move: lane_move_codes on the packed board (two dword reads, masked-OR writes, the chunk masks)
+            // ---- the step's one body: the move's judgement, then the board work of the move or of the restart
             const bool stepped = mine && !done;
+            // The next game's kit, read speculatively in the step's one LDS round trip, whoever restarts: the template's two
+            // dwords of the two start chunks (rs.z has been in registers since the restart before, or the prologue) and the
+            // ring's word of the game after it (the slot of episode rs.y + 1: the ordinal nres + 1 <= c_b + len_b of roll_helper's
+            // invariant at every step of the block, so the slot is one the helper does not write during this block; a lane
+            // that does not restart drops the word, and so does a launch without autoreset, whose ring nobody filled).
+            // (scalars, not arrays: a select between two arrays' elements becomes a select of addresses, and the arrays scratch)
+            const uint32_t scell_a = rs.z & 0xFFFFu, scell_b = rs.z >> 16;
+            uint32_t sk_a = scell_a >> 4, sk_b = scell_b >> 4;
+            asm("" : "+v"(sk_a), "+v"(sk_b));                           // (each chunk's two dwords are one ds_read2)
+            const uint32_t ts0_a = tmpl[2u * sk_a], ts1_a = tmpl[2u * sk_a + 1u], ts0_b = tmpl[2u * sk_b], ts1_b = tmpl[2u * sk_b + 1u];
+            const uint32_t nx = sring[snext * WAVE + (uint32_t)lane];
             float rw0 = 0.0f, rw1 = 0.0f;
+            int ncell_a = 0, ncell_b = 0;                               // the new heads: the old ones' cells +-1 or +-S
+            uint32_t nk_a = 0u, nk_b = 0u, tc0_a = 0u, tc0_b = 0u, tc1_a = 0u, tc1_b = 0u;
+            bool sl_a = false, sl_b = false;
             if (stepped) {
+                int ncell[2];
+                uint32_t nk[2], tc0[2], tc1[2];
+                bool sl[2];
                 const uint32_t abyte = ab.x & 0xFFu;
                 const int a[2] = {draw_action_byte(abyte, 0, last[0], NONREV), draw_action_byte(abyte, 1, last[1], NONREV)};
-                int ncell[2];                                            // the new heads: the old ones' cells +-1 or +-S
-                unsigned long long nbit[2];
-                uint32_t nk[2], ndw[2], nsh[2];
+                uint32_t ndw[2], nsh[2];
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
                     ncell[p] = cell[p] + cell_delta(deltas, a[p]);
                     nk[p] = (uint32_t)ncell[p] >> 4;
                     asm("" : "+v"(nk[p]));                           // (the chunk index as one value: its two dwords are one ds_read2 / ds_write2)
-                    nbit[p] = 1ull << nk[p];
                     ndw[p] = lds_cell_dword(board_lds, (uint32_t)ncell[p]);
                     nsh[p] = lds_cell_shift((uint32_t)ncell[p]);
                 }
-                // One LDS round trip: the dwords of the two new heads and the template's chunks of theirs.  Only a new head can
-                // lie in a stale chunk (the old heads' chunks are in mask); its nibble then comes from the template, which is
-                // what the chunk holds once it is refreshed below.  The old heads' cells are not read: they are overwritten.
-                uint32_t bw[2], tc0[2], tc1[2];                  // (two arrays: each is indexed by the player alone)
-                bool sl[2];
+                // The round trip's other reads: the dwords of the two new heads and the template's chunks of theirs.  Only a
+                // new head can lie in a stale chunk (the old heads' chunks are in mask); its nibble then comes from the template,
+                // which is what the chunk holds once it is refreshed below.  The old heads' cells are not read: they are overwritten.
+                uint32_t bw[2];
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
                     bw[p] = *(lds_u32 *)(uintptr_t)ndw[p];
                     tc0[p] = tmpl[2u * nk[p]];
                     tc1[p] = tmpl[2u * nk[p] + 1u];
-                    sl[p] = (stale & nbit[p]) != 0ull;
+                    sl[p] = ((stale >> nk[p]) & 1ull) != 0ull;
                 }
                 uint32_t tf[2];
 #pragma unroll
@@ -1605,79 +1625,85 @@ __device__ __forceinline__ void roll_resident(kernarg_t *kp, int E, int epw, uin
                 eplen += 1u;
                 tick += 1u;
                 st_dirty = true;
-                if (!(done && autoreset)) {
-                    // the writes in the reference's order: bodies, then P1's head, then P2's (an out-of-bounds head lands on
-                    // the border WALL cell; a same-cell head-on leaves P2's head).  Each is one masked OR on the cell's dword;
-                    // same-lane LDS operations keep their order, so a later write starts from the earlier one's result.
-                    // A new head's stale chunk is refreshed first: the template's two dwords, then the cell writes on top (both
-                    // heads in one stale chunk write the same dwords twice).
-#pragma unroll
-                    for (int p = 0; p < 2; ++p) {
-                        if (sl[p]) {
-                            board[2u * nk[p]] = tc0[p];
-                            board[2u * nk[p] + 1u] = tc1[p];
-                            stale &= ~nbit[p];
-                        }
-                    }
-                    lds_set_nibble(hdw[0], hsh[0], NIB_P1_BODY);
-                    lds_set_nibble(hdw[1], hsh[1], NIB_P2_BODY);
-                    lds_set_nibble(ndw[0], nsh[0], NIB_P1_HEAD);
-                    lds_set_nibble(ndw[1], nsh[1], NIB_P2_HEAD);
-                    const unsigned long long nb = nbit[0] | nbit[1];         // (the old heads' chunks are in both already)
-                    mask |= nb;
-                    dirty |= nb;
+                ncell_a = ncell[0], ncell_b = ncell[1];
+                nk_a = nk[0], nk_b = nk[1];
+                tc0_a = tc0[0], tc0_b = tc0[1], tc1_a = tc1[0], tc1_b = tc1[1];
+                sl_a = sl[0], sl_b = sl[1];
+            }
+            // The kit is consumed here, once, on every path: behind the move's wait (LDS returns in order: nothing is left to
+            // wait for), and in front of the board work's writes, so that no wait for it stands behind them in the tail.
+            asm volatile("" : : "v"(ts0_a), "v"(ts1_a), "v"(ts0_b), "v"(ts1_b), "v"(nx));
+            const bool fin = done;                                      // what the step records: the move's outcome, or that of a
+            const int win = winner;                                     // game finished before the step (the restart's tail resets both)
+            // A restart (ACKTR.py:307-310) is due in the step the game finishes in, and in a launch's first step for an env
+            // that entered finished; only the latter makes no move.  The lane then does the move's board work at the start
+            // cells in place of the new heads.
+            const bool restart = mine && done && autoreset;
+            ROLL_STAMP(1);
+            if (stepped || restart) {
+                // The board work, one piece of code for both: a chunk that must be refreshed gets the template's two dwords (a
+                // new head's stale chunk; a restart's two head chunks, always), THEN the cell writes go on top, in the
+                // reference's order: bodies, P1's head, P2's (an out-of-bounds head lands on the border WALL cell; a
+                // same-cell head-on leaves P2's head; game.py:90-91 for a restart, which writes no body).  Each cell write
+                // is one masked OR on the cell's dword; a lane's LDS operations keep their order, so two heads in one chunk
+                // or one dword come out right (the chunk is then written twice with the same template bytes before either
+                // nibble is set), and the short last chunk is no special case: its padding nibbles are 0 in the template.
+                // A restart's old trail is not wiped: its chunks go stale by the mask as it was (an env that finishes in this
+                // step has skipped the move's writes and refreshes: there is no move's board work for it).
+                if (restart) {
+                    dirty |= mask;
+                    stale |= mask;
+                    mask = 0ull;
                 }
+                const int wcell[2] = {restart ? (int)scell_a : ncell_a, restart ? (int)scell_b : ncell_b};
+                uint32_t wk[2] = {restart ? sk_a : nk_a, restart ? sk_b : nk_b};
+                const uint32_t wd0[2] = {restart ? ts0_a : tc0_a, restart ? ts0_b : tc0_b}, wd1[2] = {restart ? ts1_a : tc1_a, restart ? ts1_b : tc1_b};
+                const bool rf[2] = {restart || sl_a, restart || sl_b};
+                uint32_t wdw[2], wsh[2];
+                unsigned long long nb = 0ull;
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
-                    cell[p] = ncell[p];
-                    hdw[p] = ndw[p];
-                    hsh[p] = nsh[p];
+                    asm("" : "+v"(wk[p]));                           // (the chunk index as one value: its two dwords are one ds_write2)
+                    wdw[p] = lds_cell_dword(board_lds, (uint32_t)wcell[p]);
+                    wsh[p] = lds_cell_shift((uint32_t)wcell[p]);
+                    const unsigned long long wbit = 1ull << wk[p];
+                    nb |= wbit;
+                    if (rf[p]) {
+                        board[2u * wk[p]] = wd0[p];
+                        board[2u * wk[p] + 1u] = wd1[p];
+                        stale &= ~wbit;
+                    }
+                }
+                if (!restart) {
+                    lds_set_nibble(hdw[0], hsh[0], NIB_P1_BODY);
+                    lds_set_nibble(hdw[1], hsh[1], NIB_P2_BODY);
+                }
+                lds_set_nibble(wdw[0], wsh[0], NIB_P1_HEAD);
+                lds_set_nibble(wdw[1], wsh[1], NIB_P2_HEAD);
+                mask |= nb;                                          // (a move's old heads' chunks are in both already)
+                dirty |= nb;
+#pragma unroll
+                for (int p = 0; p < 2; ++p) {
+                    cell[p] = wcell[p];
+                    hdw[p] = wdw[p];
+                    hsh[p] = wsh[p];
                 }
             }
-            const bool fin = done;                                      // what the step records: the move's outcome, or that of a
-            const int win = winner;                                     // game finished before the step (the restart below resets both)
-            ROLL_STAMP(1);
-
-            // ---- a restart (ACKTR.py:307-310), one divergent region: the state words, the board, the next game's starts.
-            // The board: the two head chunks only, straight-line (everything else the old game drew goes stale).  One LDS
-            // round trip reads the template's two dwords of each head chunk; the write order is: chunk 1's two dwords,
-            // chunk 2's two dwords, head 1's nibble, head 2's nibble (game.py:90-91).  The two heads are different cells,
-            // possibly of one chunk or one dword: the chunk is then written twice with the same template bytes before
-            // either nibble is set, and each lds_set_nibble touches its own four bits.  A head on the short last chunk is
-            // no special case: the chunk's padding nibbles are 0 in the template and stay 0.  A lane writes only its own
-            // board: no fence, no wave barrier.  The next game: rs4.episode moves on and the start cells of the game after
-            // it are read from the helper's ring (rs.z: start_cells_word, no r and no c here);
-            // rs4.envp and rs4.nenvp stay as the prologue read them until the epilogue (no step of mode None reads them).
-            // The carried state becomes restarted_st4's: the heads at the start cells, both alive, no last action, eplen 0.
-            if (mine && done && autoreset) {
+            // ---- a restart's tail: the state words and the next game.  Nothing here waits for LDS: the word of the game after
+            // the one that begins was read above.  The carried state becomes restarted_st4's (the heads are at the start
+            // cells already): both alive, no last action, eplen 0.  rs4.episode moves on; rs4.envp and rs4.nenvp stay as the
+            // prologue read them until the epilogue (no step of mode None reads them).
+            if (restart) {
                 alive = META_ALIVE0 | META_ALIVE1;
                 done = false;
                 winner = 0;
                 last[0] = last[1] = 0u;
                 eplen = 0u;
                 st_dirty = true;
-                cell[0] = (int)(rs.z & 0xFFFFu);                     // the ring's word: start_cells' values
-                cell[1] = (int)(rs.z >> 16);
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    hdw[p] = lds_cell_dword(board_lds, (uint32_t)cell[p]);
-                    hsh[p] = lds_cell_shift((uint32_t)cell[p]);
-                }
-                const uint32_t k1 = (uint32_t)cell[0] >> 4, k2 = (uint32_t)cell[1] >> 4;
-                const unsigned long long heads = (1ull << k1) | (1ull << k2);
-                dirty |= mask | heads;
-                stale = (stale | mask) & ~heads;                     // the old trail is not wiped: its chunks go stale
-                mask = heads;
-                const uint32_t ta[2] = {tmpl[2u * k1], tmpl[2u * k1 + 1u]}, tb[2] = {tmpl[2u * k2], tmpl[2u * k2 + 1u]};
-                board[2u * k1] = ta[0];                              // both chunks as the template has them, and only then ...
-                board[2u * k1 + 1u] = ta[1];
-                board[2u * k2] = tb[0];
-                board[2u * k2 + 1u] = tb[1];
-                lds_set_nibble(hdw[0], hsh[0], NIB_P1_HEAD);         // ... the two heads, on top of whichever write came last
-                lds_set_nibble(hdw[1], hsh[1], NIB_P2_HEAD);
                 rs.y += 1u;
                 nres += 1u;
-                rs.z = sring[(rs.y & (2u * ROLL_R - 1u)) * WAVE + lane];  // the start cells of game rs.y, drawn by the helper, in the episode's slot
+                rs.z = nx;                                           // the start cells of game rs.y, drawn by the helper
+                snext = (snext + 1u) & (2u * ROLL_R - 1u);
             }
             ROLL_STAMP(2);
 
