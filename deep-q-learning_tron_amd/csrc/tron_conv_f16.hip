@@ -219,7 +219,7 @@ __global__ __launch_bounds__(THREADS, 2) void k_conv3x3_f16(
 #pragma unroll
         for (int k = 0; k < THREADS / 64; ++k) m = fmaxf(m, red[k]);
         const int e = (int)((__float_as_uint(m) >> 23) & 255u) - 126;   // m = f 2^e, f in [0.5, 1)
-        if (m > 0.0f && e >= -100 && e <= 100) {                        // (no usable maximum: the activation scale stays)
+        if (m > 0.0f && e >= -100 && e <= 128) {                        // (no usable maximum — zero, tiny, inf, NaN: the activation scale stays)
             act_scale = __uint_as_float((uint32_t)(127 + 14 - e) << 23);
             act_unscale = __uint_as_float((uint32_t)(127 - 14 + e) << 23);
         }

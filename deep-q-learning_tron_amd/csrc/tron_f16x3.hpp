@@ -49,7 +49,8 @@ __device__ __forceinline__ uint32_t pack2(f16 a, f16 b)
 //      tree in tron_conv_wgrad.hip, a chain from 0 in tron_conv_wgrad_rows.hip); either order changes the other kernel's
 //      machine code (which maxima pair up in v_max3_f32), so that line stays with each caller;
 //   3. absmax_scale: 2^(14 - e) for a maximum m = f 2^e, which puts it in [2^13, 2^14) — or the caller's fallback where
-//      there is no usable maximum: zero, denormal, huge or NaN gradients.
+//      there is no usable maximum: zero, denormal (below 2^-101), infinite or NaN gradients.  A huge finite maximum IS scaled
+//      (down): fed to split() unscaled it would overflow f16 to inf and the MFMAs would sum inf - inf.
 // The fallback is deliberately not the same everywhere: the weight-gradient kernels fall back to 1.0 (the gradient goes
 // in unscaled), tron_conv_f16.hip's data-gradient call keeps the activation scale ACT_SCALE / ACT_UNSCALE it starts from.
 // NOT shared, each with its own copy of this arithmetic because sharing changed its machine code:
@@ -73,8 +74,8 @@ __device__ __forceinline__ float absmax_scale(float m, float fallback)
 {
     const uint32_t bits = __float_as_uint(m);
     const int e = (int)((bits >> 23) & 255u) - 126;                     // m = f 2^e, f in [0.5, 1)
-    if (!(m > 0.0f) || e < -100 || e > 100) return fallback;
-    return __uint_as_float((uint32_t)(127 + 14 - e) << 23);            // 2^(14 - e)
+    if (!(m > 0.0f) || e < -100 || e > 128) return fallback;           // (e = 129: inf.  Every finite maximum from 2^-101 up is scaled:
+    return __uint_as_float((uint32_t)(127 + 14 - e) << 23);            // 2^(14 - e) and its inverse stay normal floats up to e = 128)
 }
 
 // ---- operands read transposed out of LDS --------------------------------------------------------------------------------
