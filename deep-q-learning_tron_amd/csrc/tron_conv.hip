@@ -28,6 +28,7 @@
 
 #include "../../include/tron_hip.h"
 #include "tron_conv.hpp"
+#include "tron_launch.hpp"
 #include "tron_mish.hpp"
 
 namespace {
@@ -395,16 +396,10 @@ int launch_conv(const void *in, const float *wgt, const float *bias, const float
                 int64_t B, int cin, int cout, float plane4, int apply_mish, int in_codes, hipStream_t st)
 {
     using C = Cfg<S>;
-    auto kern = k_conv3x3<S, CODES>;
-    static uint64_t prepared = 0;     // hipFuncSetAttribute is per device
+    constexpr auto kern = k_conv3x3<S, CODES>;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return TRON_ERR_NO_DEVICE; }
-    if (!(prepared & (1ull << (dev & 63)))) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)C::LDS_BYTES) != hipSuccess)
-            (void)hipGetLastError();
-        prepared |= 1ull << (dev & 63);
-    }
+    if (current_device(dev) != TRON_OK) return TRON_ERR_NO_DEVICE;
+    allow_lds<kern>(dev, (int)C::LDS_BYTES);
     const int64_t groups = (B + C::P - 1) / C::P;
     const int64_t blocks = cout == 64 ? ((groups + 7) / 8) * 16 : groups;
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(THREADS), C::LDS_BYTES, st, in, wgt, bias, res, out, pre_out,

@@ -31,6 +31,7 @@
 
 #include "../../include/tron_hip.h"
 #include "tron_conv.hpp"
+#include "tron_launch.hpp"
 #include "tron_mish.hpp"
 
 #ifndef TRON_F16_ABLATE      // diagnostic builds only (wrong results): 1 = no staging of the next chunk, 2 = A fragments not re-read, 5 = one split-image store per tile instead of eight, 6 = no weight copies, 7 = no input loads
@@ -662,23 +663,14 @@ int launch(const void *in, const f16 *ws, const float *bias, const float *res, f
     using C = Cfg<S>;
     constexpr size_t LDS_BYTES = 4 * (size_t)C::IN_HALF + 4 * (size_t)TAPS_PAD * 32 * NT * PITCH + 1024 + (MBWD ? THREADS * 4 : 0);
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
-    auto kern = k_conv3x3_f16<S, NT, SMALL, PERSIST, MBWD>;
-    static uint64_t prepared = 0;
-    static int cus[64];
+    constexpr auto kern = k_conv3x3_f16<S, NT, SMALL, PERSIST, MBWD>;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return TRON_ERR_NO_DEVICE; }
-    if (!(prepared & (1ull << (dev & 63)))) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)LDS_BYTES) != hipSuccess)
-            (void)hipGetLastError();
-        hipDeviceProp_t prop;
-        cus[dev & 63] = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-        (void)hipGetLastError();
-        prepared |= 1ull << (dev & 63);
-    }
+    if (current_device(dev) != TRON_OK) return TRON_ERR_NO_DEVICE;
+    allow_lds<kern>(dev, (int)LDS_BYTES);
+    const int cus = device_cus(dev);
     const int64_t groups = (B + C::P - 1) / C::P * C::NB;
     // PERSIST: one workgroup per CU (the kernel's LDS allows no more) walking groups blockIdx.x, + grid, ...
-    const int64_t grid = PERSIST && groups > cus[dev & 63] ? cus[dev & 63] / C::NB * C::NB : groups;
+    const int64_t grid = PERSIST && groups > cus ? cus / C::NB * C::NB : groups;
     if (grid_out) {
         if (grid > grid_max) return TRON_ERR_UNSUPPORTED;               // (the caller sized its partial-sum scratch for grid_max workgroups)
         *grid_out = grid;

@@ -24,6 +24,7 @@
 
 #include "../../include/tron_hip.h"
 #include "tron_f16x3.hpp"
+#include "tron_launch.hpp"
 
 namespace {
 
@@ -389,15 +390,10 @@ int launch(const float *in, const float *gp, const float *absmax, int n_absmax, 
            int cout, unsigned char *ws, hipStream_t st)
 {
     using C = Cfg<CIT, IMGS>;
-    static uint64_t prepared = 0;
+    constexpr auto kern = k_wgrad<CIT, IMGS>;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return TRON_ERR_NO_DEVICE; }
-    auto kern = k_wgrad<CIT, IMGS>;
-    if (!(prepared & (1ull << (dev & 63)))) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_ALL) != hipSuccess)
-            (void)hipGetLastError();
-        prepared |= 1ull << (dev & 63);
-    }
+    if (current_device(dev) != TRON_OK) return TRON_ERR_NO_DEVICE;
+    allow_lds<kern>(dev, C::LDS_ALL);
     const int W = cout * cin * 9, nhalves = cout / (COT * 16);
     const Plan p = plan(cin, cout);
     const int nrounds = (int)((batch + IMGS - 1) / IMGS);

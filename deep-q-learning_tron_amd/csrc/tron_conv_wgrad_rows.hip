@@ -24,6 +24,7 @@
 
 #include "../../include/tron_hip.h"
 #include "tron_f16x3.hpp"
+#include "tron_launch.hpp"
 
 namespace {
 
@@ -240,15 +241,10 @@ template <class C>
 int launch_rows(const float *in, const float *gp, const float *absmax, int n_absmax, float *partial, int64_t batch, int cout,
                 int grid_max, int *nparts, hipStream_t st)
 {
-    static uint64_t prepared = 0;                                       // one bit per device: the attribute is per device
-    auto kern = k_wgrad_rows<C>;
+    constexpr auto kern = k_wgrad_rows<C>;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return TRON_ERR_NO_DEVICE; }
-    if (!(prepared & (1ull << (dev & 63)))) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS) != hipSuccess)
-            (void)hipGetLastError();
-        prepared |= 1ull << (dev & 63);
-    }
+    if (current_device(dev) != TRON_OK) return TRON_ERR_NO_DEVICE;
+    allow_lds<kern>(dev, C::LDS);
     const int nhalves = cout / C::COW;
     const int wgs = (int)(batch < grid_max / nhalves ? batch : grid_max / nhalves);
     hipLaunchKernelGGL(kern, dim3(wgs * nhalves), dim3(C::THREADS), C::LDS, st, in, gp, absmax, n_absmax, partial, (int)batch, cout);

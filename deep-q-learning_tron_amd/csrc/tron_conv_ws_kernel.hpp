@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "../../include/tron_hip.h"
+#include "tron_launch.hpp"
 #include "tron_mish.hpp"
 
 // 34x34 images (32x32 boards: the actor-critic nets): the gradient-free forward's instantiations live beside the training ones in
@@ -809,19 +810,17 @@ __global__ __launch_bounds__(256) void k_px16_to_f32(const unsigned char *__rest
     }
 }
 
-int device_cus()
+// one launch of k_conv_ws<G, RES, F32, MODE>: each of the four variants opts in to its LDS by itself
+template <class G, bool RES, bool F32, int MODE>
+void launch_ws_variant(int dev, int grid, hipStream_t st, const void *in, const void *wfrag, const float *bias, const void *res, void *out,
+                       float *out_f32, float *pre_f32, int64_t B, int apply_mish, int64_t nitems, void *pre_px, const WsBwd &bw)
 {
-    static int cus[64];
-    static uint64_t known = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 256; }
-    if (!(known & (1ull << (dev & 63)))) {
-        hipDeviceProp_t prop;
-        cus[dev & 63] = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-        (void)hipGetLastError();
-        known |= 1ull << (dev & 63);
-    }
-    return cus[dev & 63];
+    constexpr auto kern = k_conv_ws<G, RES, F32, MODE>;
+    allow_lds<kern>(dev, (int)G::LDS_BYTES);
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G::THREADS), G::LDS_BYTES, st, reinterpret_cast<const unsigned char *>(in),
+                       reinterpret_cast<const f16x8 *>(wfrag), bias, reinterpret_cast<const unsigned char *>(res),
+                       reinterpret_cast<unsigned char *>(out), out_f32, pre_f32, (int)B, apply_mish, (int)nitems,
+                       reinterpret_cast<unsigned char *>(pre_px), bw);
 }
 
 template <class G, int MODE = WS_INFER>
@@ -831,33 +830,19 @@ int launch_ws(const void *in, const void *wfrag, const float *bias, const void *
 {
     const int64_t nitems = (B + G::IPI - 1) / G::IPI * G::NB;
     if (nitems > 0x7fffffff) return TRON_ERR_UNSUPPORTED;
-    int grid = device_cus() / G::NB * G::NB;
+    int dev = 0;
+    if (current_device(dev) != TRON_OK) return TRON_ERR_NO_DEVICE;
+    int grid = device_cus(dev) / G::NB * G::NB;
     if (nitems < grid) grid = (int)nitems;
     if (grid_out) *grid_out = grid;
-    constexpr size_t LDS_ALL = G::LDS_BYTES;
-    static uint64_t prepared[4] = {0, 0, 0, 0};                         // per variant, one bit per device (the attribute is per device)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return TRON_ERR_NO_DEVICE; }
-    const uint64_t dev_bit = 1ull << (dev & 63);
-#define TRON_WS_LAUNCH(RES_, F32_)                                                                                    \
-    do {                                                                                                              \
-        auto kern = k_conv_ws<G, RES_, F32_, MODE>;                                                                   \
-        if (!(prepared[RES_ * 2 + F32_] & dev_bit)) {                                                                 \
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                    (int)LDS_ALL) != hipSuccess)                                                      \
-                (void)hipGetLastError();                                                                              \
-            prepared[RES_ * 2 + F32_] |= dev_bit;                                                                     \
-        }                                                                                                             \
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G::THREADS), LDS_ALL, st,                                    \
-                           reinterpret_cast<const unsigned char *>(in), reinterpret_cast<const f16x8 *>(wfrag), bias, \
-                           reinterpret_cast<const unsigned char *>(res), reinterpret_cast<unsigned char *>(out),      \
-                           out_f32, pre_f32, (int)B, apply_mish, (int)nitems, reinterpret_cast<unsigned char *>(pre_px), bw); \
-    } while (0)
     // anything but the chain's inner layers takes the general variant (BWD: the one that also writes f32 planes)
     const bool f32o = MODE == WS_BWD ? out_f32 != nullptr : (out_f32 || pre_f32 || !apply_mish || !out);
-    if (res) { if (f32o) TRON_WS_LAUNCH(true, true); else TRON_WS_LAUNCH(true, false); }
-    else     { if (f32o) TRON_WS_LAUNCH(false, true); else TRON_WS_LAUNCH(false, false); }
-#undef TRON_WS_LAUNCH
+    auto go = [&](auto res_, auto f32_) {
+        launch_ws_variant<G, decltype(res_)::value, decltype(f32_)::value, MODE>(dev, grid, st, in, wfrag, bias, res, out, out_f32, pre_f32, B,
+                                                                                 apply_mish, nitems, pre_px, bw);
+    };
+    if (res) { if (f32o) go(std::true_type{}, std::true_type{}); else go(std::true_type{}, std::false_type{}); }
+    else     { if (f32o) go(std::false_type{}, std::true_type{}); else go(std::false_type{}, std::false_type{}); }
     return hipGetLastError() == hipSuccess ? TRON_OK : TRON_ERR_LAUNCH;
 }
 

@@ -29,16 +29,11 @@ int launch_pool(const void *in_px16, const void *wfrag, const float *bias, const
     using G = Geo<12, 12, 64, 64, 1, 8, 1>;
     constexpr size_t LDS_ALL = G::LDS_BYTES + (G::COUT / 4) * (G::SS * 16 + 16) + 1024 + 32;     // + the output image, its dump, the pass counters
     static_assert(LDS_ALL <= 160 * 1024, "LDS");
-    auto kern = k_conv_ws<G, true, false, MODE>;
-    static uint64_t prepared = 0;
+    constexpr auto kern = k_conv_ws<G, true, false, MODE>;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return TRON_ERR_NO_DEVICE; }
-    if (!(prepared & (1ull << (dev & 63)))) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_ALL) != hipSuccess)
-            (void)hipGetLastError();
-        prepared |= 1ull << (dev & 63);
-    }
-    int grid = device_cus();
+    if (current_device(dev) != TRON_OK) return TRON_ERR_NO_DEVICE;
+    allow_lds<kern>(dev, (int)LDS_ALL);
+    int grid = device_cus(dev);
     if (batch < grid) grid = (int)batch;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G::THREADS), LDS_ALL, reinterpret_cast<hipStream_t>(stream),
                        reinterpret_cast<const unsigned char *>(in_px16), reinterpret_cast<const f16x8 *>(wfrag), bias,

@@ -414,7 +414,9 @@ int launch_wgrad_px(const void *gimg, const void *aimg, const float *ginfo, int6
 {
     static_assert(C::NB <= 8, "bands");
     const int kinds = (CO / C::COT) * (CI / C::CIT);                     // workgroup kinds: channel tiles of both operands
-    const int cus = device_cus();
+    int dev = 0;
+    const int no_device = current_device(dev);
+    const int cus = no_device ? 256 : device_cus(dev);                   // (a size query needs no device: it plans for 256 CUs)
     // workgroups per band in proportion to the band's slabs; every kind gets the same split
     int per_kind = cus / kinds;
     if (per_kind < C::NB) per_kind = C::NB;
@@ -435,14 +437,8 @@ int launch_wgrad_px(const void *gimg, const void *aimg, const float *ginfo, int6
     }
     const int64_t parts = (int64_t)used * C::KG;                         // per kind: disjoint (co, ci) tiles, so the kinds share the parts
     if (ws_need) { *ws_need = parts * 9 * CO * CI * (int64_t)sizeof(float); return TRON_OK; }
-    static uint64_t prepared = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return TRON_ERR_NO_DEVICE; }
-    if (!(prepared & (1ull << (dev & 63)))) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_wgrad_px<C>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS) != hipSuccess)
-            (void)hipGetLastError();
-        prepared |= 1ull << (dev & 63);
-    }
+    if (no_device) return no_device;
+    allow_lds<k_wgrad_px<C>>(dev, C::LDS);
     WBands bands;
     for (int b = 0; b < 8; ++b) bands.n[b] = nwg[b];
     const int grid = (used + 7) / 8 * 8 * kinds;                        // (wg = 8 (block / (8 kinds)) + block % 8: whole groups of 8 per kind)
@@ -685,20 +681,16 @@ template <class C>
 int launch_conv1_wgrad(const int8_t *codes, const void *gimg, const float *ginfo, int64_t B, int cin, float plane4, float *partial, float *gw,
                        hipStream_t st, int64_t *ws_need)
 {
-    const int cus = device_cus();
+    int dev = 0;
+    const int no_device = current_device(dev);
+    const int cus = no_device ? 256 : device_cus(dev);                   // (a size query needs no device: it plans for 256 CUs)
     int per_cu = (160 * 1024) / C::LDS;
     per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
     int64_t grid = (int64_t)cus * per_cu;
     if (grid > B * C::NBAND) grid = B * C::NBAND;
     if (ws_need) { *ws_need = (int64_t)cus * 4 * 32 * C::NCOL * (int64_t)sizeof(float); return TRON_OK; }
-    static uint64_t prepared = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return TRON_ERR_NO_DEVICE; }
-    if (!(prepared & (1ull << (dev & 63)))) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv1_wgrad_px<C>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS) != hipSuccess)
-            (void)hipGetLastError();
-        prepared |= 1ull << (dev & 63);
-    }
+    if (no_device) return no_device;
+    allow_lds<k_conv1_wgrad_px<C>>(dev, C::LDS);
     hipLaunchKernelGGL(k_conv1_wgrad_px<C>, dim3((unsigned)grid), dim3(256), C::LDS, st, codes, reinterpret_cast<const unsigned char *>(gimg), (int)B, partial);
     hipLaunchKernelGGL(k_conv1_wgrad_finish, dim3(32), dim3(768), 0, st, partial, (int)grid, cin, plane4, ginfo, gw);
     return hipGetLastError() == hipSuccess ? TRON_OK : TRON_ERR_LAUNCH;

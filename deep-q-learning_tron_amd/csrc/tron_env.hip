@@ -58,6 +58,7 @@
 //   k_inc                                     inline in the kernel   lane_move_codes' steps on code bytes in global memory
 //   k_obs_roll, k_obs_roll_tape(_rec)         inline in roll_resident  the same steps on 4-bit codes in LDS, with the chunk masks
 #include "tron_device.hpp"
+#include "tron_launch.hpp"
 #include "tron_minimax.hpp"
 #include "../../include/tron_hip.h"
 
@@ -2344,7 +2345,7 @@ namespace {
 
 inline hipStream_t S_(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
-constexpr size_t LDS_LIMIT = 160u * 1024u;   // a CU's LDS: the most a workgroup can be given, and only after the opt-in (allow_big_lds)
+constexpr size_t LDS_LIMIT = 160u * 1024u;   // a CU's LDS: the most a workgroup can be given, and only after the opt-in (allow_lds)
 
 inline bool is_f32_planes(int fmt) { return fmt == TRON_OBS_PLANES3_F32 || fmt == TRON_OBS_PLANES4_F32; }
 
@@ -2409,26 +2410,13 @@ TRON_KERNEL(false, k_encode_codes);       // no handle: the caller's tiles to th
 TRON_KERNEL(false, k_pop_up);             // no handle: the caller's codes to the caller's planes
 #undef TRON_KERNEL
 
-// hipFuncSetAttribute acts on the current device only: remember, per kernel, which devices it was prepared on (one bit per
-// device ordinal) instead of a per-process flag.
-template <auto Kernel>
-void allow_big_lds(int device)
-{
-    static uint64_t prepared = 0;
-    const uint64_t bit = 1ull << ((unsigned)device & 63u);
-    if (prepared & bit) return;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT) != hipSuccess)
-        (void)hipGetLastError();
-    prepared |= bit;
-}
-
 // Every kernel launch of this file.  The LDS opt-in of a kernel that takes dynamic LDS, on first use; the invalidation its
 // row of the table asks for; an empty grid (a part without tiles) launches nothing.  h may be null where smem is 0 and the
 // kernel writes no state (the entry points without a handle).
 template <auto Kernel, class... Args>
 int launch(tron_env *h, dim3 grid, dim3 block, size_t smem, hipStream_t st, Args... args)
 {
-    if (smem) allow_big_lds<Kernel>(h->device);
+    if (smem) allow_lds<Kernel>(h->device, (int)LDS_LIMIT);
     if constexpr (writes_state<Kernel>::value) h->entry_masks = h->handed = false;
     if (grid.x > 0) hipLaunchKernelGGL(Kernel, grid, block, smem, st, args...);
     return hipGetLastError() == hipSuccess ? TRON_OK : TRON_ERR_LAUNCH;
@@ -2824,7 +2812,7 @@ int roll_tile_envs(const tron_env *h)
     const int E0 = h->E;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) { (void)hipGetLastError(); return E0; }
-    allow_big_lds<k_obs_roll_walk>(h->device);                          // (the query below is made in front of its first launch)
+    allow_lds<k_obs_roll_walk>(h->device, (int)LDS_LIMIT);                   // (the query below is made in front of its first launch)
     int best = E0;
     double best_fill = -1.0;
     for (int E = E0; E >= (3 * E0 + 3) / 4 && E >= 1; --E) {
@@ -2889,7 +2877,7 @@ void report_roll_shape(const tron_env *h, int E, int waves, int epw, size_t smem
     static bool reported = false;
     if (reported) return;
     reported = true;
-    allow_big_lds<k_obs_roll>(h->device);
+    allow_lds<k_obs_roll>(h->device, (int)LDS_LIMIT);
     int per_cu = 0;
     hipDeviceProp_t prop;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_obs_roll, 2 * waves * WAVE, smem) == hipSuccess &&

@@ -78,6 +78,32 @@ __device__ __forceinline__ float absmax_scale(float m, float fallback)
     return __uint_as_float((uint32_t)(127 + 14 - e) << 23);            // 2^(14 - e) and its inverse stay normal floats up to e = 128)
 }
 
+// ---- the product over a wave's TM x TN block of 16 x 16 MFMA tiles, one 32-deep K slab ---------------------------------------
+// acc0 += ah bh, acc1 += ah bl + al bh (whoever reads them joins acc0 + acc1 * LO_UNSCALE), as three sweeps over the block:
+// hi*lo, hi*hi, lo*hi.  The lo*hi MFMA adds to the accumulator the hi*lo one wrote, and a dependent MFMA issues 48 cycles
+// after its producer — two sweeps (eight MFMAs at 2 x 2) apart nobody waits.
+// NOT shared: k_gram2_f16x3 in tron_kfac.hip keeps the same three sweeps open-coded — through this helper the same instructions
+// come out under another register allocation (its accumulators are zeroed in another order and the MFMAs name other registers);
+// k_gram_nchw there interleaves the three products per tile on purpose.  The 1-D sites (one row or column of tiles per wave:
+// k_conv7_wgrad, tron_kfac_px.hip, the conv kernels) have loops of their own shape.
+template <int TM, int TN>
+__device__ __forceinline__ void mma_f16x3(const f16x8 (&ah)[TM], const f16x8 (&al)[TM], const f16x8 (&bh)[TN], const f16x8 (&bl)[TN],
+                                          f32x4 (&acc0)[TM][TN], f32x4 (&acc1)[TM][TN])
+{
+#pragma unroll
+    for (int t = 0; t < TM; ++t)
+#pragma unroll
+        for (int n = 0; n < TN; ++n) acc1[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[t], bl[n], acc1[t][n], 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < TM; ++t)
+#pragma unroll
+        for (int n = 0; n < TN; ++n) acc0[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[t], bh[n], acc0[t][n], 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < TM; ++t)
+#pragma unroll
+        for (int n = 0; n < TN; ++n) acc1[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[t], bh[n], acc1[t][n], 0, 0, 0);
+}
+
 // ---- operands read transposed out of LDS --------------------------------------------------------------------------------
 // ds_read_b64_tr_b16 by inline asm, not by __builtin_amdgcn_ds_read_tr16_b64: behind the builtin hipcc (ROCm 7.2) puts an
 // s_waitcnt vmcnt(0) in front of every transposed read that follows an LDS-DMA (it cannot tell the read from the copy's

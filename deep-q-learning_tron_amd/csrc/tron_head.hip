@@ -14,7 +14,8 @@
 //     k_gemm_f16x3      C = act(A W^T + bias), A and W split f16 row-major; C as f32 and / or split f16
 //     k_q_head          actor2 (64 -> 4) in f32 + argmax
 // GEMM tile: 128 x 64 per 8-wave workgroup (wave = 32 x 32 = 2 x 2 MFMA tiles), K in chunks of 64 staged by 16-byte
-// copies into single-buffered LDS (60 KB: two workgroups share a CU and cover each other's barriers).
+// copies into single-buffered LDS (60 KB: two workgroups share a CU and cover each other's barriers) — or, the same kernel
+// template with six column tiles per wave, 128 x 192 where N and K allow it (wide_splitk).
 //
 // The same layers on the TRAINING path (loss.backward() through them, DDQN.py:148):
 //     12x12:           tron_pool12 / tron_conv7_dense around tron_gemm_f16x3 (conv7's dense form: three plain GEMMs)
@@ -28,6 +29,7 @@
 #include <stdint.h>
 
 #include "../../include/tron_hip.h"
+#include "tron_launch.hpp"
 #include "tron_mish.hpp"
 
 namespace {
@@ -452,8 +454,8 @@ constexpr int GM = 128, GN = 64, GK = 64;          // workgroup tile, K chunk
 constexpr int GPITCH = GK * 2 + 32;                // bytes per LDS row: 32 mod 64 is conflict-free for ds_read_b128 by (row = lane % 16,
                                                    // column = lane / 16) with the instruction's lane groups; 16 mod 32 (144) is two-way
 constexpr int G_THREADS = 512;
-constexpr int A_HALF = GM * GPITCH, W_HALF = GN * GPITCH;
-constexpr int G_LDS = 2 * A_HALF + 2 * W_HALF;     // 61 440 bytes
+constexpr int A_HALF = GM * GPITCH;                // bytes of the tile's A rows, hi (or lo)
+constexpr int WN = 192;                            // the wide tile's columns (GN: the narrow one's)
 
 // C[M][N] = act((A W^T) * 64 + bias[n / bias_div]); A = Ah + Al 2^-11 (pre-scaled by 2^-6), W = Wh + Wl 2^-11, all f16
 // row-major with K contiguous.  N % 64 == 0, K % 64 == 0.  out_f32 and / or (out_h, out_l) (pre-scaled by 2^-6 again).
@@ -519,23 +521,37 @@ __device__ __forceinline__ int64_t a_piece_bytes(const RowGeo &r, int kc, int K,
     }
 }
 
-template <int MODE, int PS>
-__global__ __launch_bounds__(G_THREADS, 4) void k_gemm_f16x3(const f16 *__restrict__ Ah, const f16 *__restrict__ Al,
-                                                             const f16 *__restrict__ Wh, const f16 *__restrict__ Wl,
-                                                             const float *__restrict__ bias, int bias_div, int M, int N,
-                                                             int K, int act, float *__restrict__ out_f32,
-                                                             f16 *__restrict__ out_h, f16 *__restrict__ out_l,
-                                                             const float *__restrict__ a_scale, int cls)
+// One wave owns 32 rows x 16 NT columns (2 x NT MFMA tiles), the 8 waves = 4 (rows) x 2 (columns) a 128 x 32 NT tile:
+//   NT = 2   128 x 64, 61 440 bytes of LDS, four workgroups per CU; every MODE
+//   NT = 6   128 x 192 (N % 192 == 0: conv7's dense form, N = 576), 102 400 bytes, two per CU; G_PLAIN only.  The narrow tile
+//            pulls (128 + 64) rows of K through L2 -> LDS per 128 x 64 outputs, this one (128 + 192) rows per 128 x 192: 1.8x
+//            less feed per output, and a wave's A fragments serve six column tiles instead of two (LDS reads per MFMA 0.44
+//            against 0.67); 96 accumulator registers.  It alone is cut along K: slice blockIdx.y of the `aux` slices of the K
+//            chunks, and with `partial` the raw sums go to partial[slice][M][N] (k_gemm_finish adds them in slice order).
+// aux: the parity class of a DGRAD7 launch (NT = 2), the number of K slices (NT = 6).
+constexpr int gemm_lds(int nt) { return 2 * A_HALF + 2 * (32 * nt) * GPITCH; }
+template <int MODE, int PS, int NT>
+__global__ __launch_bounds__(G_THREADS, NT == 2 ? 4 : 2) void k_gemm_f16x3(const f16 *__restrict__ Ah, const f16 *__restrict__ Al,
+                                                                           const f16 *__restrict__ Wh, const f16 *__restrict__ Wl,
+                                                                           const float *__restrict__ bias, int bias_div, int M, int N,
+                                                                           int K, int act, float *__restrict__ out_f32,
+                                                                           f16 *__restrict__ out_h, f16 *__restrict__ out_l,
+                                                                           const float *__restrict__ a_scale, int aux,
+                                                                           float *__restrict__ partial)
 {
+    static_assert(NT == 2 || NT == 6, "a wave's column tiles: the 128 x 64 or the 128 x 192 tile");
+    static_assert(MODE == G_PLAIN || NT == 2, "the CONV7 / DGRAD7 row geometry exists on the 128 x 64 tile only");
+    constexpr bool SPLITK = MODE == G_PLAIN && NT == 6;
+    constexpr int TN = 32 * NT, W_HALF = TN * GPITCH, W_PIECES = TN * 8;  // the tile's columns; bytes and 16-byte pieces of a W half
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     unsigned char *a_h = lds, *a_l = lds + A_HALF, *w_h = lds + 2 * A_HALF, *w_l = w_h + W_HALF;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave & 3, wn = wave >> 2, li = lane & 15, g = lane >> 4;
-    const int nblocks = N / GN;
-    const int m0 = (blockIdx.x / nblocks) * GM, n0 = (blockIdx.x % nblocks) * GN;   // neighbours share the A rows in L2
+    const int cls = aux, nblocks = N / TN;
+    const int m0 = (blockIdx.x / nblocks) * GM, n0 = (blockIdx.x % nblocks) * TN;   // neighbours share the A rows in L2
 
-    // staging: 16-byte pieces; A: [2 halves][128 rows][8 pieces], W: [2 halves][64 rows][8 pieces]
-    f32x4 ra[4], rw[2];
+    // staging: 16-byte pieces; A: [2 halves][128 rows][8 pieces], W: [2 halves][32 NT rows][8 pieces]
+    f32x4 ra[4], rw[NT];
     RowGeo rg[2];                                                         // (pieces j and j + 2 of a thread are the two halves of one row)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -552,8 +568,8 @@ __global__ __launch_bounds__(G_THREADS, 4) void k_gemm_f16x3(const f16 *__restri
             if (MODE == G_PLAIN || ab >= 0) ra[j] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const unsigned char *>(half ? Al : Ah) + ab + pc * 16);
         }
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int q = tid + j * G_THREADS, half = q >> 9, r = q & 511, row = r >> 3, pc = r & 7;
+        for (int j = 0; j < NT; ++j) {
+            const int q = tid + j * G_THREADS, half = q / W_PIECES, r = q % W_PIECES, row = r >> 3, pc = r & 7;
             rw[j] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const unsigned char *>(half ? Wl : Wh) +
                                                      ((size_t)(n0 + row) * K + (size_t)kc * GK) * 2 + pc * 16);
         }
@@ -565,51 +581,48 @@ __global__ __launch_bounds__(G_THREADS, 4) void k_gemm_f16x3(const f16 *__restri
             *reinterpret_cast<f32x4 *>(lds + half * A_HALF + row * GPITCH + pc * 16) = ra[j];
         }
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int q = tid + j * G_THREADS, half = q >> 9, r = q & 511, row = r >> 3, pc = r & 7;
+        for (int j = 0; j < NT; ++j) {
+            const int q = tid + j * G_THREADS, half = q / W_PIECES, r = q % W_PIECES, row = r >> 3, pc = r & 7;
             *reinterpret_cast<f32x4 *>(lds + 2 * A_HALF + half * W_HALF + row * GPITCH + pc * 16) = rw[j];
         }
     };
 
-    f32x4 acc0[2][2], acc1[2][2];
+    f32x4 acc0[2][NT], acc1[2][NT];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) {
+        for (int b = 0; b < NT; ++b) {
             acc0[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
             acc1[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
-    const int a_off = (wm * 32 + li) * GPITCH + g * 16, b_off = (wn * 32 + li) * GPITCH + g * 16;
-    const int nk = K / GK;
-    load_chunk(0);
-    store_chunk();
+    const int a_off = (wm * 32 + li) * GPITCH + g * 16, b_off = (wn * 16 * NT + li) * GPITCH + g * 16;
+    int kb = 0, nk = K / GK;                                             // this workgroup's K chunks [kb, nk): all of them, or its slice
+    if constexpr (SPLITK) {
+        const int per = (nk + aux - 1) / aux;
+        kb = (int)blockIdx.y * per;
+        nk = kb + per < nk ? kb + per : nk;
+    }
+    if (!SPLITK || kb < nk) {
+        load_chunk(kb);
+        store_chunk();
+    }
     __syncthreads();
-    for (int kc = 0; kc < nk; ++kc) {
+    for (int kc = kb; kc < nk; ++kc) {
         if (kc + 1 < nk) load_chunk(kc + 1);                            // in flight under the MFMAs
 #pragma unroll
         for (int s = 0; s < GK / 32; ++s) {
-            f16x8 ah[2], al[2], bh[2], bl[2];
+            f16x8 ah[2], al[2], bh[NT], bl[NT];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 ah[t] = *reinterpret_cast<const f16x8 *>(a_h + a_off + t * 16 * GPITCH + s * 64);
                 al[t] = *reinterpret_cast<const f16x8 *>(a_l + a_off + t * 16 * GPITCH + s * 64);
-                bh[t] = *reinterpret_cast<const f16x8 *>(w_h + b_off + t * 16 * GPITCH + s * 64);
-                bl[t] = *reinterpret_cast<const f16x8 *>(w_l + b_off + t * 16 * GPITCH + s * 64);
             }
-            // hi*lo, hi*hi, lo*hi over the four tiles each: the lo*hi MFMA adds to the accumulator the hi*lo one wrote,
-            // and a dependent MFMA issues 48 cycles after its producer — eight MFMAs apart nobody waits
 #pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int n = 0; n < 2; ++n) acc1[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[t], bl[n], acc1[t][n], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int n = 0; n < 2; ++n) acc0[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[t], bh[n], acc0[t][n], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int n = 0; n < 2; ++n) acc1[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[t], bh[n], acc1[t][n], 0, 0, 0);
+            for (int n = 0; n < NT; ++n) {
+                bh[n] = *reinterpret_cast<const f16x8 *>(w_h + b_off + n * 16 * GPITCH + s * 64);
+                bl[n] = *reinterpret_cast<const f16x8 *>(w_l + b_off + n * 16 * GPITCH + s * 64);
+            }
+            mma_f16x3(ah, al, bh, bl, acc0, acc1);
         }
         __syncthreads();                                                 // everyone is done reading this chunk
         if (kc + 1 < nk) {
@@ -622,16 +635,23 @@ __global__ __launch_bounds__(G_THREADS, 4) void k_gemm_f16x3(const f16 *__restri
     const float out_scale = a_scale ? ACT_UNSCALE / *a_scale : ACT_UNSCALE;
     // epilogue: D row = 4 * (lane >> 4) + r, column = lane & 15
 #pragma unroll
-    for (int n = 0; n < 2; ++n) {
-        const int col = n0 + wn * 32 + n * 16 + li;
+    for (int n = 0; n < NT; ++n) {
+        const int col = n0 + wn * 16 * NT + n * 16 + li;
         const float bv = bias ? bias[col / bias_div] : 0.0f;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            const f32x4 v = (acc0[t][n] + acc1[t][n] * LO_UNSCALE) * out_scale + bv;
+            const f32x4 raw = acc0[t][n] + acc1[t][n] * LO_UNSCALE;
+            const f32x4 v = raw * out_scale + bv;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int m = m0 + wm * 32 + t * 16 + 4 * g + r;
                 if (m >= M) continue;
+                if constexpr (SPLITK) {
+                    if (partial) {                                       // a K slice's raw sums: k_gemm_finish has the epilogue
+                        partial[((size_t)blockIdx.y * M + m) * N + col] = raw[r];
+                        continue;
+                    }
+                }
                 const float y = act ? mish_fast(v[r]) : v[r];
                 if constexpr (MODE == G_DGRAD7) {                        // row m of the class -> its pooled pixel, channels-last
                     const RowGeo o = row_geo<MODE, PS>(m, cls);
@@ -651,136 +671,7 @@ __global__ __launch_bounds__(G_THREADS, 4) void k_gemm_f16x3(const f16 *__restri
     }
 }
 
-
-// ---- the same product on a 128 x 192 tile (N % 192 == 0: conv7's dense form, N = 576) --------------------------------------
-// k_gemm_f16x3's 128 x 64 tile pulls (128 + 64) rows of K through L2 -> LDS per 128 x 64 outputs; this one (128 + 192) rows per
-// 128 x 192: 1.8x less feed per output, and a wave's A fragments serve six column tiles instead of two (LDS reads per MFMA 0.44
-// against 0.67).  8 waves = 4 (rows) x 2 (columns), a wave 32 x 96 outputs = 2 x 6 MFMA tiles, 96 accumulator registers.
-// splitk > 1: slice blockIdx.y of the K chunks, raw sums to partial[slice][M][N] (k_gemm_finish adds them in slice order).
-constexpr int WN = 192, WW_HALF = WN * GPITCH;
-constexpr int GW_LDS = 2 * A_HALF + 2 * WW_HALF;    // 102 400 bytes
-__global__ __launch_bounds__(G_THREADS, 2) void k_gemm_wide(const f16 *__restrict__ Ah, const f16 *__restrict__ Al,
-                                                            const f16 *__restrict__ Wh, const f16 *__restrict__ Wl,
-                                                            const float *__restrict__ bias, int bias_div, int M, int N, int K, int act,
-                                                            float *__restrict__ out_f32, f16 *__restrict__ out_h, f16 *__restrict__ out_l,
-                                                            const float *__restrict__ a_scale, int splitk, float *__restrict__ partial)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    unsigned char *a_h = lds, *a_l = lds + A_HALF, *w_h = lds + 2 * A_HALF, *w_l = w_h + WW_HALF;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave & 3, wn = wave >> 2, li = lane & 15, g = lane >> 4;
-    const int nblocks = N / WN;
-    const int m0 = (blockIdx.x / nblocks) * GM, n0 = (blockIdx.x % nblocks) * WN;
-
-    f32x4 ra[4], rw[6];
-    auto load_chunk = [&](int kc) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {                                    // A: [2 halves][128 rows][8 pieces]
-            const int q = tid + j * G_THREADS, half = q >> 10, r = q & 1023, row = r >> 3, pc = r & 7;
-            int m = m0 + row;
-            m = m < M ? m : M - 1;
-            ra[j] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const unsigned char *>(half ? Al : Ah) + ((size_t)m * K + (size_t)kc * GK) * 2 + pc * 16);
-        }
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {                                    // W: [2 halves][192 rows][8 pieces]
-            const int q = tid + j * G_THREADS, half = q >= 1536 ? 1 : 0, r = q - half * 1536, row = r >> 3, pc = r & 7;
-            rw[j] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const unsigned char *>(half ? Wl : Wh) + ((size_t)(n0 + row) * K + (size_t)kc * GK) * 2 + pc * 16);
-        }
-    };
-    auto store_chunk = [&]() {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int q = tid + j * G_THREADS, half = q >> 10, r = q & 1023, row = r >> 3, pc = r & 7;
-            *reinterpret_cast<f32x4 *>(lds + half * A_HALF + row * GPITCH + pc * 16) = ra[j];
-        }
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            const int q = tid + j * G_THREADS, half = q >= 1536 ? 1 : 0, r = q - half * 1536, row = r >> 3, pc = r & 7;
-            *reinterpret_cast<f32x4 *>(lds + 2 * A_HALF + half * WW_HALF + row * GPITCH + pc * 16) = rw[j];
-        }
-    };
-
-    f32x4 acc0[2][6], acc1[2][6];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 6; ++b) {
-            acc0[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            acc1[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-    const int a_off = (wm * 32 + li) * GPITCH + g * 16, b_off = (wn * 96 + li) * GPITCH + g * 16;
-    const int nk_all = K / GK, per = (nk_all + splitk - 1) / splitk;
-    const int kb = (int)blockIdx.y * per, nk = kb + per < nk_all ? kb + per : nk_all;
-    if (kb < nk) {
-        load_chunk(kb);
-        store_chunk();
-    }
-    __syncthreads();
-    for (int kc = kb; kc < nk; ++kc) {
-        if (kc + 1 < nk) load_chunk(kc + 1);                            // in flight under the MFMAs
-#pragma unroll
-        for (int s = 0; s < GK / 32; ++s) {
-            f16x8 ah[2], al[2], bh[6], bl[6];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                ah[t] = *reinterpret_cast<const f16x8 *>(a_h + a_off + t * 16 * GPITCH + s * 64);
-                al[t] = *reinterpret_cast<const f16x8 *>(a_l + a_off + t * 16 * GPITCH + s * 64);
-            }
-#pragma unroll
-            for (int n = 0; n < 6; ++n) {
-                bh[n] = *reinterpret_cast<const f16x8 *>(w_h + b_off + n * 16 * GPITCH + s * 64);
-                bl[n] = *reinterpret_cast<const f16x8 *>(w_l + b_off + n * 16 * GPITCH + s * 64);
-            }
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int n = 0; n < 6; ++n) acc1[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[t], bl[n], acc1[t][n], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int n = 0; n < 6; ++n) acc0[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[t], bh[n], acc0[t][n], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int n = 0; n < 6; ++n) acc1[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[t], bh[n], acc1[t][n], 0, 0, 0);
-        }
-        __syncthreads();
-        if (kc + 1 < nk) {
-            store_chunk();
-            __syncthreads();
-        }
-    }
-    const float out_scale = a_scale ? ACT_UNSCALE / *a_scale : ACT_UNSCALE;
-#pragma unroll
-    for (int n = 0; n < 6; ++n) {
-        const int col = n0 + wn * 96 + n * 16 + li;
-        const float bv = bias ? bias[col / bias_div] : 0.0f;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const f32x4 raw = acc0[t][n] + acc1[t][n] * LO_UNSCALE;
-            const f32x4 v = raw * out_scale + bv;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = m0 + wm * 32 + t * 16 + 4 * g + r;
-                if (m >= M) continue;
-                if (partial) {
-                    partial[((size_t)blockIdx.y * M + m) * N + col] = raw[r];
-                    continue;
-                }
-                const float y = act ? mish_fast(v[r]) : v[r];
-                if (out_f32) out_f32[(size_t)m * N + col] = y;
-                if (out_h) {
-                    f16 hh, ll;
-                    split(y * ACT_SCALE, hh, ll);
-                    out_h[(size_t)m * N + col] = hh;
-                    out_l[(size_t)m * N + col] = ll;
-                }
-            }
-        }
-    }
-}
-
-// the K slices of k_gemm_wide added in slice order, then its epilogue; four columns per thread
+// the K slices of the 128 x 192 tile added in slice order, then its epilogue; four columns per thread
 __global__ void k_gemm_finish(const float *__restrict__ partial, int splitk, int64_t M, int N, const float *__restrict__ bias,
                               int bias_div, int act, const float *__restrict__ a_scale, float *__restrict__ out_f32,
                               f16 *__restrict__ out_h, f16 *__restrict__ out_l)
@@ -839,7 +730,7 @@ __global__ void k_q_head(const float *__restrict__ x, const float *__restrict__ 
 
 inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
-// Which launches take k_gemm_wide, and in how many K slices (0: k_gemm_f16x3).  Measured (profiles/r04_head_gemm_wide.txt): the wide
+// Which launches take the 128 x 192 tile (NT = 6), and in how many K slices (0: the 128 x 64 tile).  Measured (profiles/r04_head_gemm_wide.txt): the wide
 // tile wins where K is long — conv7's dense forward (K = 2 304: 89 -> 75 us at 4 096 rows, 150 -> 121 at 8 192, 1 035 -> 804 at
 // 65 536) and its weight gradient (K = the batch: 99 -> 80 us) — and loses at K = 576 (conv7's input gradient: 68 -> 74 us).
 // Few tiles are cut along K so that most of the 256 CUs have one: the slices' raw sums go through `partial` and k_gemm_finish.
@@ -875,7 +766,7 @@ HeadPlan plan(int64_t B, int K7, int N7, int64_t a7_per_image = 0, int d7_rows =
     p.c2h = take(B * 128 * 2); p.c2l = take(B * 128 * 2);
     p.w3h = take(64 * 128 * 2); p.w3l = take(64 * 128 * 2);
     p.c3 = take(B * 64 * 4);
-    p.part = take(a7_per_image ? 0 : wide_partial_bytes(B, N7, K7));     // (conv7's dense form: the K slices of k_gemm_wide)
+    p.part = take(a7_per_image ? 0 : wide_partial_bytes(B, N7, K7));     // (conv7's dense form: the K slices of the 128 x 192 tile)
     p.total = o;
     return p;
 }
@@ -885,38 +776,28 @@ int gemm(const f16 *Ah, const f16 *Al, const f16 *Wh, const f16 *Wl, const float
          int act, float *out_f32, f16 *out_h, f16 *out_l, hipStream_t st, const float *a_scale = nullptr, int cls = 0,
          float *partial_ws = nullptr)
 {
-    static uint64_t prepared = 0;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return TRON_ERR_NO_DEVICE; }
-    if (!(prepared & (1ull << (dev & 63)))) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_f16x3<MODE, PS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                G_LDS) != hipSuccess)
-            (void)hipGetLastError();
-        prepared |= 1ull << (dev & 63);
-    }
+    if (current_device(dev) != TRON_OK) return TRON_ERR_NO_DEVICE;
     if (M >= (1ll << 31) || N % GN != 0 || K % GK != 0) return TRON_ERR_UNSUPPORTED;
     if (M == 0) return TRON_OK;
-    if (MODE == G_PLAIN) {
+    const int64_t mtiles = (M + GM - 1) / GM;
+    if constexpr (MODE == G_PLAIN) {
         const int splitk = wide_splitk(M, N, K);
         if (splitk == 1 || (splitk > 1 && partial_ws)) {
-            static uint64_t prepared_wide = 0;
-            if (!(prepared_wide & (1ull << (dev & 63)))) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_wide), hipFuncAttributeMaxDynamicSharedMemorySize, GW_LDS) != hipSuccess)
-                    (void)hipGetLastError();
-                prepared_wide |= 1ull << (dev & 63);
-            }
-            const int64_t tiles = ((M + GM - 1) / GM) * (N / WN);
-            hipLaunchKernelGGL(k_gemm_wide, dim3((unsigned)tiles, splitk), dim3(G_THREADS), GW_LDS, st, Ah, Al, Wh, Wl, bias, bias_div, (int)M, N, K, act,
-                               out_f32, out_h, out_l, a_scale, splitk, splitk > 1 ? partial_ws : nullptr);
+            constexpr auto wide = k_gemm_f16x3<G_PLAIN, PS, 6>;
+            allow_lds<wide>(dev, gemm_lds(6));
+            hipLaunchKernelGGL(wide, dim3((unsigned)(mtiles * (N / WN)), splitk), dim3(G_THREADS), gemm_lds(6), st, Ah, Al, Wh, Wl, bias, bias_div,
+                               (int)M, N, K, act, out_f32, out_h, out_l, a_scale, splitk, splitk > 1 ? partial_ws : nullptr);
             if (splitk > 1)
                 hipLaunchKernelGGL(k_gemm_finish, dim3((unsigned)((M * N / 4 + 255) / 256)), dim3(256), 0, st, partial_ws, splitk, M, N, bias, bias_div,
                                    act, a_scale, out_f32, out_h, out_l);
             return hipGetLastError() == hipSuccess ? TRON_OK : TRON_ERR_LAUNCH;
         }
     }
-    const int64_t blocks = ((M + GM - 1) / GM) * (N / GN);
-    hipLaunchKernelGGL((k_gemm_f16x3<MODE, PS>), dim3((unsigned)blocks), dim3(G_THREADS), G_LDS, st, Ah, Al, Wh, Wl, bias, bias_div,
-                       (int)M, N, K, act, out_f32, out_h, out_l, a_scale, cls);
+    constexpr auto narrow = k_gemm_f16x3<MODE, PS, 2>;
+    allow_lds<narrow>(dev, gemm_lds(2));
+    hipLaunchKernelGGL(narrow, dim3((unsigned)(mtiles * (N / GN))), dim3(G_THREADS), gemm_lds(2), st, Ah, Al, Wh, Wl, bias, bias_div, (int)M, N, K,
+                       act, out_f32, out_h, out_l, a_scale, cls, (float *)nullptr);
     return hipGetLastError() == hipSuccess ? TRON_OK : TRON_ERR_LAUNCH;
 }
 
@@ -1568,15 +1449,9 @@ int p7_bwd(const float *gy, const float *pre, const void *saved, const float *w,
         if (hipGetLastError() != hipSuccess) return TRON_ERR_LAUNCH;
     }
     if (gw) {
-        static uint64_t prepared = 0;
         int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return TRON_ERR_NO_DEVICE; }
-        if (!(prepared & (1ull << (dev & 63)))) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv7_wgrad<PS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    W7<PS>::LDS) != hipSuccess)
-                (void)hipGetLastError();
-            prepared |= 1ull << (dev & 63);
-        }
+        if (current_device(dev) != TRON_OK) return TRON_ERR_NO_DEVICE;
+        allow_lds<k_conv7_wgrad<PS>>(dev, W7<PS>::LDS);
         const int nsl = (int)(B < W7_SLICES ? B : W7_SLICES);
         float *wpart = reinterpret_cast<float *>(ws + p.wpart);
         hipLaunchKernelGGL(k_conv7_wgrad<PS>, dim3((unsigned)(7 * nsl)), dim3(W7_THREADS), W7<PS>::LDS, st, gph, gpl, ph, pl, (int)B, nsl, wpart);

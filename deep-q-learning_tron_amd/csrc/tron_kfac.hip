@@ -18,6 +18,7 @@
 #include "../../include/tron_hip.h"
 #include "tron_f16x3.hpp"
 #include "tron_kfac_px.hpp"
+#include "tron_launch.hpp"
 #include <stdlib.h>
 
 namespace {
@@ -76,13 +77,9 @@ extern "C" int tron_extract_patches(const float *x, int64_t batch, int32_t chann
 //   k_patches_t      x -> P^T as split f16 [d padded to 64][rows padded to 64] (K = rows contiguous: what both MFMA operands
 //                    want), a thread = 8 consecutive output positions of one patch column, 16-byte stores
 //   k_transpose_split  the same for a Linear layer's input a [rows][d]: a^T split, through an LDS tile
-//   k_gram_f16x3     partial[s] += X X^T over K range s of the chunk: 128 x 64 tiles, 8 waves, K chunks of 64 through LDS
-//                    (csrc/tron_head.hip's GEMM loop); blockIdx = (tile, K split) so that small d still fills the chip
+//   k_gram2_f16x3    partial[s] += X X^T over K range s of the chunk: 128 x 128 tiles, 16 waves, K chunks of 32 by LDS-DMA;
+//                    blockIdx = (tile, K split) so that small d still fills the chip
 //   k_gram_finish    gram[i][j] = scale * sum_s partial[s][min(i,j)][max(i,j)]          (fixed order: deterministic)
-#ifndef TRON_GRAM_V2         // 0: the register-staged 128 x 64 kernel (A/B measurements)
-#define TRON_GRAM_V2 1
-#endif
-
 namespace {
 
 using namespace tron;
@@ -205,120 +202,10 @@ __global__ __launch_bounds__(256) void k_transpose_split(const float *__restrict
     }
 }
 
-constexpr int GM = 128, GN = 64, GK = 64;
-constexpr int GPITCH = GK * 2 + 32;                // LDS row pitch in bytes: conflict-free ds_read_b128 (tron_head.hip)
-constexpr int G_THREADS = 512;
-constexpr int A_HALF = GM * GPITCH, W_HALF = GN * GPITCH;
-constexpr int G_LDS = 2 * A_HALF + 2 * W_HALF;     // 61 440 bytes: two workgroups per CU
-
-__global__ __launch_bounds__(G_THREADS, 4) void k_gram_f16x3(const f16 *__restrict__ Xh, const f16 *__restrict__ Xl, int d, int dpad,
-                                                             int64_t pitch, int nk, int ksplit, float *__restrict__ partial)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    unsigned char *a_h = lds, *a_l = lds + A_HALF, *w_h = lds + 2 * A_HALF, *w_l = w_h + W_HALF;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave & 3, wn = wave >> 2, li = lane & 15, g = lane >> 4;
-    const int nblocks = dpad / GN, ntiles = ((d + GM - 1) / GM) * nblocks;
-    const int tile = blockIdx.x % ntiles, s = blockIdx.x / ntiles;
-    const int m0 = (tile / nblocks) * GM, n0 = (tile % nblocks) * GN;
-    if (n0 + GN <= m0) return;                                          // strictly below the diagonal: k_gram_finish mirrors
-    const int k_lo = (int)((int64_t)nk * s / ksplit), k_hi = (int)((int64_t)nk * (s + 1) / ksplit);
-    if (k_lo >= k_hi) return;
-
-    f32x4 ra[4], rw[2];
-    auto load_chunk = [&](int kc) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int q = tid + j * G_THREADS, half = q >> 10, r = q & 1023, row = r >> 3, pc = r & 7;
-            int m = m0 + row;
-            m = m < dpad ? m : dpad - 1;
-            ra[j] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const unsigned char *>(half ? Xl : Xh) +
-                                                     ((size_t)m * pitch + (size_t)kc * GK) * 2 + pc * 16);
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int q = tid + j * G_THREADS, half = q >> 9, r = q & 511, row = r >> 3, pc = r & 7;
-            rw[j] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const unsigned char *>(half ? Xl : Xh) +
-                                                     ((size_t)(n0 + row) * pitch + (size_t)kc * GK) * 2 + pc * 16);
-        }
-    };
-    auto store_chunk = [&]() {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int q = tid + j * G_THREADS, half = q >> 10, r = q & 1023, row = r >> 3, pc = r & 7;
-            *reinterpret_cast<f32x4 *>(lds + half * A_HALF + row * GPITCH + pc * 16) = ra[j];
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int q = tid + j * G_THREADS, half = q >> 9, r = q & 511, row = r >> 3, pc = r & 7;
-            *reinterpret_cast<f32x4 *>(lds + 2 * A_HALF + half * W_HALF + row * GPITCH + pc * 16) = rw[j];
-        }
-    };
-
-    f32x4 acc0[2][2], acc1[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            acc0[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            acc1[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-    const int a_off = (wm * 32 + li) * GPITCH + g * 16, b_off = (wn * 32 + li) * GPITCH + g * 16;
-    load_chunk(k_lo);
-    store_chunk();
-    __syncthreads();
-    for (int kc = k_lo; kc < k_hi; ++kc) {
-        if (kc + 1 < k_hi) load_chunk(kc + 1);                          // in flight under the MFMAs
-#pragma unroll
-        for (int sl = 0; sl < GK / 32; ++sl) {
-            f16x8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                ah[t] = *reinterpret_cast<const f16x8 *>(a_h + a_off + t * 16 * GPITCH + sl * 64);
-                al[t] = *reinterpret_cast<const f16x8 *>(a_l + a_off + t * 16 * GPITCH + sl * 64);
-                bh[t] = *reinterpret_cast<const f16x8 *>(w_h + b_off + t * 16 * GPITCH + sl * 64);
-                bl[t] = *reinterpret_cast<const f16x8 *>(w_l + b_off + t * 16 * GPITCH + sl * 64);
-            }
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int n = 0; n < 2; ++n) acc1[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[t], bl[n], acc1[t][n], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int n = 0; n < 2; ++n) acc0[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[t], bh[n], acc0[t][n], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int n = 0; n < 2; ++n) acc1[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[t], bh[n], acc1[t][n], 0, 0, 0);
-        }
-        __syncthreads();
-        if (kc + 1 < k_hi) {
-            store_chunk();
-            __syncthreads();
-        }
-    }
-    // D row = 4 * (lane >> 4) + r, column = lane & 15; this split's partial sums are added to what earlier chunks left
-    float *out = partial + (size_t)s * d * dpad;
-#pragma unroll
-    for (int n = 0; n < 2; ++n) {
-        const int col = n0 + wn * 32 + n * 16 + li;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const f32x4 v = (acc0[t][n] + acc1[t][n] * LO_UNSCALE) * GRAM_UNSCALE;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = m0 + wm * 32 + t * 16 + 4 * g + r;
-                if (m < d) out[(size_t)m * dpad + col] += v[r];
-            }
-        }
-    }
-}
-
-// The same product on 128 x 128 tiles fed by LDS-DMA (TRON_GRAM_V2, the default).  k_gram_f16x3 above stages its operands
-// through registers and ds_write_b128 — 48 stores per K chunk and workgroup at 13 LDS cycles each keep the CU's one store
-// path busy 80 % of the time — and its 128 x 64 tiles pull 49 KB from L2 per 1 M MACs.  Here a 16-wave workgroup (one per CU,
-// 4 waves per SIMD, each wave a 32 x 32 sub-tile) owns a 128 x 128 tile; a K chunk of 32 — rows m0 .. m0+127 and
+// X X^T on 128 x 128 tiles fed by LDS-DMA.  Staging the operands through registers and ds_write_b128 on 128 x 64 tiles (the
+// head GEMM's loop, csrc/tron_head.hip) costs 48 stores per K chunk of 64 and workgroup at 13 LDS cycles each — the CU's one
+// store path busy 80 % of the time — and pulls 49 KB from L2 per 1 M MACs.  Here a 16-wave workgroup (one per CU, 4 waves
+// per SIMD, each wave a 32 x 32 sub-tile) owns a 128 x 128 tile; a K chunk of 32 — rows m0 .. m0+127 and
 // n0 .. n0+127 of X, hi and lo: 32 KB — is copied global -> LDS by 32 `global_load_lds_dwordx4` (2 per wave) into a ring of
 // FOUR stages: three chunks in flight while one is multiplied, one barrier per chunk.  LDS rows are 64 bytes without padding;
 // a row's four 16-byte pieces are stored XOR-ed with (-(row >> 2)) & 3 — the per-lane SOURCE address does the swizzle, the
@@ -395,6 +282,7 @@ __global__ __launch_bounds__(G2_THREADS, 4) void k_gram2_f16x3(const f16 *__rest
             bh[t] = *reinterpret_cast<const f16x8 *>(base + b_off[t]);
             bl[t] = *reinterpret_cast<const f16x8 *>(base + G2_STAGE / 2 + b_off[t]);
         }
+        // (tron_f16x3.hpp's mma_f16x3, open-coded: through the helper this kernel's register allocation comes out differently)
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -503,6 +391,7 @@ __global__ __launch_bounds__(256) void k_gram_nchw(const float *__restrict__ g, 
                 bh[t] = *reinterpret_cast<const f16x8 *>(&lds[buf][0][b_off[t]]);
                 bl[t] = *reinterpret_cast<const f16x8 *>(&lds[buf][1][b_off[t]]);
             }
+            // (interleaved per tile, not mma_f16x3's three sweeps: at TW == 1 there is no block of tiles to spread a sweep over)
 #pragma unroll
             for (int t = 0; t < TW; ++t)
 #pragma unroll
@@ -562,18 +451,10 @@ inline GramPlan gram_plan(int64_t rows_total, int64_t rows_unit, int d)
     if (rows < rows_unit) rows = rows_unit;
     if (rows > rows_total) rows = (rows_total + rows_unit - 1) / rows_unit * rows_unit;
     p.rows_chunk = (rows + 63) / 64 * 64;
-#if TRON_GRAM_V2
     const int nb2 = (p.dpad + G2_T - 1) / G2_T, upper = nb2 * (nb2 + 1) / 2;
     int ks = 768 / upper;                                               // one 16-wave workgroup per CU: three rounds of the chip
-#else
-    const int nblocks = p.dpad / GN, mt = (d + GM - 1) / GM;
-    int upper = 0;
-    for (int bm = 0; bm < mt; ++bm)
-        for (int bn = 0; bn < nblocks; ++bn) upper += (bn * GN + GN > bm * GM);
-    int ks = 2048 / (upper > 0 ? upper : 1);                            // ~8 workgroups per CU in flight over the launch
-#endif
-    const int64_t nk = p.rows_chunk / GK;
-    if (ks > nk / 16) ks = (int)(nk / 16);                              // a split walks at least 16 K chunks
+    const int64_t nk = p.rows_chunk / 64;
+    if (ks > nk / 16) ks = (int)(nk / 16);                              // a split walks at least 16 x 64 rows of K
     if (ks < 1) ks = 1;
     if (ks > 256) ks = 256;
     p.ksplit = ks;
@@ -585,24 +466,12 @@ inline GramPlan gram_plan(int64_t rows_total, int64_t rows_unit, int d)
 
 int gram_pass(const f16 *xh, const f16 *xl, const GramPlan &p, int d, int64_t rows_pad, float *partial, hipStream_t st)
 {
-    static uint64_t prepared = 0;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return TRON_ERR_NO_DEVICE; }
-    if (!(prepared & (1ull << (dev & 63)))) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_gram_f16x3), hipFuncAttributeMaxDynamicSharedMemorySize, G_LDS) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(k_gram2_f16x3), hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS) != hipSuccess)
-            (void)hipGetLastError();
-        prepared |= 1ull << (dev & 63);
-    }
-#if TRON_GRAM_V2
+    if (current_device(dev) != TRON_OK) return TRON_ERR_NO_DEVICE;
+    allow_lds<k_gram2_f16x3>(dev, G2_LDS);
     const int nb2 = (p.dpad + G2_T - 1) / G2_T;
     hipLaunchKernelGGL(k_gram2_f16x3, dim3((unsigned)(nb2 * nb2 * p.ksplit)), dim3(G2_THREADS), G2_LDS, st, xh, xl, d, p.dpad, rows_pad,
                        (int)(rows_pad / G2_K), p.ksplit, partial);
-#else
-    const int ntiles = ((d + GM - 1) / GM) * (p.dpad / GN);
-    hipLaunchKernelGGL(k_gram_f16x3, dim3((unsigned)(ntiles * p.ksplit)), dim3(G_THREADS), G_LDS, st, xh, xl, d, p.dpad, rows_pad,
-                       (int)(rows_pad / GK), p.ksplit, partial);
-#endif
     return hipGetLastError() == hipSuccess ? TRON_OK : TRON_ERR_LAUNCH;
 }
 

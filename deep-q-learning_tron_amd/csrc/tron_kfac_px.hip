@@ -284,7 +284,9 @@ template <class C>
 int64_t kfac_px_run(const float *x, const unsigned char *x_px16, int64_t B, float scale, float *gram, void *workspace, hipStream_t st, bool size_only)
 {
     static_assert(C::NB <= 8, "bands");
-    const int cus = device_cus();
+    int dev = 0;
+    const int no_device = current_device(dev);
+    const int cus = no_device ? 256 : device_cus(dev);                   // (a size query needs no device: it plans for 256 CUs)
     int per_kind = cus / 5;
     if (per_kind < C::NB) per_kind = C::NB;
     int slabs[8], tot = 0;
@@ -309,14 +311,8 @@ int64_t kfac_px_run(const float *x, const unsigned char *x_px16, int64_t B, floa
     if (size_only) return px_bytes + part_bytes + 256;
     unsigned char *px = reinterpret_cast<unsigned char *>(workspace);      // (x_px16 given: the image is read where it is; the slot stays unused)
     float *partial = reinterpret_cast<float *>(px + px_bytes);
-    static uint64_t prepared = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return TRON_ERR_NO_DEVICE; }
-    if (!(prepared & (1ull << (dev & 63)))) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_kfac_px<C>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS) != hipSuccess)
-            (void)hipGetLastError();
-        prepared |= 1ull << (dev & 63);
-    }
+    if (no_device) return no_device;
+    allow_lds<k_kfac_px<C>>(dev, C::LDS);
     if (wgs != used && hipMemsetAsync(partial, 0, (size_t)part_bytes, st) != hipSuccess) { (void)hipGetLastError(); return TRON_ERR_LAUNCH; }
     const int64_t total = B * (C::C / 8) * C::SS;
     if (!x_px16)

@@ -1,5 +1,5 @@
 """What the tests of csrc/tron_kfac.hip's Gram kernels share (tests/test_gpu_kfac_gram.py, tests/test_kfac_gram_model_cpu.py):
-the host plan of the file written out again in Python (TRON_GRAM_V2 = 1), float64 references of the factor and of the
+the host plan of the file written out again in Python, float64 references of the factor and of the
 three-term split-f16 product the kernels define, the condition under which that product is exact in f32 whatever the order of
 the additions, the inputs, and the one table of cases both test files run.  A plain module, imported by name; nothing here
 needs a GPU.

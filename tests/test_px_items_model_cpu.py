@@ -66,7 +66,7 @@ def test_launchers_are_what_the_model_restates(source):
         assert line in source, line
     with open(KERNEL_HPP) as f:
         hpp = f.read()
-    for line in ("const int64_t nitems = (B + G::IPI - 1) / G::IPI * G::NB;", "int grid = device_cus() / G::NB * G::NB;",
+    for line in ("const int64_t nitems = (B + G::IPI - 1) / G::IPI * G::NB;", "int grid = device_cus(dev) / G::NB * G::NB;",
                  "if (nitems < grid) grid = (int)nitems;", "for (; item < nitems; item += (int)gridDim.x, cur ^= 1) {",
                  "const int band = blockIdx.x % G::NB;", "const int ip = item / G::NB;"):
         assert line in hpp, line
