@@ -36,6 +36,12 @@ __device__ __forceinline__ M from_row_below(M v)                     // lane r <
     else
         return (M)dpp_from_below((uint32_t)v);
 }
+// the cells a frontier reaches in one level, walls and all (k_moves, k_search)
+template <typename M>
+__device__ __forceinline__ M spread(M f)
+{
+    return (M)((f << 1) | (f >> 1) | from_row_above<M>(f) | from_row_below<M>(f));
+}
 // sums over the GROUP consecutive lanes that hold one board (every lane gets the result)
 template <int GROUP>
 __device__ __forceinline__ int group_sum(int v)
@@ -57,6 +63,8 @@ __device__ __forceinline__ int popc(M v)
 // three consecutive words of a plane.
 // Words of one plane of a board of G cells: the cells, and two words of slack behind the last one for row_bits.
 __host__ __device__ inline int plane_words(int G) { return ((G + 31) >> 5) + 2; }
+// LDS of a board that is held as its three bit planes and nothing else (k_moves, k_search), a multiple of 16 bytes.
+__host__ __device__ inline int planes_lds(int G) { return (12 * plane_words(G) + 15) & ~15; }
 
 // Bits [start, start + S) of a bit plane, S <= 34: three words cover them wherever they start.
 template <typename M>

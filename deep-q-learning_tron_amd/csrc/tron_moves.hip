@@ -34,16 +34,7 @@ using namespace tron;
 constexpr int MV_BLOCK = 256;
 constexpr int MV_WAVES = MV_BLOCK / 64;
 
-// LDS of one board: the three bit planes of `plane_words` words.
-__host__ __device__ inline int board_lds(int G) { return (12 * plane_words(G) + 15) & ~15; }
-
-// the cells a frontier reaches in one level, walls and all
-template <typename M>
-__device__ __forceinline__ M spread(M f)
-{
-    return (M)((f << 1) | (f >> 1) | from_row_above<M>(f) | from_row_below<M>(f));
-}
-
+// spread(): the cells a frontier reaches in one level, walls and all (tron_flood.hpp)
 // GROUP lanes per board (one lane per row), 64 / GROUP boards per wave, MV_WAVES waves per block.
 template <typename M, int GROUP>
 __global__ __launch_bounds__(MV_BLOCK) void k_moves(const int8_t *__restrict__ codes, int64_t n, int S,
@@ -55,7 +46,7 @@ __global__ __launch_bounds__(MV_BLOCK) void k_moves(const int8_t *__restrict__ c
     const int grp = lane / GROUP, row = lane % GROUP, slot = wave * BPW + grp;
     const int64_t board = (int64_t)blockIdx.x * (MV_WAVES * BPW) + slot;
     const int G = S * S;
-    uint32_t *planes = reinterpret_cast<uint32_t *>(reinterpret_cast<int8_t *>(mv_lds) + (size_t)slot * (size_t)board_lds(G));
+    uint32_t *planes = reinterpret_cast<uint32_t *>(reinterpret_cast<int8_t *>(mv_lds) + (size_t)slot * (size_t)planes_lds(G));
     const bool have = board < n;
 
     // ---- the board in, then my row as masks
@@ -137,7 +128,7 @@ template <typename M, int GROUP>
 void launch_moves(const int8_t *codes, int64_t n, int S, int32_t *out_moves, int8_t *out_actions, hipStream_t st)
 {
     constexpr int per_block = MV_WAVES * (64 / GROUP);
-    const size_t smem = (size_t)per_block * (size_t)board_lds(S * S);          // at most 3 328 bytes (side 32)
+    const size_t smem = (size_t)per_block * (size_t)planes_lds(S * S);          // at most 3 328 bytes (side 32)
     const dim3 grid((unsigned)((n + per_block - 1) / per_block));
     hipLaunchKernelGGL((k_moves<M, GROUP>), grid, dim3(MV_BLOCK), smem, st, codes, n, S, out_moves, out_actions);
 }

@@ -23,7 +23,7 @@ def model_actions(model, planes, prob_plane, env_vec):
 
 
 def rating(model, model2=None, n_games=10000, slides=None, width=10, gamemode="ice", fair=True, seed=0x5EED,
-           max_steps=None, verbose=True, mc_weights=None, mc_judge=None, mc_steps=None):
+           max_steps=None, verbose=True, mc_weights=None, mc_judge=None, mc_steps=None, search_plies=2):
     """Returns a list of dicts {slide, p1_win, p2_win, draw, p1_rate} (play.py:76-98).
     model2="minimax" seats MinimaxPlayer(2, "voronoi") as player 2 — the "minimax rating" that
     ACKTR.py:408-421 logs (there it is played net against net).  model2="montecarlo" seats the flat Monte-Carlo
@@ -35,7 +35,8 @@ def rating(model, model2=None, n_games=10000, slides=None, width=10, gamemode="i
     those playouts (None: width * width); mc_judge="territory" judges the playouts that mc_steps cuts off by territory,
     mc_judge="fill" by the checkerboard fill bound (VecTron.montecarlo_actions' judge=).  model2="lookahead" seats the
     one-ply lookahead (VecTron.lookahead_actions: the safe move behind which player 2 reaches most cells first) in any
-    gamemode; its pick looks at no slide."""
+    gamemode; its pick looks at no slide.  model2="search" seats the maximin search (VecTron.search_actions: search_plies =
+    1, 2 or 3 joint moves deep, territory at the leaves) in any gamemode; like the lookahead it looks at no slide."""
     model2 = model2 or model
     if model2 == "montecarlo" and gamemode not in (None, "none"):
         raise ValueError('model2="montecarlo" plays mode None\'s rule: gamemode must be None or "none"')
@@ -61,6 +62,8 @@ def rating(model, model2=None, n_games=10000, slides=None, width=10, gamemode="i
             a2 = env.montecarlo_actions(2, k_steps=mc_steps, call=t, rates=True, weights=mc_weights, judge=mc_judge)
         elif model2 == "lookahead":
             a2 = env.lookahead_actions(2)
+        elif model2 == "search":
+            a2 = env.search_actions(2, plies=search_plies)
         else:
             a2 = env.minimax_actions(2) if isinstance(model2, str) else model_actions(model2, planes[:, 1], prob_plane, env2)
         obs, _, done, _ = env.step(torch.stack([a1, a2], 1), autoreset=False)

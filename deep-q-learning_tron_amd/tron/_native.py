@@ -66,6 +66,7 @@ SIGNATURES = {
     "tron_territory_codes": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
     "tron_reach_codes": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
     "tron_moves_codes": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
+    "tron_search_codes": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "tron_extract_patches":(C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "tron_kfac_patch_gram": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
     "tron_kfac_patch_gram_workspace": (C.c_int64, [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),

@@ -316,6 +316,24 @@ class VecTron:
         out.copy_(actions)
         return out
 
+    def search(self, plies=2, want_actions=True):
+        """search_codes on every env's current board (the player-1 codes playout takes): (values int32 [N, 2, 4],
+        actions int8 [N, 2] | None).  The env itself is left exactly as it was; a finished env's row is what search_codes
+        makes of its image."""
+        return search_codes(self._p1_codes(), plies=plies, want_actions=want_actions)
+
+    def search_actions(self, player, plies=2, out=None):
+        """The maximin search opponent, lookahead_actions' deeper counterpart: int8 [N], `player`'s (1|2) pick of
+        search_codes — the first move whose worst case over the opponent's four replies, `plies` joint moves deep with
+        territory at the leaves, is greatest.  One launch, no draws; no slide is looked at in any mode."""
+        if int(player) not in (1, 2):
+            raise ValueError("player is 1 or 2")
+        actions = self.search(plies=plies)[1][:, int(player) - 1]
+        if out is None:
+            return actions.contiguous()
+        out.copy_(actions)
+        return out
+
     def slide_rates(self):
         """float64 [N, 2] on the device: the rate each player's `random.random() <= rate` meets in this env's mode
         (game.py:169) — ice: the env's slide for both players; temper: get_rate(degree, weight[p]) in game.py:100-102's
@@ -657,6 +675,32 @@ def moves_codes(codes, want_actions=True):
 def safe_moves(moves):
     """moves_codes' moves [n, 2, 4, 3] as safe-move masks, bool [n, 2, 4]: room >= 0."""
     return moves[..., 0] >= 0
+
+
+SEARCH_REJECTED = -2 ** 31                                             # search_codes' eight values of a rejected board
+
+
+def search_codes(codes, plies=2, want_actions=True):
+    """Exact maximin move values of a stack of observation-code boards int8 [n, S, S], `plies` = 1, 2 or 3 joint moves deep
+    (tron_search_codes; the boards and open cells of territory_codes).  Returns (values int32 [n, 2, 4], actions int8
+    [n, 2] or None).  T_p(a) is the cell beside head p (0: the +10 head) in direction a = UP, RIGHT, DOWN, LEFT, and the
+    move is safe when that cell is open.  A joint move (a for player 1, b for player 2) follows mode None's step rule:
+    both unsafe, or both safe onto the same cell, is a draw; exactly one unsafe, the other player wins; otherwise the
+    child position has both targets closed and the heads on them, the old head cells staying closed.  At a node reached
+    after k joint moves with r plies left, V_p = first_p - first_q of territory_codes when r = 0; else V_p = max over a
+    of U_p(a), U_p(a) = min over all four b of W_p(a, b), W_p = 0 on a draw, +(2048 - k) if p wins the joint move,
+    -(2048 - k) if p loses it, V_p(child, r - 1) otherwise.  All 16 joint moves are judged by the rule; V_1 and V_2 are
+    separate maximins over the same leaves.  values[i, p, a] = the root's U_p(a); actions[i, p] = the first direction of
+    the greatest U_p, always 0..3 on a playable board.  A rejected board (not exactly one +10 and one -10 inside the
+    border) gets eight SEARCH_REJECTED and actions of -1."""
+    c, n, side = _boards(codes, "search_codes")
+    cp = nat.ptr(c)                                                    # a host tensor is refused here
+    values = torch.empty(n, 2, 4, dtype=torch.int32, device=c.device)
+    actions = torch.empty(n, 2, dtype=torch.int8, device=c.device) if want_actions else None
+    with torch.cuda.device(c.device):
+        nat.check(nat.lib().tron_search_codes(cp, n, side, int(plies), nat.ptr(values), nat.ptr(actions), nat.stream_ptr()),
+                  "tron_search_codes")
+    return values, actions
 
 
 def playout_values(codes, k_steps, copies=1, seed=0x5EED, stream_id=0, call=0, want_actions=True, rates=None, weights=None,

@@ -626,6 +626,39 @@ int tron_moves_codes(const int8_t *codes, int64_t n, int32_t side,
                      int8_t  *out_actions,  /* i8[n][2]        or NULL */
                      void *stream);
 
+/* ---- search: exact maximin move values one to three plies deep (csrc/tron_search.hip) ----------------------------------
+ * Every joint line of `plies` simultaneous moves, territory at the leaves, a maximin per player, integers throughout, one
+ * launch.  Not the reference's minimax (tron_minimax_codes): that tree alternates turns; this one is the game's own rule.
+ * position   a board is read exactly as tron_territory_codes reads it: the open cells O are byte 1 strictly inside the
+ *            border; the heads h1 (+10) and h2 (-10) are closed; a board without exactly one of each strictly inside the
+ *            border is REJECTED.  Directions a are 0..3 = UP, RIGHT, DOWN, LEFT.  T_p(a) is the cell beside h_p in
+ *            direction a; player p's move a is safe when T_p(a) is in O.
+ * joint move player 1 moves a, player 2 moves b; mode None's step rule:
+ *              both unsafe, or both safe with T_1(a) == T_2(b): a draw;
+ *              exactly one unsafe: the other player wins;
+ *              otherwise the child position is O' = O \ {T_1(a), T_2(b)} with heads T_1(a), T_2(b); the old head cells
+ *              stay closed.
+ * values     for player p and opponent q at a node reached after k joint moves, with r plies left:
+ *              r = 0: V_p = first_p - first_q, tron_territory_codes' first1 and first2 of the node's position, taken from
+ *                     p's side;
+ *              r > 0: V_p = max over a of U_p(a), and U_p(a) = min over all four b of W_p(a, b), where W_p is 0 on a draw,
+ *                     +(2048 - k) if p wins the joint move, -(2048 - k) if p loses it (win sooner, lose later), and
+ *                     V_p(child, r - 1) otherwise.
+ *            All 16 joint moves are judged by the rule: no special case for an unsafe move or a boxed-in player.
+ *            |first_p - first_q| <= 1022 < 2048 - 2, so a decided line always outranks territory.  V_1 and V_2 are
+ *            separate maximins over the same leaves, not negatives of each other.
+ * plies      1, 2 or 3.
+ * out_values i32[n][2][4] or NULL: [i][p][a] = the root's U_p(a) with r = plies.  Eight INT32_MIN for a REJECTED board.
+ * out_actions i8[n][2] or NULL: [i][p] = the first direction of the greatest U_p, always 0..3 on a playable board; -1 for
+ *            both players of a REJECTED board.
+ * TRON_ERR_BAD_ARG: codes == NULL with n > 0, n < 0, n >= 2^31; TRON_ERR_UNSUPPORTED: side outside 6..34 or plies outside
+ * 1..3.  Bad arguments are reported before anything unsupported.  n == 0, or both outputs NULL, launches nothing and
+ * returns TRON_OK.  Nothing outside [0, n) of an output is written.  codes is only read and may sit at any alignment.  */
+int tron_search_codes(const int8_t *codes, int64_t n, int32_t side, int32_t plies,
+                      int32_t *out_values,   /* i32[n][2][4] or NULL */
+                      int8_t  *out_actions,  /* i8[n][2]     or NULL */
+                      void *stream);
+
 /* ---- K-FAC helper of the ACKTR path (Net/kfac.py:28-38 `_extract_patches`; its TODO at kfac.py:9-12
  * asks for this kernel) -------------------------------------------------------------------------- */
 /* x f32[batch][channels][height][width] -> out f32[batch*OH*OW][channels*kh*kw], row = (sample, oy, ox),
